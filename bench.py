@@ -9,7 +9,12 @@ with the tree rebuilt on every evaluation (the reference CPU driver's behaviour)
 says otherwise.  Inputs are the reference's synthetic Gaussian ball (main3.cu:113-137 over the stream of
 :662-664, produced by the library's host-only nbco_init_gaussian) resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps once, writes its outputs when asked to and prints the line.  --full adds
+what the headline does not need: the median of --repeats timed regions, the roofline entry (HIP events around the near-field
+launches), the extra legs (tree reuse, mutual near field, late phase, strong scaling, octree, nbco3 / nbco3_dist) and the
+CPU baseline.
 
 With N > 1 and no WORLD_SIZE in the environment the parent starts N fresh rank processes itself (before it
 touches torch or the GPU) and relays rank 0's JSON line; under torchrun (WORLD_SIZE set) every process is one
@@ -31,6 +36,8 @@ if ROOT not in sys.path:
 
 FP32_VECTOR_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md "Peak FP32 (vector)"
 FLOP_PER_PAIR = 20                   # one directed pair interaction = 20 flop
+DUMP_BYTES_MAX = 64 * 10 ** 6        # --dump-outputs: every file of one run together
+DUMP_SEED = 1248                     # --dump-outputs: the row sample drawn above that size
 
 
 def parse(argv=None):
@@ -61,9 +68,16 @@ def parse(argv=None):
     ap.add_argument("--step-calls", action="store_true", help="one nbco_integrate call per step instead of one nbco_integrate_steps call for the timed region")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the tree-reuse, strong-scaling, octree and nbco3 CLI legs after the timed region")
     ap.add_argument("--cpu-steps", type=int, default=6)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (warm-up + K steps between two barriers) is run this many times from the same initial state; "
-                         "value / ms_per_step are the median, every repeat is listed")
+                         "value / ms_per_step are the median, every repeat is listed (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: --repeats 5 by default, the roofline entry, the extra legs and "
+                         "the CPU baseline (--no-extra-legs / --no-cpu-baseline still drop theirs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state they computed as DIR/pos.npy, vel.npy, acc.npy (float32, rows as the "
+                         "engine holds them; one set per rank with a .rank<r> suffix in a sharded run); above %d MB in all, a fixed "
+                         "seeded sample of the rows" % (DUMP_BYTES_MAX // 10 ** 6))
     ap.add_argument("--dump-state", metavar="PREFIX", default=None,
                     help="tests: every rank writes its [pos | vel | acc] rows after the last timed step to PREFIX.rank<r>.npy")
     ap.add_argument("--strict", action="store_true",
@@ -76,7 +90,10 @@ def parse(argv=None):
                     help="diagnostics: start from a state written by --dump-state (one GPU) instead of the Gaussian ball, e.g. a late phase")
     ap.add_argument("--engine-opt", action="append", default=[], metavar="KEY=VALUE",
                     help="diagnostics: an nbco_opts field for the engine, e.g. p2p_mutual=0 (one-directional near-field kernel) or m2l_first=1")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # ---- N > 1 without a launcher: start the ranks ourselves --------------------------------------------------------------
@@ -201,6 +218,21 @@ def coulomb_params(n_system):
     """par[] of main3.cu:685-692: {xi / N, 0, 0, omega0^2}"""
     om = np.array(OMEGA0, dtype=np.float32)
     return np.array([np.float32(XI) / np.float32(n_system), 0, 0, om[0] * om[0], om[1] * om[1], om[2] * om[2]], dtype=np.float32)
+
+
+def dump_outputs(dirname, state, writers=1, suffix=""):
+    """--dump-outputs: the [pos | vel | acc] rows of `state` (3 x n x 3 float32) as DIR/pos<suffix>.npy, vel<suffix>.npy and
+    acc<suffix>.npy.  When the rows of all `writers` together would exceed DUMP_BYTES_MAX, each writer keeps the same fixed sample
+    of its rows (drawn with DUMP_SEED, in row order).  Returns the number of rows written."""
+    state = np.asarray(state, dtype=np.float32).reshape(3, -1, 3)
+    n = state.shape[1]
+    cap = (DUMP_BYTES_MAX // writers - 3 * 1024) // state[:, :1].nbytes      # (1 KB for each .npy header)
+    if n > cap:
+        state = state[:, np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in zip(("pos", "vel", "acc"), state):
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(a))
+    return state.shape[1]
 
 
 def host_cpu():
@@ -420,8 +452,11 @@ def main():
 
     fallbacks = []     # every switch from a default form to its all-gather form, with the reason (empty = the defaults ran)
 
-    def timed_run(n_local, steps, warmup, profile, repeats=1):
-        """`repeats` times from the same initial state: accelerations, warm-up, then `steps` leapfrog steps between two barriers.
+    dumped = {}        # --dump-outputs: what the main timed run wrote
+
+    def timed_run(n_local, steps, warmup, profile, repeats=1, dump=False):
+        """`repeats` times from the same initial state: accelerations, warm-up, then `steps` leapfrog steps between two barriers;
+        `dump`: this is the run whose state --dump-state / --dump-outputs write.
         Returns (elapsed of every repeat, max over ranks; engine, run, run_steps, profile, particles of the system)"""
         n_sys = world * n_local if sharded else n_local      # particles of ONE physical system
         # every rank draws n_local particles of the same Gaussian ball from its own stream; sharded run: their union is the
@@ -543,11 +578,17 @@ def main():
         prof = eng.profile_get() if profile else None
         state = run.buf if (sharded or slabbed) else d
         assert torch.isfinite(state).all(), "non-finite state after the timed steps"
-        if args.dump_state and profile:
+        if args.dump_state and dump:
             np.save("%s.rank%d.npy" % (args.dump_state, rank), state.detach().cpu().numpy().reshape(3, -1, 3))
+        if args.dump_outputs and dump and not (slabbed and rank > 0):     # (slabs: every rank holds the whole state)
+            per_rank = sharded and world > 1
+            dumped["rows"] = dump_outputs(args.dump_outputs, state.detach().cpu().numpy(), world if per_rank else 1,
+                                          ".rank%d" % rank if per_rank else "")
+            dumped["of_rows"] = state.numel() // 9
         return times, eng, run, run_steps, prof, n_sys
 
-    times, eng, run, run_steps, prof, n_sys = timed_run(n, args.steps, args.warmup, True, args.repeats)
+    # the plain run times its K steps once and records no events; --full keeps the roofline's events around the near-field launches
+    times, eng, run, run_steps, prof, n_sys = timed_run(n, args.steps, args.warmup, args.full or args.profile_all, args.repeats, dump=True)
     elapsed = sorted(times)[len(times) // 2]       # the median repeat is the value
 
     if args.workload == "fmm_kd":
@@ -581,7 +622,7 @@ def main():
         pairs_per_eval = n * n
         extra = {}
     pairs_all = reduce(float(pairs_per_eval), dist.ReduceOp.SUM)
-    legs = not args.no_extra_legs
+    legs = args.full and not args.no_extra_legs
 
     # the reference's GPU driver rebuilds the kd-tree every tree_steps = 8 evaluations (fmm_cart3_kdtree.cuh:1619); the
     # headline value above rebuilds every step (CPU-driver semantics), this is the amortised figure beside it
@@ -700,6 +741,7 @@ def main():
         "near_field_mutual": mutual,
         "late_phase": late,
         "strong": strong,
+        "full": args.full,
         "config": {"workload": wl, "n_per_gpu": n, "order": args.order, "dt": args.dt,
                    "init": "reference stream mt19937_64(%d + rank), discard %d (main3.cu:662-664)" % (REF_SEED, REF_DISCARD),
                    "parallelism": ("kd-domain sharding x%d, %s per evaluation" % (world, "LET exchange (all-gather of traversal records, all-to-all of the listed multipoles + positions)" if run.let else "one all-gather of nodes + positions")) if sharded
@@ -707,14 +749,14 @@ def main():
     }
     # the near-field launch of every rank: (average duration, directed pairs) -> min / max fraction of the peak over the ranks
     rank_fracs = None
-    if world > 1 and pairs_per_eval and prof[dom][1]:
+    if args.full and world > 1 and pairs_per_eval and prof[dom][1]:
         mine = torch.tensor([prof[dom][0] * 1e-3 / prof[dom][1], float(pairs_per_eval)], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         rank_fracs = [float(t[1]) * FLOP_PER_PAIR / float(t[0]) / 1e12 / FP32_VECTOR_PEAK_TFLOPS for t in allr]
-    if rank == 0:
+    if rank == 0 and prof is not None:
         ms, launches = prof[dom]
-        if launches and pairs_per_eval:
+        if args.full and launches and pairs_per_eval:
             avg_s = ms * 1e-3 / launches
             ach = pairs_per_eval * FLOP_PER_PAIR / avg_s / 1e12
             kname = ("p2p_mutual_kernel" if args.workload == "fmm_kd" and info.p2p_halves else "p2p_kernel") if dom == "p2p" else "direct_tiles"
@@ -772,9 +814,11 @@ def main():
                 out["cli_dist"] = cli_dist_leg(world, n_sys, args.order, args.warmup + args.steps, args.tree_steps, args.rebalance)
             except Exception as e:
                 out["cli_dist"] = {"error": str(e)[:200]}
-        if not args.no_cpu_baseline and args.workload != "fmm_oct":
+        if args.full and not args.no_cpu_baseline and args.workload != "fmm_oct":
             # (also on the N > 1 lines: rank 0's host, after the timed region; the per-GPU workload of --particles)
             out["cpu_baseline"] = cpu_baseline(args, n)
+        if dumped:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": ["pos", "vel", "acc"], "dtype": "f32", **dumped}
         sys.stdout.flush()
         os.dup2(json_fd, 1)
         print(json.dumps(out), flush=True)

@@ -49,11 +49,11 @@ def test_failing_rank_fails_the_run(tmp_path):
 
 @pytest.mark.gpu
 def test_two_ranks_on_one_card_through_the_real_path(engine_lib):
-    """`bench.py --gpus 2 --backend gloo --particles 65536 --steps 2`: two processes, two engine contexts on the one card,
-    collectives over gloo -- DomainRun with the HIP engine and a real process group."""
+    """`bench.py --gpus 2 --backend gloo --particles 65536 --steps 2 --full`: two processes, two engine contexts on the one card,
+    collectives over gloo -- DomainRun with the HIP engine and a real process group (--full: the strong-scaling leg too)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--particles", "65536",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, env=env, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 2 and out["config"]["n_system"] == 131072

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     args = sys.argv[1:]
-    rounds, bench_args = 3, "--no-cpu-baseline --repeats 3"
+    rounds, bench_args = 3, "--full --no-cpu-baseline --repeats 3"
     while args and args[0].startswith("--"):
         if args[0] == "--rounds":
             rounds = int(args[1]); args = args[2:]

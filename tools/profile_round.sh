@@ -8,7 +8,7 @@ tag=$1
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT || exit 1
-B="bench.py --no-extra-legs --no-cpu-baseline --steps 30"
+B="bench.py --full --no-extra-legs --no-cpu-baseline --steps 30"
 echo "[$(date +%T)] kernel trace" | tee -a $out/progress.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o out -- python3 $B > $out/bench_under_rocprof.json 2> $out/kt.err || exit 2
 echo "[$(date +%T)] FETCH_SIZE" | tee -a $out/progress.txt
@@ -23,7 +23,7 @@ timeout -k 10 200 ./build/pair_ceiling $out/pair_ceiling.json > $out/pair_ceilin
 timeout -k 10 200 ./build/valu_probe $out/valu_probe.json 5 > $out/valu_probe.txt 2>&1 || exit 7
 NBCO_P2P_DUMP=/tmp/p2p_$tag.bin timeout -k 10 200 python3 tools/p2p_dump.py > $out/p2p_dump.txt 2>&1 && timeout -k 10 200 ./build/p2p_lab /tmp/p2p_$tag.bin $out/p2p_lab.json > $out/p2p_lab.txt 2>&1 || exit 7
 echo "[$(date +%T)] default bench" | tee -a $out/progress.txt
-timeout -k 10 400 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 8
+timeout -k 10 400 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 8
 # condense on the box (the raw traces exceed what gpurun copies back), keep the summaries, drop the raw files
 echo "[$(date +%T)] summaries" | tee -a $out/progress.txt
 f() { find $out/$1 -name "$2" | head -1; }

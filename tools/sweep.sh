@@ -5,7 +5,7 @@ mkdir -p $out
 run() { # name, env..., -- args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 200 python bench.py --no-extra-legs --no-cpu-baseline --profile-all "$@" > $out/$name.json 2> $out/$name.err || return 1
+  env "${envs[@]}" timeout -k 10 200 python bench.py --full --no-extra-legs --no-cpu-baseline --profile-all "$@" > $out/$name.json 2> $out/$name.err || return 1
   python3 - "$name" "$out/$name.json" >> $out/sweep.txt <<'PY'
 import json,sys
 d=json.load(open(sys.argv[2]))
