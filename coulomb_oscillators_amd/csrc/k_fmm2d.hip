@@ -1,0 +1,800 @@
+// k_fmm2d.hip -- the 2-D fp64 evaluators of the reference's `nbco` program (Simulation/main.cu, DIM 2, SCAL double):
+// the -log r pair law a_i += d / (|d|^2 + EPS2), d = x_i - x_j (direct.cuh:23-26, appel.cuh:293-297), the direct sums
+// `direct2` / `direct3` (direct.cuh:171,233) and the uniform-quadtree FMM `fmm_cart` (fmm_cart.cuh:395-544), plus the
+// double-precision step / elastic / rescale kernels and the integrator sequence of integrator.cuh:32-167.
+//
+// FMM in complex form.  With z = x + iy and f(z) = sum_j 1 / (z - z_j), the field is a = conj(f).  A 2-D traceless tensor of
+// order k has two components, so the reference's expansions map one-to-one onto complex coefficients:
+//   multipole about c   a_k = sum_j (z_j - c)^k,  k = 0..p (a_1 = 0 about the centroid, not computed: fmm_cart.cuh:68-96)
+//   local about c       f(z) = sum_l b_l (z - c)^l,  l = 0..p-1 (the reference's local orders 1..p, the field's Taylor terms)
+//   M2L                 b_l += (-1)^l C(k+l, l) a_k w^(k+l+1),  w = conj(D) / (|D|^2 + EPS2) (= 1/D softened), D = c_t - c_s
+//                       square truncation: k = 0..p, l = 0..p-1, total order k + l + 1 = 1..2p (fmm_cart_base.cuh:757-798)
+//   M2M / L2L           exact binomial shifts of the truncated series (fmm_cart.cuh:116-188, 288-334)
+// Cells are the reference's: keys ix * side + iy with x slowest (appel.cuh:44-55), a stable radix sort over 2L bits, and
+// positions AND velocities left in cell order (fmm_cart.cuh:500-504).
+//
+// Kernel plan per evaluation (L levels): minmax partials, scalars, keys, radix sort, gather, cell ranges, P2M, L-2 M2M, one M2L
+// launch for all levels, L-2 L2L, and the near field fused with L2P and the rescale.  No atomics anywhere: every sum has a fixed
+// order, so results are bit-reproducible.
+#include "nbco_internal.hpp"
+#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <cmath>
+#include <random>
+
+namespace {
+
+constexpr int kB = 256;        // threads per block of the 1-D kernels
+constexpr int kNear = 64;      // one wave per target cell in the near-field kernel
+constexpr int kRedBlocks = 512;
+constexpr int kMaxL2 = 15;     // 2L <= 30: keys stay below 2^30
+
+static int grid_for(long long n, int cap = 1 << 20) { return (int)std::max<long long>(1, std::min<long long>((n + kB - 1) / kB, cap)); }
+__host__ __device__ inline long long quad_beg(int l) { return ((1LL << (2 * l)) - 1) / 3; }
+
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 cscale(double2 a, double s) { return make_double2(a.x * s, a.y * s); }
+
+__host__ __device__ constexpr double binom(int n, int k)
+{
+	double r = 1;
+	for (int i = 1; i <= k; ++i) r = r * (double)(n - k + i) / (double)i;
+	return r;
+}
+
+// ---- basic fp64 kernels (kernel.cuh:100 step, :119 add_elastic, appel.cuh:514 rescale) -----------------------------------------
+__global__ __launch_bounds__(kB) void f2d_axpy_kernel(double *__restrict__ b, const double *__restrict__ a, double ds, long long n2)
+{
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n2; i += (long long)gridDim.x * kB) b[i] += a[i] * ds;
+}
+
+__global__ __launch_bounds__(kB) void f2d_elastic_kernel(const double2 *__restrict__ x, double2 *__restrict__ a, long long n,
+                                                         const double *__restrict__ k)
+{
+	const double kx = k[0], ky = k[1];
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		double2 t = a[i];
+		const double2 p = x[i];
+		t.x -= kx * p.x;
+		t.y -= ky * p.y;
+		a[i] = t;
+	}
+}
+
+// ---- direct sums: all pairs, sources staged through LDS as an x-row and a y-row ------------------------------------------------
+template <bool KAHAN>
+__global__ __launch_bounds__(kB) void f2d_direct_kernel(const double2 *__restrict__ x, double2 *__restrict__ a, long long n, double eps2,
+                                                        const double *__restrict__ param)
+{
+	__shared__ double sx[kB], sy[kB];
+	const long long i = (long long)blockIdx.x * kB + threadIdx.x;
+	const double2 zi = i < n ? x[i] : make_double2(0.0, 0.0);
+	double ax = 0, ay = 0, cx = 0, cy = 0;
+	for (long long j0 = 0; j0 < n; j0 += kB)
+	{
+		__syncthreads();
+		const long long j = j0 + threadIdx.x;
+		if (j < n)
+		{
+			const double2 s = x[j];
+			sx[threadIdx.x] = s.x;
+			sy[threadIdx.x] = s.y;
+		}
+		__syncthreads();
+		const int cnt = (int)std::min<long long>(kB, n - j0);
+		for (int t = 0; t < cnt; ++t)
+		{
+			const double dx = zi.x - sx[t], dy = zi.y - sy[t];
+			const double inv = 1.0 / (dx * dx + dy * dy + eps2);
+			if (KAHAN)
+			{
+				// compensated accumulation (direct.cuh:233 direct3)
+				const double tx = dx * inv - cx, ty = dy * inv - cy;
+				const double nx = ax + tx, ny = ay + ty;
+				cx = (nx - ax) - tx;
+				cy = (ny - ay) - ty;
+				ax = nx;
+				ay = ny;
+			}
+			else
+			{
+				ax += dx * inv;
+				ay += dy * inv;
+			}
+		}
+	}
+	if (i < n)
+	{
+		const double s = param ? param[0] : 1.0;
+		a[i] = make_double2(ax * s, ay * s);
+	}
+}
+
+// ---- mean relative error (reductions.cuh:99 relerrReduce2): fixed-order block sums, then one block over the partials ------------
+__device__ double block_sum(double v, double *sh)
+{
+	sh[threadIdx.x] = v;
+	__syncthreads();
+	for (int s = kB / 2; s > 0; s >>= 1)
+	{
+		if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+		__syncthreads();
+	}
+	const double r = sh[0];
+	__syncthreads();
+	return r;
+}
+
+__global__ __launch_bounds__(kB) void f2d_relerr_kernel(const double2 *__restrict__ x, const double2 *__restrict__ ref, long long n,
+                                                        double *__restrict__ part)
+{
+	__shared__ double sh[kB];
+	double acc = 0;
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		const double2 p = x[i], q = ref[i];
+		const double dx = p.x - q.x, dy = p.y - q.y;
+		// rel_diff1 (reductions.cuh:37-42): the reference row's |ref|^2 is offset by 1e-18
+		acc += std::sqrt(fmax((dx * dx + dy * dy) / (q.x * q.x + q.y * q.y + 1e-18), 0.0));
+	}
+	const double s = block_sum(acc, sh);
+	if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kB) void f2d_relerr_final_kernel(const double *__restrict__ part, int nb, long long n, double *__restrict__ out)
+{
+	__shared__ double sh[kB];
+	double acc = 0;
+	for (int i = threadIdx.x; i < nb; i += kB) acc += part[i];
+	const double s = block_sum(acc, sh);
+	if (threadIdx.x == 0) out[0] = s / (double)n;
+}
+
+// ---- tree build -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kB) void f2d_minmax_kernel(const double2 *__restrict__ x, long long n, double *__restrict__ part)
+{
+	__shared__ double sh[4][kB];
+	double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		const double2 p = x[i];
+		mnx = fmin(mnx, p.x);
+		mny = fmin(mny, p.y);
+		mxx = fmax(mxx, p.x);
+		mxy = fmax(mxy, p.y);
+	}
+	sh[0][threadIdx.x] = mnx;
+	sh[1][threadIdx.x] = mny;
+	sh[2][threadIdx.x] = mxx;
+	sh[3][threadIdx.x] = mxy;
+	__syncthreads();
+	for (int s = kB / 2; s > 0; s >>= 1)
+	{
+		if ((int)threadIdx.x < s)
+		{
+			sh[0][threadIdx.x] = fmin(sh[0][threadIdx.x], sh[0][threadIdx.x + s]);
+			sh[1][threadIdx.x] = fmin(sh[1][threadIdx.x], sh[1][threadIdx.x + s]);
+			sh[2][threadIdx.x] = fmax(sh[2][threadIdx.x], sh[2][threadIdx.x + s]);
+			sh[3][threadIdx.x] = fmax(sh[3][threadIdx.x], sh[3][threadIdx.x + s]);
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x < 4) part[4 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+#pragma clang fp contract(off)
+// scal = {min x, min y, 1 / delta}: delta = max(max - min) / side, clamped below at sqrt(EPS2) (fmm_cart.cuh:476-481)
+__global__ __launch_bounds__(64) void f2d_scalars_kernel(const double *__restrict__ part, int nb, int side, double eps2, double *__restrict__ scal)
+{
+	if (threadIdx.x != 0) return;
+	double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
+	for (int b = 0; b < nb; ++b)
+	{
+		mnx = fmin(mnx, part[4 * b + 0]);
+		mny = fmin(mny, part[4 * b + 1]);
+		mxx = fmax(mxx, part[4 * b + 2]);
+		mxy = fmax(mxy, part[4 * b + 3]);
+	}
+	double delta = fmax(mxx - mnx, mxy - mny) / (double)side;
+	const double eps = std::sqrt(eps2);
+	if (delta < eps) delta = eps;
+	scal[0] = mnx;
+	scal[1] = mny;
+	scal[2] = 1.0 / delta;
+}
+
+// integer cell keys, row-major ix * side + iy (appel.cuh:44-55; to_ivec truncates, clip to [0, side-1])
+__global__ __launch_bounds__(kB) void f2d_keys_kernel(const double2 *__restrict__ x, long long n, const double *__restrict__ scal, int side,
+                                                      uint32_t *__restrict__ keys, uint32_t *__restrict__ idx)
+{
+	const double mnx = scal[0], mny = scal[1], rd = scal[2];
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		const double2 p = x[i];
+		int ix = (int)((p.x - mnx) * rd), iy = (int)((p.y - mny) * rd);
+		ix = std::min(std::max(ix, 0), side - 1);
+		iy = std::min(std::max(iy, 0), side - 1);
+		keys[i] = (uint32_t)(ix * side + iy);
+		idx[i] = (uint32_t)i;
+	}
+}
+#pragma clang fp contract(on)
+
+__global__ __launch_bounds__(kB) void f2d_gather_kernel(const double2 *__restrict__ x, const double2 *__restrict__ v, const uint32_t *__restrict__ idx,
+                                                        double2 *__restrict__ out, long long n)
+{
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		const uint32_t j = idx[i];
+		out[i] = x[j];
+		out[n + i] = v[j];
+	}
+}
+
+// index[c] = first particle of leaf c in the sorted order (c = 0..m; index[m] = n): appel.cuh:141-216
+__global__ __launch_bounds__(kB) void f2d_index_kernel(const uint32_t *__restrict__ keys, long long n, int m, int *__restrict__ index)
+{
+	const int c = blockIdx.x * kB + threadIdx.x;
+	if (c > m) return;
+	long long lo = 0, hi = n;
+	while (lo < hi)
+	{
+		const long long mid = (lo + hi) >> 1;
+		if (keys[mid] < (uint32_t)c) lo = mid + 1;
+		else hi = mid;
+	}
+	index[c] = (int)lo;
+}
+
+struct Quad
+{
+	double2 *center, *mpole, *local;   // [ntot], [ntot][P+1], [ntot][P]
+	int *mult, *index;                 // [ntot], leaf level [m+1]
+};
+
+// P2M about the centroid, orders 0 and 2..P (appel.cuh:222-258, fmm_cart.cuh:68-96)
+template <int P>
+__global__ __launch_bounds__(kB) void f2d_leaf_kernel(Quad q, const double2 *__restrict__ x, int m, long long beg)
+{
+	const int c = blockIdx.x * kB + threadIdx.x;
+	if (c >= m) return;
+	const int b = q.index[c], e = q.index[c + 1], mlt = e - b;
+	double2 t = make_double2(0.0, 0.0);
+	double2 mp[P + 1];
+#pragma unroll
+	for (int k = 0; k <= P; ++k) mp[k] = make_double2(0.0, 0.0);
+	if (mlt > 0)
+	{
+		for (int j = b; j < e; ++j) t = cadd(t, x[j]);
+		t.x /= (double)mlt;
+		t.y /= (double)mlt;
+		for (int j = b; j < e; ++j)
+		{
+			const double2 w = make_double2(x[j].x - t.x, x[j].y - t.y);
+			double2 pw = w;
+#pragma unroll
+			for (int k = 2; k <= P; ++k)
+			{
+				pw = cmul(pw, w);
+				mp[k] = cadd(mp[k], pw);
+			}
+		}
+		mp[0] = make_double2((double)mlt, 0.0);
+	}
+	q.center[beg + c] = t;
+	q.mult[beg + c] = mlt;
+#pragma unroll
+	for (int k = 0; k <= P; ++k) q.mpole[(beg + c) * (P + 1) + k] = mp[k];
+}
+
+// M2M: the four children of a level-l cell, about their charge-weighted centroid (fmm_cart.cuh:116-188)
+template <int P>
+__global__ __launch_bounds__(kB) void f2d_m2m_kernel(Quad q, int l)
+{
+	const int side = 1 << l, sidep = side << 1;
+	const int ij0 = blockIdx.x * kB + threadIdx.x;
+	if (ij0 >= side * side) return;
+	const int i = ij0 / side, j = ij0 - i * side;
+	const long long ij = quad_beg(l) + ij0;
+	const long long ijp = quad_beg(l + 1) + 2LL * (i * sidep + j);
+	const long long ch[4] = {ijp, ijp + 1, ijp + sidep, ijp + sidep + 1};
+	int mlt = 0;
+#pragma unroll
+	for (int s = 0; s < 4; ++s) mlt += q.mult[ch[s]];
+	double2 coord = make_double2(0.0, 0.0);
+	double2 mp[P + 1];
+#pragma unroll
+	for (int k = 0; k <= P; ++k) mp[k] = make_double2(0.0, 0.0);
+	if (mlt > 0)
+	{
+#pragma unroll
+		for (int s = 0; s < 4; ++s) coord = cadd(coord, cscale(q.center[ch[s]], (double)q.mult[ch[s]]));
+		coord.x /= (double)mlt;
+		coord.y /= (double)mlt;
+#pragma unroll
+		for (int s = 0; s < 4; ++s)
+		{
+			if (q.mult[ch[s]] == 0) continue;
+			const double2 cc = q.center[ch[s]];
+			const double2 d = make_double2(cc.x - coord.x, cc.y - coord.y);   // child centre seen from the parent's
+			double2 dp[P + 1];
+			dp[0] = make_double2(1.0, 0.0);
+#pragma unroll
+			for (int k = 1; k <= P; ++k) dp[k] = cmul(dp[k - 1], d);
+			double2 a[P + 1];
+#pragma unroll
+			for (int k = 0; k <= P; ++k) a[k] = q.mpole[ch[s] * (P + 1) + k];
+#pragma unroll
+			for (int k = 2; k <= P; ++k)
+			{
+				double2 acc = cscale(dp[k], a[0].x);
+#pragma unroll
+				for (int r = 2; r <= k; ++r) acc = cadd(acc, cscale(cmul(a[r], dp[k - r]), binom(k, r)));
+				mp[k] = cadd(mp[k], acc);
+			}
+		}
+		mp[0] = make_double2((double)mlt, 0.0);
+	}
+	q.center[ij] = coord;
+	q.mult[ij] = mlt;
+#pragma unroll
+	for (int k = 0; k <= P; ++k) q.mpole[ij * (P + 1) + k] = mp[k];
+}
+
+// M2L for every cell of levels 2..L in one launch: one thread per target, the stencil of its parent's (4r+2)^2 block minus its own
+// (2r+1)^2 neighbourhood (fmm_cart.cuh:214-262); empty sources and empty targets are skipped.  Writes (not accumulates) the locals.
+template <int P>
+__global__ __launch_bounds__(kB) void f2d_m2l_kernel(Quad q, int L, int radius, double eps2)
+{
+	const long long cell = quad_beg(2) + (long long)blockIdx.x * kB + threadIdx.x;
+	if (cell >= quad_beg(L + 1)) return;
+	int l = 2;
+	while (cell >= quad_beg(l + 1)) ++l;
+	const long long beg = quad_beg(l);
+	const int side = 1 << l;
+	const int ij = (int)(cell - beg), i = ij / side, j = ij - i * side;
+	double2 b[P];
+#pragma unroll
+	for (int k = 0; k < P; ++k) b[k] = make_double2(0.0, 0.0);
+	if (q.mult[cell] > 0)
+	{
+		const double2 ct = q.center[cell];
+		const int im = (i / 2) * 2, jm = (j / 2) * 2;
+		const int kmin = std::max(im - 2 * radius, 0), kmax = std::min(im + 2 * radius + 1, side - 1);
+		const int gmin = std::max(jm - 2 * radius, 0), gmax = std::min(jm + 2 * radius + 1, side - 1);
+		for (int k = kmin; k <= kmax; ++k)
+			for (int g = gmin; g <= gmax; ++g)
+			{
+				if (!(k > i + radius || k < i - radius || g > j + radius || g < j - radius)) continue;
+				const long long src = beg + (long long)k * side + g;
+				if (q.mult[src] == 0) continue;
+				const double2 cs = q.center[src];
+				const double dx = ct.x - cs.x, dy = ct.y - cs.y;
+				const double r2 = dx * dx + dy * dy + eps2;
+				const double2 w = make_double2(dx / r2, -dy / r2);
+				double2 a[P + 1];
+#pragma unroll
+				for (int kk = 0; kk <= P; ++kk) a[kk] = q.mpole[src * (P + 1) + kk];
+				double2 wm = make_double2(1.0, 0.0);
+#pragma unroll
+				for (int mm = 1; mm <= 2 * P; ++mm)   // total order k + l + 1
+				{
+					wm = cmul(wm, w);
+#pragma unroll
+					for (int ll = 0; ll < P; ++ll)
+					{
+						const int kk = mm - 1 - ll;
+						if (kk < 0 || kk > P || kk == 1) continue;
+						const double co = ((ll & 1) ? -1.0 : 1.0) * binom(mm - 1, ll);
+						b[ll] = cadd(b[ll], cscale(cmul(a[kk], wm), co));
+					}
+				}
+			}
+	}
+#pragma unroll
+	for (int k = 0; k < P; ++k) q.local[cell * P + k] = b[k];
+}
+
+// L2L into the non-empty cells of level l from their parents (fmm_cart.cuh:288-334)
+template <int P>
+__global__ __launch_bounds__(kB) void f2d_l2l_kernel(Quad q, int l)
+{
+	const int side = 1 << l;
+	const int ij0 = blockIdx.x * kB + threadIdx.x;
+	if (ij0 >= side * side) return;
+	const long long cell = quad_beg(l) + ij0;
+	if (q.mult[cell] == 0) return;
+	const int i = ij0 / side, j = ij0 - i * side;
+	const long long par = quad_beg(l - 1) + (long long)(i / 2) * (side / 2) + j / 2;
+	const double2 cp = q.center[par], cc = q.center[cell];
+	const double2 d = make_double2(cc.x - cp.x, cc.y - cp.y);
+	double2 bp[P], dp[P];
+#pragma unroll
+	for (int k = 0; k < P; ++k) bp[k] = q.local[par * P + k];
+	dp[0] = make_double2(1.0, 0.0);
+#pragma unroll
+	for (int k = 1; k < P; ++k) dp[k] = cmul(dp[k - 1], d);
+#pragma unroll
+	for (int mm = 0; mm < P; ++mm)
+	{
+		double2 acc = q.local[cell * P + mm];
+#pragma unroll
+		for (int ll = mm; ll < P; ++ll) acc = cadd(acc, cscale(cmul(bp[ll], dp[ll - mm]), binom(ll, mm)));
+		q.local[cell * P + mm] = acc;
+	}
+}
+
+// Near field fused with L2P and the rescale (appel.cuh:260-303, fmm_cart.cuh:353-376, :537-539): one wave per target leaf, one
+// target per lane; each of the 2r+1 neighbour rows is one contiguous run of particles, staged through LDS 64 sources at a time.
+// Without COLL the pair sum is skipped and a is multiplied by param[1] (fmm_cart.cuh:527-528).
+template <int P, bool COLL>
+__global__ __launch_bounds__(kNear) void f2d_near_kernel(Quad q, const double2 *__restrict__ x, double2 *__restrict__ a, int L, int radius,
+                                                         double eps2, const double *__restrict__ param)
+{
+	__shared__ double sx[kNear], sy[kNear];
+	const int side = 1 << L;
+	const int m = side * side;
+	const double s0 = param[0], s1 = param[1];
+	const int lane = threadIdx.x;
+	// grid-stride over the leaves: 4^L blocks exceed a dispatch's grid for L >= 13
+	for (int cell = blockIdx.x; cell < m; cell += gridDim.x)
+	{
+	const int b = q.index[cell], e = q.index[cell + 1];
+	if (b == e) continue;   // uniform across the block
+	const long long qc = quad_beg(L) + cell;
+	const int i = cell / side, j = cell - i * side;
+	const int kmin = std::max(i - radius, 0), kmax = std::min(i + radius, side - 1);
+	const int lmin = std::max(j - radius, 0), lmax = std::min(j + radius, side - 1);
+	const double2 c = q.center[qc];
+	double2 bl[P];
+#pragma unroll
+	for (int k = 0; k < P; ++k) bl[k] = q.local[qc * P + k];
+	for (int t0 = b; t0 < e; t0 += kNear)
+	{
+		const int t = t0 + lane;
+		const bool act = t < e;
+		const double2 zi = act ? x[t] : make_double2(0.0, 0.0);
+		double ax = 0, ay = 0;
+		if (COLL)
+		{
+			for (int k = kmin; k <= kmax; ++k)
+			{
+				const int rs = q.index[k * side + lmin], re = q.index[k * side + lmax + 1];
+				for (int s0r = rs; s0r < re; s0r += kNear)
+				{
+					__syncthreads();
+					if (s0r + lane < re)
+					{
+						const double2 sp = x[s0r + lane];
+						sx[lane] = sp.x;
+						sy[lane] = sp.y;
+					}
+					__syncthreads();
+					const int cnt = std::min(kNear, re - s0r);
+					for (int u = 0; u < cnt; ++u)
+					{
+						const double dx = zi.x - sx[u], dy = zi.y - sy[u];
+						const double inv = 1.0 / (dx * dx + dy * dy + eps2);
+						ax += dx * inv;
+						ay += dy * inv;
+					}
+				}
+			}
+		}
+		else if (act)
+		{
+			const double2 a0 = a[t];
+			ax = a0.x * s1;
+			ay = a0.y * s1;
+		}
+		// L2P: f(u) = sum_l b_l u^l by Horner, field = conj(f)
+		const double2 u = make_double2(zi.x - c.x, zi.y - c.y);
+		double2 f = bl[P - 1];
+#pragma unroll
+		for (int k = P - 2; k >= 0; --k) f = cadd(cmul(f, u), bl[k]);
+		ax += f.x;
+		ay -= f.y;
+		if (act) a[t] = make_double2(ax * s0, ay * s0);
+	}
+	__syncthreads();   // the next leaf overwrites the LDS rows
+	}
+}
+
+} // namespace
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+static int f2d_done(nbco_ctx *c)
+{
+	NBCO_HIP(hipGetLastError());
+	if (c->o.sync) NBCO_HIP(hipStreamSynchronize(c->stream));
+	return NBCO_OK;
+}
+
+static int f2d_direct(nbco_ctx *c, const double *p, double *a, long long n, const double *param, bool kahan)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!p || !a || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_direct: bad arguments");
+	const long long nb = (n + kB - 1) / kB;
+	if (nb > (1LL << 31) - 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_direct: n too large");
+	const double eps2 = (double)c->o.eps2;
+	if (kahan)
+		hipLaunchKernelGGL(f2d_direct_kernel<true>, dim3((unsigned)nb), dim3(kB), 0, c->stream, (const double2 *)p, (double2 *)a, n, eps2, param);
+	else
+		hipLaunchKernelGGL(f2d_direct_kernel<false>, dim3((unsigned)nb), dim3(kB), 0, c->stream, (const double2 *)p, (double2 *)a, n, eps2, param);
+	return f2d_done(c);
+}
+
+// L = max(2, round(log2(dens_inhom n / (p sqrt p)) / 2)) (fmm_cart.cuh:415-417), or opts.tree_L; 2 <= L <= 15
+static int f2d_levels(const nbco_opts &o, long long n)
+{
+	if (o.tree_L > 0) return o.tree_L;
+	const double s = o.fmm_order * std::sqrt((double)o.fmm_order);
+	int L = (int)std::round(std::log2((double)o.dens_inhom * (double)n / s) / 2);
+	return std::min(std::max(L, 2), kMaxL2);
+}
+
+template <int P>
+static int f2d_fmm_run(nbco_ctx *c, double *p, double *a, long long n, const double *param)
+{
+	const int L = f2d_levels(c->o, n);
+	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_L must be 0 or 2..15");
+	const int radius = (int)c->o.tree_radius;
+	const double eps2 = (double)c->o.eps2;
+	const int side = 1 << L, m = side * side;
+	const long long ntot = quad_beg(L + 1);
+	hipStream_t st = c->stream;
+
+	// scratch: keys in / out, indices in / out | gather and sort temp | tree | reduction partials + scalars
+	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
+	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
+	size_t sort_bytes = 0;
+	NBCO_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_in, keys, idx_in, idx, (size_t)n, 0u, (unsigned)(2 * L), st));
+	NBCO_TRY(c->reserve(c->f2d_tmp, std::max(sort_bytes, sizeof(double) * 4 * (size_t)n)));
+	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1) + P) + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
+	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
+	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
+	Quad q;
+	q.center = c->f2d_tree.as<double2>();
+	q.mpole = q.center + ntot;
+	q.local = q.mpole + ntot * (P + 1);
+	q.mult = reinterpret_cast<int *>(q.local + ntot * P);
+	q.index = q.mult + ntot;
+	double *part = c->f2d_part.as<double>(), *scal = part + 4 * kRedBlocks;
+
+	double2 *x = (double2 *)p, *v = x + n;
+	const int nbr = std::min(kRedBlocks, grid_for(n));
+	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, (const double2 *)x, n, part);
+	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_for(n)), dim3(kB), 0, st, (const double2 *)x, n, (const double *)scal, side, keys_in, idx_in);
+	sort_bytes = c->f2d_tmp.bytes;
+	NBCO_HIP(rocprim::radix_sort_pairs(c->f2d_tmp.ptr, sort_bytes, keys_in, keys, idx_in, idx, (size_t)n, 0u, (unsigned)(2 * L), st));
+	double2 *tmp = c->f2d_tmp.as<double2>();
+	hipLaunchKernelGGL(f2d_gather_kernel, dim3(grid_for(n)), dim3(kB), 0, st, (const double2 *)x, (const double2 *)v, (const uint32_t *)idx, tmp, n);
+	NBCO_HIP(hipMemcpyAsync(p, tmp, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
+
+	hipLaunchKernelGGL((f2d_leaf_kernel<P>), dim3((m + kB - 1) / kB), dim3(kB), 0, st, q, (const double2 *)x, m, quad_beg(L));
+	for (int l = L - 1; l >= 2; --l)
+		hipLaunchKernelGGL((f2d_m2m_kernel<P>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, st, q, l);
+	const long long nm2l = quad_beg(L + 1) - quad_beg(2);
+	hipLaunchKernelGGL((f2d_m2l_kernel<P>), dim3((unsigned)((nm2l + kB - 1) / kB)), dim3(kB), 0, st, q, L, radius, eps2);
+	for (int l = 3; l <= L; ++l)
+		hipLaunchKernelGGL((f2d_l2l_kernel<P>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, st, q, l);
+	const int near_grid = std::min(m, 1 << 22);
+	if (c->o.coll)
+		hipLaunchKernelGGL((f2d_near_kernel<P, true>), dim3(near_grid), dim3(kNear), 0, st, q, (const double2 *)x, (double2 *)a, L, radius, eps2, param);
+	else
+		hipLaunchKernelGGL((f2d_near_kernel<P, false>), dim3(near_grid), dim3(kNear), 0, st, q, (const double2 *)x, (double2 *)a, L, radius, eps2, param);
+	return f2d_done(c);
+}
+
+static int f2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!p || !a || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: bad arguments");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: n must be below 2^31");
+	if (c->o.tree_radius < 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_radius must be >= 1");
+	if (c->o.tree_L == 1 || c->o.tree_L > kMaxL2 || c->o.tree_L < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_L must be 0 or 2..15");
+	switch (c->o.fmm_order)
+	{
+	case 1: return f2d_fmm_run<1>(c, p, a, n, param);
+	case 2: return f2d_fmm_run<2>(c, p, a, n, param);
+	case 3: return f2d_fmm_run<3>(c, p, a, n, param);
+	case 4: return f2d_fmm_run<4>(c, p, a, n, param);
+	case 5: return f2d_fmm_run<5>(c, p, a, n, param);
+	case 6: return f2d_fmm_run<6>(c, p, a, n, param);
+	case 7: return f2d_fmm_run<7>(c, p, a, n, param);
+	case 8: return f2d_fmm_run<8>(c, p, a, n, param);
+	case 9: return f2d_fmm_run<9>(c, p, a, n, param);
+	case 10: return f2d_fmm_run<10>(c, p, a, n, param);
+	default: return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
+	}
+}
+
+static int f2d_step(nbco_ctx *c, double *b, const double *a, long double ds, long long n)
+{
+	hipLaunchKernelGGL(f2d_axpy_kernel, dim3(grid_for(2 * n)), dim3(kB), 0, c->stream, b, a, (double)ds, 2 * n);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+static int f2d_eval(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)
+{
+	double *a = buf + 4 * n;
+	const int save = c->o.sync;
+	c->o.sync = 0;
+	int rc;
+	switch (kind)
+	{
+	case NBCO_2D_EVAL_DIRECT: rc = f2d_direct(c, buf, a, n, param, false); break;
+	case NBCO_2D_EVAL_DIRECT_KAHAN: rc = f2d_direct(c, buf, a, n, param, true); break;
+	case NBCO_2D_EVAL_FMM: rc = f2d_fmm(c, buf, a, n, param); break;
+	default: rc = c->fail(NBCO_ERR_ARG, "nbco_2d: unknown evaluator kind");
+	}
+	c->o.sync = save;
+	if (rc != NBCO_OK) return rc;
+	if (elastic)   // main.cu:85-89: a -= k o x, k = param + 2
+	{
+		hipLaunchKernelGGL(f2d_elastic_kernel, dim3(grid_for(n)), dim3(kB), 0, c->stream, (const double2 *)buf, (double2 *)a, n, param + 2);
+		NBCO_HIP(hipGetLastError());
+	}
+	return NBCO_OK;
+}
+
+// host-side state initialisation (main.cu:96-170): centre, then scale each component to the wanted RMS
+static void f2d_center_rms(double *d, long long nb, double ax, double ay)
+{
+	double sx = 0, sy = 0;
+	for (long long i = 0; i < nb; ++i) { sx += d[2 * i]; sy += d[2 * i + 1]; }
+	sx /= (double)nb;
+	sy /= (double)nb;
+	for (long long i = 0; i < nb; ++i) { d[2 * i] -= sx; d[2 * i + 1] -= sy; }
+	double qx = 0, qy = 0;
+	for (long long i = 0; i < nb; ++i) { qx += d[2 * i] * d[2 * i]; qy += d[2 * i + 1] * d[2 * i + 1]; }
+	qx /= (double)nb;
+	qy /= (double)nb;
+	qx = std::sqrt(qx);
+	qy = std::sqrt(qy);
+	const double fx = ax / qx, fy = ay / qy;
+	for (long long i = 0; i < nb; ++i) { d[2 * i] *= fx; d[2 * i + 1] *= fy; }
+}
+
+extern "C" {
+
+int nbco_2d_direct(nbco_ctx *c, const double *p, double *a, long long n, const double *param) { return f2d_direct(c, p, a, n, param, false); }
+int nbco_2d_direct3(nbco_ctx *c, const double *p, double *a, long long n, const double *param) { return f2d_direct(c, p, a, n, param, true); }
+int nbco_2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param) { return f2d_fmm(c, p, a, n, param); }
+
+int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!buf || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_force: bad arguments");
+	NBCO_TRY(f2d_eval(c, kind, buf, n, param, elastic));
+	return f2d_done(c);
+}
+
+int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt_, double scale_, int elastic)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!buf || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: bad arguments");
+	if (kind < NBCO_2D_EVAL_DIRECT || kind > NBCO_2D_EVAL_FMM) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown evaluator kind");
+	double *x = buf, *v = buf + 2 * n, *a = buf + 4 * n;
+	const long double dt = dt_, scale = scale_;
+	auto K = [&](long double s) { return f2d_step(c, v, a, s, n); };
+	auto D = [&](long double s) { return f2d_step(c, x, v, s, n); };
+	auto F = [&]() { return f2d_eval(c, kind, buf, n, param, elastic); };
+	const long double th = 1.3512071919596576340476878089715L;   // integrator.cuh:98
+	const long double xi = +0.1786178958448091E+00L, la = -0.2123418310626054E+00L, ch = -0.6626458266981849E-01L;  // :130-132
+	switch (scheme)
+	{
+	case NBCO_INTEG_EULER:        // integrator.cuh:32
+		NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt)); NBCO_TRY(F());
+		break;
+	case NBCO_INTEG_PRE_EULER:    // :50
+		NBCO_TRY(F()); NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt));
+		break;
+	case NBCO_INTEG_LEAPFROG:     // :68
+	{
+		const long double ds = dt * scale * 0.5L;
+		NBCO_TRY(K(ds)); NBCO_TRY(D(dt)); NBCO_TRY(F()); NBCO_TRY(K(ds));
+		break;
+	}
+	case NBCO_INTEG_FORESTRUTH:   // :100
+	{
+		const long double ds = dt * scale;
+		NBCO_TRY(D(dt * th / 2)); NBCO_TRY(F());
+		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
+		NBCO_TRY(K(ds * (1 - 2 * th))); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
+		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * th / 2));
+		break;
+	}
+	case NBCO_INTEG_PEFRL:        // :134
+	{
+		const long double ds = dt * scale;
+		NBCO_TRY(D(dt * xi)); NBCO_TRY(F());
+		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
+		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * (1 - 2 * (ch + xi)))); NBCO_TRY(F());
+		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
+		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * xi));
+		break;
+	}
+	default:
+		return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown scheme");
+	}
+	return f2d_done(c);
+}
+
+int nbco_2d_integrate_steps(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                            int elastic, int steps)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (steps < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate_steps: steps < 0");
+	const int save = c->o.sync;
+	c->o.sync = 0;
+	int rc = NBCO_OK;
+	for (int s = 0; s < steps && rc == NBCO_OK; ++s) rc = nbco_2d_integrate(c, scheme, kind, buf, n, param, dt, scale, elastic);
+	c->o.sync = save;
+	if (rc != NBCO_OK) return rc;
+	return f2d_done(c);
+}
+
+int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!x || !ref || !out_host || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_mean_relerr: bad arguments");
+	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
+	double *part = c->f2d_part.as<double>();
+	const int nb = std::min(kRedBlocks, grid_for(n));
+	hipLaunchKernelGGL(f2d_relerr_kernel, dim3(nb), dim3(kB), 0, c->stream, (const double2 *)x, (const double2 *)ref, n, part);
+	hipLaunchKernelGGL(f2d_relerr_final_kernel, dim3(1), dim3(kB), 0, c->stream, (const double *)part, nb, n, part + 4 * kRedBlocks);
+	NBCO_HIP(hipGetLastError());
+	NBCO_HIP(hipMemcpyAsync(out_host, part + 4 * kRedBlocks, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	return NBCO_OK;
+}
+
+// main.cu:120-145 initKV over [positions nb | velocities nb], nb = n
+int nbco_2d_init_kv(double *s, long long n, const double *A, const double *om, unsigned long long seed, unsigned long long discard)
+{
+	if (!s || n <= 0 || !A || !om) return NBCO_ERR_ARG;
+	std::mt19937_64 gen(seed);
+	gen.discard(discard);
+	std::uniform_real_distribution<double> dist(0.0, 1.0);
+	const double twopi = 6.283185307179586476925286766559;
+	// one glibc sincos per angle: the reference's documented build (GCC at -O2 and above) fuses its sin / cos pair of main.cu:133-136
+	// into sincos, whose last bit differs from separate sin and cos for some inputs
+	for (long long i = 0; i < n; ++i)
+	{
+		const double eta = dist(gen), etax = twopi * dist(gen), etay = twopi * dist(gen);
+		const double rt = std::sqrt(eta), rt1 = std::sqrt(1 - eta);
+		double sx, cx, sy, cy;
+		::sincos(etax, &sx, &cx);
+		::sincos(etay, &sy, &cy);
+		s[2 * i] = A[0] * rt * cx;
+		s[2 * i + 1] = A[1] * rt1 * cy;
+		s[2 * (n + i)] = A[0] * om[0] * rt * sx;
+		s[2 * (n + i) + 1] = A[1] * om[1] * rt1 * sy;
+	}
+	f2d_center_rms(s, n, A[0] / 2, A[1] / 2);
+	f2d_center_rms(s + 2 * n, n, om[0] * A[0] / 2, om[1] * A[1] / 2);
+	return NBCO_OK;
+}
+
+// main.cu:147-170 initGA: 4n standard normals, positions scaled by x, velocities by u, then centred and RMS-adjusted
+int nbco_2d_init_gaussian(double *s, long long n, const double *x2, const double *u2, unsigned long long seed, unsigned long long discard)
+{
+	if (!s || n <= 0 || !x2 || !u2) return NBCO_ERR_ARG;
+	std::mt19937_64 gen(seed);
+	gen.discard(discard);
+	std::normal_distribution<double> dist(0.0, 1.0);
+	for (long long i = 0; i < 4 * n; ++i) s[i] = dist(gen);
+	for (long long i = 0; i < n; ++i) { s[2 * i] *= x2[0]; s[2 * i + 1] *= x2[1]; }
+	for (long long i = n; i < 2 * n; ++i) { s[2 * i] *= u2[0]; s[2 * i + 1] *= u2[1]; }
+	f2d_center_rms(s, n, x2[0], x2[1]);
+	f2d_center_rms(s + 2 * n, n, u2[0], u2[1]);
+	return NBCO_OK;
+}
+
+} // extern "C"

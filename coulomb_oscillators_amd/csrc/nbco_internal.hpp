@@ -189,6 +189,8 @@ struct nbco_ctx
 	DevBuf let_sel, let_have, dist_pos;
 	// octree-traceless evaluator (k_fmm_oct.hip)
 	DevBuf oct_tree, oct_groups;
+	// 2-D fp64 evaluators (k_fmm2d.hip): quadtree arrays, keys / permutation, gather scratch, reduction partials
+	DevBuf f2d_tree, f2d_keys, f2d_tmp, f2d_part;
 	OctTreeDev oct;
 	struct DistState
 	{

@@ -17,6 +17,8 @@ _LIB = os.environ.get("NBCO_LIB") or os.path.join(_HERE, "libnbco_hip.so")   # N
 
 EVAL_DIRECT, EVAL_DIRECT_KAHAN, EVAL_FMM_KDTREE, EVAL_FMM_TRACELESS, EVAL_FMM_SYMMETRIC = 0, 1, 2, 3, 4
 INTEG_EULER, INTEG_PRE_EULER, INTEG_LEAPFROG, INTEG_FORESTRUTH, INTEG_PEFRL = 0, 1, 2, 3, 4
+EVAL2D_DIRECT, EVAL2D_DIRECT_KAHAN, EVAL2D_FMM = 0, 1, 2   # NBCO_2D_EVAL_* (2-D fp64 evaluators of main.cu)
+REF_SEED, REF_DISCARD = 5351550349027530206, 1248     # NBCO_REF_SEED / NBCO_REF_DISCARD (main.cu:779-784)
 PHASES = ["build", "p2m_m2m", "traverse", "lists", "p2p", "m2l", "l2l", "l2p", "finish", "direct", "axpy"]
 
 KD_FIELDS = {"mult": 0, "index": 1, "splitdim": 2, "center": 3, "lbound": 4, "rbound": 5,
@@ -159,6 +161,15 @@ def _load():
         "nbco_profile_enable": [P, I],
         "nbco_profile_reset": [P],
         "nbco_profile_get": [P, I, C.POINTER(D), C.POINTER(LL)],
+        "nbco_2d_direct": [P, P, P, LL, P],
+        "nbco_2d_direct3": [P, P, P, LL, P],
+        "nbco_2d_fmm": [P, P, P, LL, P],
+        "nbco_2d_force": [P, I, P, LL, P, I],
+        "nbco_2d_integrate": [P, I, I, P, LL, P, D, D, I],
+        "nbco_2d_integrate_steps": [P, I, I, P, LL, P, D, D, I, I],
+        "nbco_2d_mean_relerr": [P, P, P, LL, C.POINTER(D)],
+        "nbco_2d_init_kv": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
+        "nbco_2d_init_gaussian": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -168,6 +179,20 @@ def _load():
     L.nbco_last_error.restype = C.c_char_p
     _lib = L
     return L
+
+
+def init2d(n, kind="kv", a=None, b=None, seed=REF_SEED, discard=REF_DISCARD):
+    """Host initial state of main.cu (nbco_2d_init_kv / nbco_2d_init_gaussian): numpy float64 [2, n, 2] = [positions, velocities].
+    kind "kv": a = semi-axes A, b = depressed phase advances omega; "ga": a = position std x, b = velocity std u.  Needs no GPU."""
+    import numpy as np
+    out = np.zeros((2, n, 2), dtype=np.float64)
+    a2 = (C.c_double * 2)(*a)
+    b2 = (C.c_double * 2)(*b)
+    fn = _load().nbco_2d_init_kv if kind == "kv" else _load().nbco_2d_init_gaussian
+    rc = fn(out.ctypes.data_as(C.c_void_p), n, C.cast(a2, C.c_void_p), C.cast(b2, C.c_void_p), seed, discard)
+    if rc != 0:
+        raise EngineError("nbco_2d_init_%s failed with status %d" % (kind, rc), status=rc)
+    return out
 
 
 def default_opts(**kw):
@@ -285,6 +310,31 @@ class Engine:
     def integrate_steps(self, scheme, kind, buf, n, param, dt, steps, scale=1.0, elastic=True):
         """`steps` steps in one call (nbco_integrate_steps): same final state as `steps` calls of integrate()"""
         self._chk(self.lib.nbco_integrate_steps(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps)))
+
+    # ---- 2-D fp64 evaluators (main.cu): float64 tensors, xy pairs, param = {xi/N, 0, kx, ky} -------------------------------
+    def direct_2d(self, p, a, n, param=None):
+        self._chk(self.lib.nbco_2d_direct(self.ctx, _ptr(p), _ptr(a), n, _ptr(param)))
+
+    def direct3_2d(self, p, a, n, param=None):
+        self._chk(self.lib.nbco_2d_direct3(self.ctx, _ptr(p), _ptr(a), n, _ptr(param)))
+
+    def fmm_2d(self, p, a, n, param):
+        """fmm_cart: p holds positions then velocities (2n xy pairs); both are left in cell order"""
+        self._chk(self.lib.nbco_2d_fmm(self.ctx, _ptr(p), _ptr(a), n, _ptr(param)))
+
+    def compute_force_2d(self, kind, buf, n, param, elastic=True):
+        self._chk(self.lib.nbco_2d_force(self.ctx, kind, _ptr(buf), n, _ptr(param), int(elastic)))
+
+    def integrate_2d(self, scheme, kind, buf, n, param, dt, scale=1.0, elastic=True):
+        self._chk(self.lib.nbco_2d_integrate(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic)))
+
+    def integrate_steps_2d(self, scheme, kind, buf, n, param, dt, steps, scale=1.0, elastic=True):
+        self._chk(self.lib.nbco_2d_integrate_steps(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps)))
+
+    def mean_relerr_2d(self, x, ref, n):
+        out = C.c_double()
+        self._chk(self.lib.nbco_2d_mean_relerr(self.ctx, _ptr(x), _ptr(ref), n, C.byref(out)))
+        return out.value
 
     # ---- reductions -----------------------------------------------------------------------------
     def minmax(self, p, n):

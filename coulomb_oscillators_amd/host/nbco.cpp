@@ -1,0 +1,311 @@
+// nbco -- the reference's 2-D program (Simulation/main.cu: N charges in a 2-D anisotropic trap, fp64, a KV beam by default) over
+// the C ABI of libnbco_hip.so.  Flags, defaults, exit codes, error strings, the initial state, args.txt and the snapshot files
+// follow main.cu:257-903; the evaluator is nbco_2d_fmm (fmm_cart) plus the elastic term, integrated by nbco_2d_integrate.
+//
+// Deviations: -cpu / -cpu-threads are refused (main.cu -cpu runs a host FMM, which this product does not have); -gpu, -gridsize
+// and -cacheline are validated as main.cu does and then have no effect; -p above 10 is refused by the library (NBCO_ERR_ARG).
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <limits>
+#include <string>
+#include <vector>
+#include "../../include/nbco.h"
+
+namespace {
+
+struct V2 { double x, y; };
+
+const char *kHelp =
+    "nbco: 2-D Coulomb oscillators (fp64 quadtree FMM on an AMD Instinct GPU).\n\n"
+    "Usage: nbco [options] [input]\n\n"
+    "  input             binary state file: all positions, then all velocities, as pairs of doubles\n"
+    "                    (N = file size / 32).  Without it the state is drawn from a KV distribution\n"
+    "                    (or a Gaussian one with -ga).\n\n"
+    "Options:\n"
+    "  -h, -help         print this text\n"
+    "  -o <dir>          existing folder for args.txt and the snapshots (default ./out); each snapshot\n"
+    "                    out<iter>_<ds>.bin holds positions and velocities in the input file's format,\n"
+    "                    in the tree order of the evaluation\n"
+    "  -n <N>            particle count without an input file (default 30001)\n"
+    "  -ds <v>           time step (default 5e-4)\n"
+    "  -iters <k>        the run takes k + 1 steps (default 30000)\n"
+    "  -steps <k>        a snapshot every k steps (default 200)\n"
+    "  -integ <name>     integrator instead of leapfrog; the name follows one leading character, as in\n"
+    "                    the original parser: -eu (symplectic Euler), -fr (Forest-Ruth), -pefrl (PEFRL)\n"
+    "  -p <order>        expansion order, 1..10 (default 5)\n"
+    "  -r <radius>       near-field radius in leaf cells, integer >= 1 (default 1)\n"
+    "  -eps <v>          softening length, > 0 (default 1e-9; EPS2 = v^2)\n"
+    "  -i <v>            density factor of the level count round(log4(N v / p^1.5)) (default 1)\n"
+    "  -ncoll            skip the near field (a is scaled by 0 there instead)\n"
+    "  -test             time one evaluation, then print the mean relative error against the\n"
+    "                    compensated direct sum for p = 1..10; no snapshots\n"
+    "  -ga               Gaussian initial state instead of KV\n"
+    "  -xi <v>           perveance\n"
+    "  -omega0 <x> <y>   trap phase advances\n"
+    "  -x <x> <y>        position spread (sets A = 2 x)\n"
+    "  -u <x> <y>        velocity spread (omega follows as u / x)\n"
+    "  -A <x> <y>        semi-axes (sets x = A / 2)\n"
+    "  -omega <x> <y>    depressed phase advances (u follows as omega x)\n"
+    "  -gpu <n>, -gridsize <n>, -cacheline <n>\n"
+    "                    accepted for compatibility (n >= 1); no effect\n"
+    "  -cpu, -cpu-threads <n>\n"
+    "                    not available: this build has no host evaluator\n";
+
+int fail(const std::string &msg)
+{
+	std::cerr << msg;
+	return -1;
+}
+
+bool is(const char *a, const char *name) { return std::strcmp(a + 1, name) == 0; }
+
+}  // namespace
+
+int main(const int argc, const char **argv)
+{
+	int nBodies = 30001, nIters = 30001, nSteps = 200, integ = NBCO_INTEG_LEAPFROG;
+	int fmm_order = 5, tree_radius = 1;
+	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1;
+	std::string strout("out"), strin;
+	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true;
+
+	// KV parameters matched to the emittances (main.cu:271-313)
+	const double twopi = 6.283185307179586476925286766559;
+	double xi = 2.e-6;
+	V2 omega0{6.22 * twopi, 6.21 * twopi};
+	V2 emit{0.03e-3, 0.01e-3}, omega, domega, A, x, u;
+	omega.y = 0.8 * omega0.y;
+	A.y = 2 * std::sqrt(emit.y / omega.y);
+	const double A2 = A.y * A.y;
+	domega.y = (omega0.y + omega.y) * (omega0.y - omega.y);
+	const double om0x2 = omega0.x * omega0.x, om0x4 = om0x2 * om0x2, om0x6 = om0x4 * om0x2;
+	const double c = -2 * om0x2, d = -A2 * domega.y * domega.y / (4 * emit.x), p = c, q = d;
+	const double Delta0 = 16 * om0x4, Delta1 = 27 * d * d + 128 * om0x6;
+	const double Q = std::cbrt((Delta1 + std::sqrt((27 * d * d + 256 * om0x6) * (27 * d * d))) / 2);
+	const double S = std::sqrt((-2 * p + (Q + Delta0 / Q)) / 3) / 2;
+	omega.x = S - std::sqrt(-4 * S * S - 2 * p - q / S) / 2;   // the quartic's fourth root
+	A.x = 2 * std::sqrt(emit.x / omega.x);
+	xi = domega.y * A.y * (A.x + A.y) / 2;
+	x = V2{A.x / 2, A.y / 2};
+	u = V2{omega.x * A.x / 2, omega.y * A.y / 2};
+
+	auto need = [&](int i, int k, const char *) { return i + k < argc ? 0 : 1; };
+	for (int i = 1; i < argc; ++i)
+	{
+		const char *a = argv[i];
+		if (a[0] != '-') { strin = a; in = true; continue; }
+		const std::string opt = std::string("'") + a + "'";
+		auto missing = [&]() { return fail("Error: missing argument to " + opt + "\n"); };
+		auto missing2 = [&]() { return fail("Error: missing argument(s) to " + opt + "\n"); };
+		auto invalid = [&](const char *v, const char *tail = "") { return fail("Error: invalid argument to " + opt + ": " + v + tail + "\n"); };
+		auto invalid2 = [&]() { return fail("Error: invalid argument(s) to " + opt + ": " + argv[i + 1] + " " + argv[i + 2] + "\n"); };
+		auto int_arg = [&](int &dst) -> int {
+			if (need(i, 1, a)) return missing();
+			dst = std::atoi(argv[i + 1]);
+			if (dst <= 0) return invalid(argv[i + 1]);
+			++i;
+			return 0;
+		};
+		auto pair_arg = [&](V2 &dst) -> int {
+			if (need(i, 2, a)) return missing2();
+			dst = V2{std::atof(argv[i + 1]), std::atof(argv[i + 2])};
+			if (dst.x < 0 || dst.y < 0) return invalid2();
+			i += 2;
+			return 0;
+		};
+		int rc = 0, dummy = 0;
+		if (is(a, "h") || is(a, "help")) { std::cout << kHelp; return 0; }
+		else if (is(a, "o")) { if (need(i, 1, a)) return missing(); strout = argv[++i]; }
+		else if (is(a, "n")) rc = int_arg(nBodies);
+		else if (is(a, "ds"))
+		{
+			if (need(i, 1, a)) return missing();
+			dt = std::atof(argv[i + 1]);
+			if (dt <= 0) return invalid(argv[i + 1]);
+			++i;
+		}
+		else if (is(a, "iters"))
+		{
+			if (need(i, 1, a)) return missing();
+			nIters = std::atoi(argv[i + 1]) + 1;
+			if (nIters <= 0) return invalid(argv[i + 1]);
+			++i;
+		}
+		else if (is(a, "steps")) rc = int_arg(nSteps);
+		else if (is(a, "integ"))
+		{
+			if (need(i, 1, a)) return missing();
+			const char *v = argv[i + 1];
+			// main.cu:460-476 compares the name from its second character on
+			if (v[0] && is(v, "eu")) integ = NBCO_INTEG_EULER;
+			else if (v[0] && is(v, "fr")) integ = NBCO_INTEG_FORESTRUTH;
+			else if (v[0] && is(v, "pefrl")) integ = NBCO_INTEG_PEFRL;
+			else return invalid(v);
+			++i;
+		}
+		else if (is(a, "p")) rc = int_arg(fmm_order);
+		else if (is(a, "r")) rc = int_arg(tree_radius);
+		else if (is(a, "eps"))
+		{
+			if (need(i, 1, a)) return missing();
+			EPS2 = std::atof(argv[i + 1]);
+			if (EPS2 <= 0) return invalid(argv[i + 1]);
+			EPS2 *= EPS2;
+			if (EPS2 == 0) return fail("Error: too small argument to " + opt + ": " + argv[i + 1] + "\n");
+			++i;
+		}
+		else if (is(a, "i"))
+		{
+			if (need(i, 1, a)) return missing();
+			dens_inhom = std::atof(argv[i + 1]);
+			if (dens_inhom <= 0) return invalid(argv[i + 1], " (should be greater than 0)");
+			++i;
+		}
+		else if (is(a, "ncoll")) coll = false;
+		else if (is(a, "cpu")) cpu = true;
+		else if (is(a, "cpu-threads")) { cpu = true; rc = int_arg(dummy); }
+		else if (is(a, "cacheline") || is(a, "gpu") || is(a, "gridsize")) rc = int_arg(dummy);
+		else if (is(a, "test")) test = true;
+		else if (is(a, "ga")) ga = true;
+		else if (is(a, "xi"))
+		{
+			if (need(i, 1, a)) return missing();
+			xi = std::atof(argv[i + 1]);
+			if (xi < 0) return invalid(argv[i + 1]);
+			++i;
+		}
+		else if (is(a, "omega0")) rc = pair_arg(omega0);
+		else if (is(a, "x")) { rc = pair_arg(x); A = V2{x.x * 2, x.y * 2}; }
+		else if (is(a, "u")) { rc = pair_arg(u); calc_omega = true; }
+		else if (is(a, "A")) { rc = pair_arg(A); x = V2{A.x / 2, A.y / 2}; }
+		else if (is(a, "omega")) { rc = pair_arg(omega); calc_u = true; }
+		else return fail("Error: unrecognised option '" + std::string(a) + "'\n");
+		if (rc) return rc;
+	}
+	if (cpu) return fail("Error: '-cpu' is not available: this build evaluates on the GPU only\n");
+	if (fmm_order > 10) return fail("Error: invalid argument to '-p': " + std::to_string(fmm_order) + " (orders above 10 are not provided)\n");
+	if (calc_omega) omega = V2{u.x / x.x, u.y / x.y};
+	else if (calc_u) u = V2{omega.x * x.x, omega.y * x.y};
+
+	std::vector<double> buf;
+	if (in)
+	{
+		std::ifstream fin(strin, std::ios::in | std::ios::binary);
+		if (!fin) return fail("Error: cannot read from input location.\n");
+		fin.ignore(std::numeric_limits<std::streamsize>::max());
+		const long long bytes = (long long)fin.gcount();
+		nBodies = (int)(bytes / 32);
+		if (nBodies <= 0) return fail("Error: the input file holds no particle.\n");
+		buf.assign(6 * (size_t)nBodies, 0.0);
+		fin.clear();
+		fin.seekg(0, std::ios::beg);
+		fin.read(reinterpret_cast<char *>(buf.data()), 32LL * nBodies);
+	}
+	else
+	{
+		buf.assign(6 * (size_t)nBodies, 0.0);
+		std::cout << "emittances: " << x.x * u.x << ' ' << x.y * u.y << "\nperveance: " << xi << "\ndep. phase adv.: " << omega.x << ' '
+		          << omega.y << "\nsemi-axes: " << A.x << ' ' << A.y << std::endl;
+		const double a2[2] = {ga ? x.x : A.x, ga ? x.y : A.y}, b2[2] = {ga ? u.x : omega.x, ga ? u.y : omega.y};
+		const int rc = ga ? nbco_2d_init_gaussian(buf.data(), nBodies, a2, b2, NBCO_REF_SEED, NBCO_REF_DISCARD)
+		                  : nbco_2d_init_kv(buf.data(), nBodies, a2, b2, NBCO_REF_SEED, NBCO_REF_DISCARD);
+		if (rc != NBCO_OK) return fail("Error: initial state failed\n");
+	}
+	const long long n = nBodies;
+
+	if (!test)
+	{
+		std::ofstream farg(strout + "/args.txt", std::ios::out);
+		if (!farg)
+			return fail("Error: cannot write on output location. Check that \"" + strout + "\" folder exists. Create it if not.\n");
+		for (int i = 0; i < argc; ++i) farg << argv[i] << ' ';
+	}
+	const double par[4] = {xi / (double)nBodies, 0, omega0.x * omega0.x, omega0.y * omega0.y};   // main.cu:803-808
+
+	nbco_opts o;
+	nbco_opts_default(&o);
+	o.fmm_order = fmm_order;
+	o.tree_radius = (float)tree_radius;
+	o.eps2 = (float)EPS2;
+	o.coll = coll ? 1 : 0;
+	o.dens_inhom = (float)dens_inhom;
+	o.tree_L = 0;
+	o.sync = 0;
+	o.stream = nullptr;
+	nbco_ctx *ctx = nullptr;
+	int rc = nbco_create(&ctx, &o);
+	if (rc != NBCO_OK) return fail("Error: no usable GPU context (status " + std::to_string(rc) + ")\n");
+	double *d_buf = nullptr, *d_par = nullptr;
+	auto hip_ok = [&](hipError_t e) {
+		if (e != hipSuccess) std::cerr << "Error: " << hipGetErrorString(e) << '\n';
+		return e == hipSuccess;
+	};
+	auto done = [&](int code) {
+		if (d_buf) (void)hipFree(d_buf);
+		if (d_par) (void)hipFree(d_par);
+		nbco_destroy(ctx);
+		return code;
+	};
+	auto lib_ok = [&](int r) {
+		if (r != NBCO_OK) std::cerr << "Error: " << nbco_last_error(ctx) << '\n';
+		return r == NBCO_OK;
+	};
+	const size_t cpy = sizeof(double) * 4 * (size_t)n;
+	if (!hip_ok(hipMalloc(&d_buf, sizeof(double) * 6 * (size_t)n)) || !hip_ok(hipMalloc(&d_par, sizeof par)) ||
+	    !hip_ok(hipMemcpy(d_buf, buf.data(), cpy, hipMemcpyHostToDevice)) || !hip_ok(hipMemcpy(d_par, par, sizeof par, hipMemcpyHostToDevice)))
+		return done(-1);
+
+	if (test)   // main.cu:823-852
+	{
+		if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 0)) || !lib_ok(nbco_sync(ctx))) return done(-1);
+		const auto t0 = std::chrono::steady_clock::now();
+		if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 0)) || !lib_ok(nbco_sync(ctx))) return done(-1);
+		const auto t1 = std::chrono::steady_clock::now();
+		std::cout << "Time elapsed: " << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() * 1.e-6 << " [s]" << std::endl;
+		double *d_tmp = nullptr;
+		if (!hip_ok(hipMalloc(&d_tmp, sizeof(double) * 2 * (size_t)n))) return done(-1);
+		for (int order = 1; order <= 10; ++order)
+		{
+			o.fmm_order = order;
+			double err = 0;
+			if (!lib_ok(nbco_set_opts(ctx, &o)) || !lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 0)) ||
+			    !hip_ok(hipMemcpy(d_tmp, d_buf + 4 * n, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToDevice)) ||
+			    !lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_DIRECT_KAHAN, d_buf, n, d_par, 0)) ||
+			    !lib_ok(nbco_2d_mean_relerr(ctx, d_tmp, d_buf + 4 * n, n, &err)))
+			{
+				(void)hipFree(d_tmp);
+				return done(-1);
+			}
+			std::cout << order << ": Relative error: " << err << std::endl;
+		}
+		(void)hipFree(d_tmp);
+		return done(0);
+	}
+
+	// main.cu:853-893: one evaluation, then per iteration a step and every nSteps iterations a snapshot
+	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return done(-1);
+	for (int iter = 0; iter < nIters; ++iter)
+	{
+		if (!lib_ok(nbco_2d_integrate(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1))) return done(-1);
+		if (iter % nSteps == 0)
+		{
+			std::cout << iter << ' ' << std::flush;
+			if (!hip_ok(hipMemcpy(buf.data(), d_buf, cpy, hipMemcpyDeviceToHost))) return done(-1);
+			std::ofstream fout(strout + "/out" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+			if (!fout)
+			{
+				std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+				return done(-1);
+			}
+			fout.write(reinterpret_cast<const char *>(buf.data()), (std::streamsize)cpy);
+		}
+	}
+	std::cout << std::endl;
+	return done(0);
+}

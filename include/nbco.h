@@ -407,6 +407,41 @@ int nbco_init_gaussian(float *host_state, long long n, const float *sigma_x3, co
 int nbco_init_gaussian_slice(float *host_slice, long long n, long long first, long long count, const float *sigma_x3,
                              const float *sigma_u3, unsigned long long seed, unsigned long long discard, int uniform_positions);
 
+/* ---- 2-D fp64 evaluators: the reference's `nbco` program (Simulation/main.cu, DIM 2, SCAL double) ----------------------------------
+ * Conventions of this section:
+ *   - positions / velocities / accelerations are fp64 xy pairs (16-byte stride); a state buffer is [pos n | vel n | acc n];
+ *   - `param` is the 4-double DEVICE array {xi/N, 0, kx, ky} of main.cu:803-808: evaluators scale by param[0], the elastic term
+ *     uses param + 2, and the FMM without near field (opts.coll == 0) multiplies a by param[1] (fmm_cart.cuh:527-528);
+ *   - the pair law is a_i += d / (|d|^2 + EPS2), d = x_i - x_j (direct.cuh:23-26, appel.cuh:293-297);
+ *   - options: the 2-D path reads fmm_order (1..10; higher orders return NBCO_ERR_ARG, the reference allows more), tree_radius
+ *     (its integer part, >= 1), eps2 (the float widened to double), coll, dens_inhom, tree_L (0 = the formula of
+ *     fmm_cart.cuh:415-417, else 2..15), sync and stream; it ignores every other field.  One context serves 2-D and 3-D calls.
+ *   - nbco_2d_fmm leaves positions AND velocities (p + 2n) in cell order (fmm_cart.cuh:500-504); any n >= 1 is accepted (the
+ *     reference asserts n > 128) and the tree has at most 15 levels below the root (2L <= 30). */
+enum { NBCO_2D_EVAL_DIRECT = 0, NBCO_2D_EVAL_DIRECT_KAHAN = 1, NBCO_2D_EVAL_FMM = 2 };
+int nbco_2d_direct(nbco_ctx *c, const double *p, double *a, long long n, const double *param);    /* direct.cuh:171 direct2, DIM 2 */
+int nbco_2d_direct3(nbco_ctx *c, const double *p, double *a, long long n, const double *param);   /* direct.cuh:233 direct3 */
+int nbco_2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param);             /* fmm_cart.cuh:395 fmm_cart; v at p + 2n */
+/* integrator.cuh:22 compute_force: a = f(x), then a -= k o x when `elastic` (main.cu:85-89 coulombOscillatorFMM) */
+int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic);
+/* integrator.cuh:32-167 (NBCO_INTEG_*): long double coefficient arithmetic, each step b += a * ds in double */
+int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                      int elastic);
+/* `steps` calls of nbco_2d_integrate, bit for bit (main.cu:855-893 loop body) */
+int nbco_2d_integrate_steps(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt,
+                            double scale, int elastic, int steps);
+/* reductions.cuh:99 relerrReduce2: mean over particles of sqrt(|x_i - ref_i|^2 / (|ref_i|^2 + 1e-18)) (rel_diff1, :37-42;
+ * main.cu:172 test_accuracy); syncs */
+int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host);
+/* main.cu:120-145 initKV and :147-170 initGA over std::mt19937_64(seed) after discard(discard) (main.cu:779-784 uses
+ * NBCO_REF_SEED / NBCO_REF_DISCARD); host_state = [pos n x 2 | vel n x 2] doubles in HOST memory, centred with exactly the
+ * RMS A/2, omega A/2 (KV) or x, u (Gaussian) per axis.  initKV takes each angle's sine and cosine from one glibc sincos call,
+ * as the reference's documented build (GCC, -O2 and above) does. */
+int nbco_2d_init_kv(double *host_state, long long n, const double *A2, const double *omega2, unsigned long long seed,
+                    unsigned long long discard);
+int nbco_2d_init_gaussian(double *host_state, long long n, const double *x2, const double *u2, unsigned long long seed,
+                          unsigned long long discard);
+
 #ifdef __cplusplus
 }
 #endif
