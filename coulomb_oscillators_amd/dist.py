@@ -1,21 +1,26 @@
-"""Multi-GPU orchestration of the kd-tree FMM: kd-domain sharding with one all-gather per force evaluation.
+"""Multi-GPU orchestration: kd-domain sharding of the kd-tree FMM (DomainRun), slabs of the octree evaluators (SlabRun).
 
 SURVEY 8(e): the balanced kd-tree's level-log2(G) nodes hold exactly N/G particles each
 (fmm_cart3_kdtree.cuh:109-137), so GPU g owns the subtree of node 2^d - 1 + g.  The C-ABI library does the
-three compute stages (``nbco_dist_partition`` / ``nbco_dist_local`` / ``nbco_dist_finish``, include/nbco.h)
-and never communicates; this module moves the two exchange buffers with ``torch.distributed``
-(backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU tests).
+compute stages (``nbco_dist_*``, include/nbco.h) and never communicates; this module moves the exchange buffers
+with ``torch.distributed`` (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU tests).
 
 One process per GPU::
 
     run = DomainRun(Engine(fmm_order=6, ...), n_global, TorchComm())
-    run.partition(pos_mine, vel_mine)          # rebalance: every `rebalance` steps
+    run.partition(pos_mine, vel_mine)          # then again every `rebalance` evaluations, inside force()
     run.leapfrog(param, dt)                    # or run.force(param)
 
-The exchange per evaluation is an all-gather of the tree-ordered positions and of the node block (csz + multipoles
-of the domain's subtree), the latter in two stages: the traversal records leave with the positions, the multipoles
-follow under the traversal.  Forces need no reduction because cross-domain pairs are evaluated one-directionally on
-the owner of the target.
+By default an evaluation moves only what the other ranks' interaction lists name (the LET exchange: all-gathers of the
+traversal records and of a count matrix, then two all-to-alls of multipoles and positions).  The all-gather form moves
+every rank's tree-ordered positions and node block (csz + multipoles of the domain's subtree) instead, in two stages --
+the traversal records leave with the positions, the multipoles follow under the traversal -- or as one block.  Forces
+need no reduction because cross-domain pairs are evaluated one-directionally on the owner of the target.
+
+Each rank's protocol is written once.  Every method that communicates is a generator behind its public method: at each
+collective it yields one request, (name of a comm method, its arguments...), and receives that method's return value.
+`_run` performs the requests on the rank's own comm; LoopbackWorld / LoopbackSlabs drive the generators of G ranks in
+lockstep inside one process and perform each collective across them.
 """
 import torch
 
@@ -118,19 +123,29 @@ class SingleComm:
 _ERR_UNSUPPORTED = 4   # NBCO_ERR_UNSUPPORTED (include/nbco.h)
 
 
-def run_dist_step(comm, work, st):
-    """the collective a nbco_dist_step describes, on the uint8 workspace tensor `work` (include/nbco.h)"""
-    G = comm.world
+def _run(protocol, comm):
+    """run one rank's protocol generator on its comm: each request it yields is a call of a method of `comm`"""
+    reply = None
+    while True:
+        try:
+            op, *args = protocol.send(reply)
+        except StopIteration as done:
+            return done.value
+        reply = getattr(comm, op)(*args)
+
+
+def _dist_step(world, work, st):
+    """yields the collective a nbco_dist_step describes, on the uint8 workspace tensor `work` (include/nbco.h)"""
     if st.op in (1, 2):
-        comm.all_reduce_i32(work[st.send_off: st.send_off + 4 * st.count].view(torch.int32), "min" if st.op == 1 else "sum")
+        yield "all_reduce_i32", work[st.send_off: st.send_off + 4 * st.count].view(torch.int32), "min" if st.op == 1 else "sum"
     elif st.op == 3:
-        comm.all_gather(work[st.recv_off: st.recv_off + G * st.count], work[st.send_off: st.send_off + st.count])
+        yield "all_gather", work[st.recv_off: st.recv_off + world * st.count], work[st.send_off: st.send_off + st.count]
     elif st.op == 4:
         w = st.row_bytes // 4
-        rs, rr = [int(st.rows_send[r]) for r in range(G)], [int(st.rows_recv[r]) for r in range(G)]
+        rs, rr = [int(st.rows_send[r]) for r in range(world)], [int(st.rows_recv[r]) for r in range(world)]
         inp = work[st.send_off: st.send_off + st.row_bytes * sum(rs)].view(torch.float32).view(-1, w)
         out = work[st.recv_off: st.recv_off + st.row_bytes * sum(rr)].view(torch.float32).view(-1, w)
-        comm.all_to_all(out, inp, rr, rs)
+        yield "all_to_all", out, inp, rr, rs
     else:
         raise ValueError("unknown nbco_dist_step op %d" % st.op)
 
@@ -139,7 +154,8 @@ class DomainRun:
     """State and per-step protocol of ONE rank.
 
     `engine` needs dist_layout / dist_partition / dist_local / dist_finish / step / add_elastic (the
-    ctypes Engine, or a test double with the same methods for the CPU tests).
+    ctypes Engine, or a test double with the same methods for the CPU tests).  Every evaluation reads its exchange form from
+    `let` / `split` / `capped`, which the constructor sets from what engine and comm offer.
     """
 
     def __init__(self, engine, n_global, comm, device=None, rebalance=8, let=None, gather_partition=None):
@@ -230,8 +246,11 @@ class DomainRun:
         """bytes received per evaluation when whole node and position blocks are all-gathered"""
         return (self.world - 1) * (int(self.lay.nodes_bytes) + int(self.lay.pos_bytes))
 
-    # ---- rebalance: gather the full state, redo the top log2(G) median splits, keep the own domain ----
+    # ---- rebalance: redo the top log2(G) median splits, keep the own domain ----
     def partition(self, pos_mine=None, vel_mine=None):
+        return _run(self._partition(pos_mine, vel_mine), self.comm)
+
+    def _partition(self, pos_mine, vel_mine):
         nl, N = self.n_local, self.n_global
         pos_mine = self.pos if pos_mine is None else pos_mine
         vel_mine = self.vel if vel_mine is None else vel_mine
@@ -246,7 +265,7 @@ class DomainRun:
             try:
                 st = self.eng.dist_repartition_begin(self.buf, N, self.world, self.rank, self.work)
                 while st.op != 0:
-                    run_dist_step(self.comm, self.work, st)
+                    yield from _dist_step(self.world, self.work, st)
                     if st.op == 4:
                         moved += st.row_bytes * (sum(int(st.rows_recv[r]) for r in range(self.world)) - int(st.rows_recv[self.rank]))
                     elif st.op == 3:
@@ -267,35 +286,21 @@ class DomainRun:
                 self.partition_fallbacks += 1
                 pos_mine, vel_mine = self.pos, self.vel
         self.partition_bytes = (self.world - 1) * 24 * nl
-        self.comm.all_gather(self.state_all[: 3 * N], pos_mine.contiguous().view(-1))
-        self.comm.all_gather(self.state_all[3 * N:], vel_mine.contiguous().view(-1))
+        yield "all_gather", self.state_all[: 3 * N], pos_mine.contiguous().view(-1)
+        yield "all_gather", self.state_all[3 * N:], vel_mine.contiguous().view(-1)
         self.eng.dist_partition(self.state_all, N, self.world, self.rank, self.buf)
         self.evals = 0
 
     # ---- one force evaluation -------------------------------------------------------------------
-    def local(self):
-        self.eng.dist_local(self.buf, self.n_local, self.nodes_send, self.pos_send)
-
-    def exchange(self):
-        self.comm.all_gather(self.nodes_all, self.nodes_send)
-        self.comm.all_gather(self.pos_all, self.pos_send)
-
-    def finish(self, param=None, elastic=True):
-        self.eng.dist_finish(self.nodes_all, self.pos_all, self.buf, self.acc, param)
-        if elastic and param is not None:
-            self.eng.add_elastic(self.pos, self.acc, self.n_local, param[3:])
-        self.evals += 1
-
     def force(self, param=None, elastic=True):
+        return _run(self._force(param, elastic), self.comm)
+
+    def _force(self, param, elastic):
         if self.rebalance > 0 and self.evals >= self.rebalance:
-            self.partition()
+            yield from self._partition(None, None)
         if self.let:
-            self._force_let(param)
-            if elastic and param is not None:
-                self.eng.add_elastic(self.pos, self.acc, self.n_local, param[3:])
-            self.evals += 1
-            return
-        if self.split:
+            yield from self._force_let(param)
+        elif self.split:
             # Three all-gathers, each started as soon as its data exists: positions + traversal records after the subtree
             # build, multipoles after the upward pass.  The traversal (which needs no multipoles) is enqueued behind the
             # first two; the multipoles -- 224 of the 240 bytes per node at order 6 -- travel under it.
@@ -303,40 +308,34 @@ class DomainRun:
             csz_send, mp_send = self.nodes_send[:cb], self.nodes_send[cb:]
             csz_all, mp_all = self.nodes_all[: G * cb], self.nodes_all[G * cb:]
             self.eng.dist_local_geom(self.buf, self.n_local, self.pos_send, csz_send)
-            h_pos = self.comm.all_gather_start(self.pos_all, self.pos_send)
-            h_csz = self.comm.all_gather_start(csz_all, csz_send)
+            h_pos = yield "all_gather_start", self.pos_all, self.pos_send
+            h_csz = yield "all_gather_start", csz_all, csz_send
             self.eng.dist_local_mpole(self.buf, self.n_local, mp_send)
-            h_mp = self.comm.all_gather_start(mp_all, mp_send)
+            h_mp = yield "all_gather_start", mp_all, mp_send
             h_pos.wait()
             h_csz.wait()
             self.eng.dist_finish_traverse(csz_all, self.pos_all)
             self._wait_far_field(h_mp)
             self.eng.dist_finish_rest(mp_all, self.buf, self.acc, param)
-            if elastic and param is not None:
-                self.eng.add_elastic(self.pos, self.acc, self.n_local, param[3:])
-            self.evals += 1
-            return
-        if hasattr(self.eng, "dist_local_build") and hasattr(self.comm, "all_gather_start"):
-            # the positions travel while the multipoles are still being computed
-            self.eng.dist_local_build(self.buf, self.n_local, self.pos_send)
-            h_pos = self.comm.all_gather_start(self.pos_all, self.pos_send)
-            self.eng.dist_local_upward(self.buf, self.n_local, self.nodes_send)
-            h_nodes = self.comm.all_gather_start(self.nodes_all, self.nodes_send)
-            h_pos.wait()
-            h_nodes.wait()
         else:
-            self.local()
-            self.exchange()
-        self.finish(param, elastic)
+            # one node block per rank
+            self.eng.dist_local(self.buf, self.n_local, self.nodes_send, self.pos_send)
+            yield "all_gather", self.nodes_all, self.nodes_send
+            yield "all_gather", self.pos_all, self.pos_send
+            self.eng.dist_finish(self.nodes_all, self.pos_all, self.buf, self.acc, param)
+        if elastic and param is not None:
+            self.eng.add_elastic(self.pos, self.acc, self.n_local, param[3:])
+        self.evals += 1
 
     # ---- LET exchange: one small all-gather (traversal records), the traversal, then two all-to-alls of exactly the
     # multipoles and positions the other ranks' lists name (include/nbco.h, nbco_dist_let_*) --------------------------
-    def _let_counts(self, csz_all, gather):
+    def _let_counts(self, csz_all):
         """selection + gathered count matrix on the host, [sender][let_counts] (int64); repeats while a rank reports list overflow"""
         G, S = self.world, int(self.lay.let_counts)
         for _ in range(8):
             self.eng.dist_let_select(csz_all, self.counts_send)
-            M = gather()
+            yield "all_gather", self.counts_all, self.counts_send
+            M = self.counts_all.cpu()   # the one host synchronisation of the evaluation
             if not bool(M.view(G, S)[:, 2 * G].any()):
                 return M
         raise RuntimeError("LET exchange: the traversal lists kept overflowing (raise list_factor)")
@@ -388,25 +387,25 @@ class DomainRun:
         return wait
 
     def _force_let_capped(self, param):
-        """one attempt in the capped form; False = void (the caller repeats the evaluation in the exact form)"""
+        """one attempt in the capped form; returns False = void (the caller repeats the evaluation in the exact form)"""
         cb, G, S, me = self.csz_bytes, self.world, int(self.lay.let_counts), self.rank
         csz_send, csz_all = self.nodes_send[:cb], self.nodes_all[: G * cb]
-        capn, capp = self._caps
+        capn, capp = self.cap_table(self._prevM, G, S, self.lay)
         send_n, send_p, recv_n, recv_p = capn[me].tolist(), capp[me].tolist(), capn[:, me].tolist(), capp[:, me].tolist()
         caps_out = torch.stack([capn[me], capp[me]], 1).reshape(-1).contiguous()
         caps_in = torch.stack([capn[:, me], capp[:, me]], 1).reshape(-1).contiguous()
         self.eng.dist_let_local_geom(self.buf, self.n_local, csz_send)
-        h_csz = self.comm.all_gather_start(csz_all, csz_send)
+        h_csz = yield "all_gather_start", csz_all, csz_send
         self.eng.dist_let_local_mpole(self.buf, self.n_local)
         h_csz.wait()
         self.eng.dist_let_select(csz_all, self.counts_send)
-        self.comm.all_gather(self.counts_all, self.counts_send)
+        yield "all_gather", self.counts_all, self.counts_send
         counts = self._counts_to_host()
         pos_send, mp_send = self._rows("ps", sum(send_p), 4), self._rows("ms", sum(send_n), self.rec)
         pos_recv, mp_recv = self._rows("pr", sum(recv_p), 4), self._rows("mr", sum(recv_n), self.rec)
         self.eng.dist_let_pack_capped(caps_out, pos_send, mp_send)
-        self.comm.all_to_all(pos_recv, pos_send, recv_p, send_p)
-        self.comm.all_to_all(mp_recv, mp_send, recv_n, send_n)
+        yield "all_to_all", pos_recv, pos_send, recv_p, send_p
+        yield "all_to_all", mp_recv, mp_send, recv_n, send_n
         self.eng.dist_let_finish_capped(caps_in, pos_recv, mp_recv, self.buf, self.acc, param)
         # everything is queued: only now look at the counts (they left the GPU long ago)
         M = counts()
@@ -415,31 +414,22 @@ class DomainRun:
         if not ok:
             self.let_redos += 1
             return False
-        self._set_prev(M)
+        self._prevM = M
         self.let_capped_evals += 1
         self.last_exchange_bytes = (G - 1) * (cb + 8 * S) + 16 * sum(recv_p) + 4 * self.rec * sum(recv_n)
         return True
 
-    def _set_prev(self, M):
-        self._prevM = M
-        if self.capped:
-            self._caps = self.cap_table(M, self.world, int(self.lay.let_counts), self.lay)
-
     def _force_let(self, param):
         cb, G = self.csz_bytes, self.world
         csz_send, csz_all = self.nodes_send[:cb], self.nodes_all[: G * cb]
-        if self.capped and self._prevM is not None and self._force_let_capped(param):
+        if self.capped and self._prevM is not None and (yield from self._force_let_capped(param)):
             return
-
-        def gather():
-            self.comm.all_gather(self.counts_all, self.counts_send)
-            return self.counts_all.cpu()   # the one host synchronisation of the evaluation
         for _ in range(6):
             self.eng.dist_let_local_geom(self.buf, self.n_local, csz_send)
-            h_csz = self.comm.all_gather_start(csz_all, csz_send)
+            h_csz = yield "all_gather_start", csz_all, csz_send
             self.eng.dist_let_local_mpole(self.buf, self.n_local)
             h_csz.wait()
-            M = self._let_counts(csz_all, gather)
+            M = yield from self._let_counts(csz_all)
             if not bool(M.view(G, int(self.lay.let_counts))[:, 2 * G + 1].any()):
                 break   # (else: some rank's build was flagged -- its flag came with the counts -- and everybody starts over)
         else:
@@ -448,10 +438,10 @@ class DomainRun:
         pos_send, mp_send = self._rows("ps", sum(send_p), 4), self._rows("ms", sum(send_n), self.rec)
         pos_recv, mp_recv = self._rows("pr", sum(recv_p), 4), self._rows("mr", sum(recv_n), self.rec)
         self.eng.dist_let_pack(M, pos_send, mp_send)
-        self.comm.all_to_all(pos_recv, pos_send, recv_p, send_p)
-        self.comm.all_to_all(mp_recv, mp_send, recv_n, send_n)
+        yield "all_to_all", pos_recv, pos_send, recv_p, send_p
+        yield "all_to_all", mp_recv, mp_send, recv_n, send_n
         self.eng.dist_let_finish(M, pos_recv, mp_recv, self.buf, self.acc, param)
-        self._set_prev(M)
+        self._prevM = M
         self.last_exchange_bytes = (G - 1) * (cb + 8 * int(self.lay.let_counts)) + 16 * sum(recv_p) + 4 * self.rec * sum(recv_n)
 
     def _wait_far_field(self, handle):
@@ -475,45 +465,56 @@ class DomainRun:
     # ---- reductions over all domains: a handful of scalars through an all-reduce -----------------
     def minmax(self):
         """component-wise bounds of all positions, (2, 3) tensor [min; max] (reductions.cuh:67-80)"""
+        return _run(self._minmax(), self.comm)
+
+    def _minmax(self):
         mm = self.eng.minmax(self.pos, self.n_local).clone()
-        self.comm.all_reduce(mm[0], "min")
-        self.comm.all_reduce(mm[1], "max")
+        yield "all_reduce", mm[0], "min"
+        yield "all_reduce", mm[1], "max"
         return mm
 
     def energy(self, param):
         """(kinetic, elastic, coulomb) energy of the whole system at the positions of the last force evaluation: every rank sums
         its own particles (the Coulomb part from the interaction lists of that evaluation, nbco_energy_fmm), one all-reduce of
         three scalars"""
+        return _run(self._energy(param), self.comm)
+
+    def _energy(self, param):
         kin, ela, cou = self.eng.energy_fmm(self.buf, self.n_local, param)
         t = torch.tensor([kin, ela, cou], dtype=torch.float64, device=self.device)
-        self.comm.all_reduce(t, "sum")
+        yield "all_reduce", t, "sum"
         return float(t[0]), float(t[1]), float(t[2])
 
     # ---- kick-drift-kick leapfrog on the local state (integrator.cuh:68-80) --------------------------
     def leapfrog(self, param, dt, elastic=True, first=False):
+        return _run(self._leapfrog(param, dt, elastic, first), self.comm)
+
+    def _leapfrog(self, param, dt, elastic, first):
         nl = self.n_local
         if first:
-            self.force(param, elastic)
+            yield from self._force(param, elastic)
         self.eng.step(self.vel, self.acc, 0.5 * dt, nl)
         self.eng.step(self.pos, self.vel, dt, nl)
-        self.force(param, elastic)
+        yield from self._force(param, elastic)
         self.eng.step(self.vel, self.acc, 0.5 * dt, nl)
-
 
     def leapfrog_steps(self, param, dt, steps, elastic=True):
         """`steps` kick-drift-kick steps; between two force evaluations ONE pass over the domain's state (nbco_dist_turnaround)
         instead of add_elastic + three step kernels + the next build's prologue.  Same final state as `steps` calls of leapfrog()."""
+        return _run(self._leapfrog_steps(param, dt, steps, elastic), self.comm)
+
+    def _leapfrog_steps(self, param, dt, steps, elastic):
         nl = self.n_local
         if steps <= 0:
             return
         if not hasattr(self.eng, "dist_turnaround") or param is None:
             for _ in range(steps):
-                self.leapfrog(param, dt, elastic)
+                yield from self._leapfrog(param, dt, elastic, False)
             return
         self.eng.step(self.vel, self.acc, 0.5 * dt, nl)
         self.eng.step(self.pos, self.vel, dt, nl)
         for s in range(steps):
-            self.force(param, elastic=False)
+            yield from self._force(param, False)
             if s + 1 < steps:
                 self.eng.dist_turnaround(self.buf, nl, param, dt, 1.0, elastic)
         if elastic:
@@ -521,229 +522,157 @@ class DomainRun:
         self.eng.step(self.vel, self.acc, 0.5 * dt, nl)
 
 
+def _run_lockstep(protocols):
+    """run the protocol generators of G ranks (rank order) in lockstep: advance all of them to their next request, perform
+    that collective across the ranks, resume each with its result; returns their results"""
+    replies = [None] * len(protocols)
+    while True:
+        reqs, results = [], []
+        for p, reply in zip(protocols, replies):
+            try:
+                reqs.append(p.send(reply))
+            except StopIteration as done:
+                results.append(done.value)
+        if results:
+            assert not reqs, "%d ranks finished, %d ask for %s" % (len(results), len(reqs), [q[0] for q in reqs])
+            return results
+        op = reqs[0][0]
+        assert all(q[0] == op for q in reqs), "the ranks ask for different collectives: %s" % [q[0] for q in reqs]
+        replies = _collective(op, *zip(*(q[1:] for q in reqs)))
+
+
+def _collective(op, *args):
+    """the comm method `op` across the ranks of a lockstep world: every argument is given as one value per rank (rank order);
+    returns the ranks' replies"""
+    if op in ("all_gather", "all_gather_start"):
+        outs, inps = args
+        assert len({i.shape for i in inps}) == 1, "all-gather of blocks of different sizes"
+        whole = torch.cat(inps)
+        for o in outs:
+            o.copy_(whole)
+        return [_Done()] * len(outs)   # (the completed handle of all_gather_start)
+    if op in ("all_reduce", "all_reduce_i32"):
+        ts, how = args
+        assert len(set(how)) == 1, "the ranks ask for different reductions: %s" % (how,)
+        stack = torch.stack(ts)
+        red = {"sum": stack.sum, "min": stack.amin, "max": stack.amax}[how[0]](0)
+        for t in ts:
+            t.copy_(red)
+        return ts
+    assert op == "all_to_all", op
+    outs, inps, out_rows, in_rows = args
+    for r, (out, want) in enumerate(zip(outs, out_rows)):
+        segs = []
+        for s, (inp, rows) in enumerate(zip(inps, in_rows)):
+            assert rows[r] == want[s], "rank %d sends %d rows to rank %d, which expects %d" % (s, rows[r], r, want[s])
+            off = sum(rows[:r])
+            segs.append(inp[off: off + rows[r]])
+        out.copy_(torch.cat(segs))
+    return [None] * len(outs)
+
+
+class _LockstepRank:
+    """comm of one rank of a lockstep world: its place only; the collectives are performed by _run_lockstep"""
+
+    def __init__(self, world, rank):
+        self.world, self.rank = world, rank
+
+    def _elsewhere(self, *args):
+        raise RuntimeError("lockstep ranks exchange through LoopbackWorld / LoopbackSlabs")
+
+    all_gather = all_gather_start = all_reduce_i32 = all_to_all = all_reduce = _elsewhere
+
+
+class _Tampered:
+    """a rank's engine whose dist_let_finish first hands the received records to tamper(rank, pos_recv, mp_recv)"""
+
+    def __init__(self, eng, tamper, rank):
+        self._eng, self._tamper, self._rank = eng, tamper, rank
+
+    def __getattr__(self, name):
+        return getattr(self._eng, name)
+
+    def dist_let_finish(self, M, pos_recv, mp_recv, *args):
+        self._tamper(self._rank, pos_recv, mp_recv)
+        return self._eng.dist_let_finish(M, pos_recv, mp_recv, *args)
+
+
 class LoopbackWorld:
     """G domains driven in lockstep inside ONE process / on ONE GPU (one Engine context per domain).
 
-    The collectives become concatenations, everything else is the production code path; this is how the
-    1-GPU box checks the sharded evaluation against the single-GPU one.
+    Every rank runs DomainRun's own protocol; only the collectives are done here, across the ranks (concatenations,
+    reductions, the segments of an all-to-all).  This is how the 1-GPU box checks the sharded evaluation against the
+    single-GPU one.  leapfrog / leapfrog_steps / minmax / energy run in the exchange form the runs chose at construction, which
+    is what ships; force / force_let choose the form per call (the all-gather form by default), for that call only.
     """
-
-    class _Comm:
-        def __init__(self, world, rank):
-            self.world, self.rank = world, rank
-
-        def all_gather(self, out, inp):   # filled in by LoopbackWorld
-            raise RuntimeError("loopback domains exchange through LoopbackWorld")
-
-        def all_gather_start(self, out, inp):
-            raise RuntimeError("loopback domains exchange through LoopbackWorld")
-
-        all_to_all = all_reduce_i32 = all_gather
 
     def __init__(self, engines, n_global, device=None, rebalance=0, gather_partition=None):
         G = len(engines)
-        self.runs = [DomainRun(e, n_global, LoopbackWorld._Comm(G, r), device=device, rebalance=rebalance, gather_partition=gather_partition)
+        self.runs = [DomainRun(e, n_global, _LockstepRank(G, r), device=device, rebalance=rebalance, gather_partition=gather_partition)
                      for r, e in enumerate(engines)]
         self.G = G
-        self._prevM = None
-        self.let_capped_evals = self.let_redos = 0
+
+    let_capped_evals = property(lambda self: self.runs[0].let_capped_evals)   # (every rank counts the same)
+    let_redos = property(lambda self: self.runs[0].let_redos)
+
+    def _lockstep(self, method, *args, **this_call):
+        """`method` of every run in lockstep; this_call[attribute]: values of run attributes (one per rank) for this call only"""
+        saved = [{a: vars(r)[a] for a in this_call if a in vars(r)} for r in self.runs]
+        try:
+            for a, values in this_call.items():
+                for r, v in zip(self.runs, values):
+                    setattr(r, a, v)
+            return _run_lockstep([getattr(r, method)(*args) for r in self.runs])
+        finally:
+            for r, s in zip(self.runs, saved):
+                for a in this_call:
+                    if a in s:
+                        setattr(r, a, s[a])
+                    else:
+                        delattr(r, a)
 
     def partition(self, pos_parts, vel_parts):
-        if all(r.dpart for r in self.runs):
-            try:
-                return self._repartition(pos_parts, vel_parts)
-            except Exception as e:   # pivot ties beyond the distributed select: the gathered form, as DomainRun.partition does
-                if getattr(e, "status", None) != _ERR_UNSUPPORTED:
-                    raise
-                for r in self.runs:
-                    r.use_gather_partition()
-                    r.partition_fallbacks += 1
-                pos_parts, vel_parts = [r.pos for r in self.runs], [r.vel for r in self.runs]
-        state = torch.cat([torch.cat([p.reshape(-1) for p in pos_parts]), torch.cat([v.reshape(-1) for v in vel_parts])])
-        for r in self.runs:
-            r.state_all.copy_(state)
-            r.partition_bytes = (r.world - 1) * 24 * r.n_local
-            r.eng.dist_partition(r.state_all, r.n_global, r.world, r.rank, r.buf)
-            r.evals = 0
+        _run_lockstep([r._partition(p, v) for r, p, v in zip(self.runs, pos_parts, vel_parts)])
 
-    def _repartition(self, pos_parts, vel_parts):
-        """nbco_dist_repartition_* in lockstep: every collective becomes arithmetic over the ranks' workspaces"""
-        runs, G = self.runs, self.G
-        for r, p, v in zip(runs, pos_parts, vel_parts):
-            if p.data_ptr() != r.pos.data_ptr():
-                r.pos.copy_(p.reshape(-1))
-            if v.data_ptr() != r.vel.data_ptr():
-                r.vel.copy_(v.reshape(-1))
-        sts = [r.eng.dist_repartition_begin(r.buf, r.n_global, G, r.rank, r.work) for r in runs]
-        moved = [0] * G
-        while sts[0].op != 0:
-            op = sts[0].op
-            assert all(s_.op == op and s_.count == sts[0].count for s_ in sts)
-            st = sts[0]
-            if op in (1, 2):
-                views = [r.work[st.send_off: st.send_off + 4 * st.count].view(torch.int32) for r in runs]
-                stack = torch.stack(views)
-                red = stack.min(0).values if op == 1 else stack.sum(0, dtype=torch.int32)
-                for v in views:
-                    v.copy_(red)
-            elif op == 3:
-                allb = torch.cat([r.work[st.send_off: st.send_off + st.count] for r in runs])
-                for r in runs:
-                    r.work[st.recv_off: st.recv_off + G * st.count].copy_(allb)
-            elif op == 4:
-                w = st.row_bytes
-                for r, sr in zip(runs, sts):
-                    parts = []
-                    for s_, ss in zip(runs, sts):
-                        off = ss.send_off + w * sum(int(ss.rows_send[q]) for q in range(r.rank))
-                        assert int(ss.rows_send[r.rank]) == int(sr.rows_recv[s_.rank])
-                        parts.append(s_.work[off: off + w * int(ss.rows_send[r.rank])])
-                    got = torch.cat(parts)
-                    r.work[sr.recv_off: sr.recv_off + got.numel()].copy_(got)
-            for r, sr in zip(runs, sts):   # bytes received, as DomainRun.partition counts them
-                if op == 4:
-                    moved[r.rank] += sr.row_bytes * (sum(int(sr.rows_recv[q]) for q in range(G)) - int(sr.rows_recv[r.rank]))
-                elif op == 3:
-                    moved[r.rank] += (G - 1) * sr.count
-                else:
-                    moved[r.rank] += 2 * 4 * sr.count
-            sts = [r.eng.dist_repartition_next() for r in runs]
-        for r in runs:
-            r.partition_bytes = moved[r.rank]
-            r.evals = 0
+    def leapfrog(self, param, dt, elastic=True, first=False):
+        self._lockstep("_leapfrog", param, dt, elastic, first)
 
-    def _force_let_capped(self, param, elastic, squeeze):
-        """one attempt in the capped form, in lockstep; squeeze(capn, capp) may shrink the table (tests of the void path)"""
-        runs, G = self.runs, self.G
-        cb, S = runs[0].csz_bytes, int(runs[0].lay.let_counts)
-        capn, capp = DomainRun.cap_table(self._prevM, G, S, runs[0].lay)
-        if squeeze is not None:
-            squeeze(capn, capp)
-        for r in runs:
-            r.eng.dist_let_local_geom(r.buf, r.n_local, r.nodes_send[:cb])
-        csz = torch.cat([r.nodes_send[:cb] for r in runs])
-        for r in runs:
-            r.eng.dist_let_local_mpole(r.buf, r.n_local)
-            r.nodes_all[: G * cb].copy_(csz)
-            r.eng.dist_let_select(r.nodes_all[: G * cb], r.counts_send)
-        counts = torch.cat([r.counts_send for r in runs])   # (stays on the device until everything is queued)
-        sends = []
-        for r in runs:
-            me = r.rank
-            ps, ms = r._rows("ps", int(capp[me].sum()), 4), r._rows("ms", int(capn[me].sum()), r.rec)
-            r.eng.dist_let_pack_capped(torch.stack([capn[me], capp[me]], 1).reshape(-1).contiguous(), ps, ms)
-            sends.append((ps, ms))
-        for r in runs:
-            me = r.rank
-            pp, mm = [], []
-            for s_, (ps, ms) in enumerate(sends):
-                op, on = int(capp[s_, :me].sum()), int(capn[s_, :me].sum())
-                pp.append(ps[op: op + int(capp[s_, me])])
-                mm.append(ms[on: on + int(capn[s_, me])])
-            pos_recv, mp_recv = torch.cat(pp).contiguous(), torch.cat(mm).contiguous()
-            r.eng.dist_let_finish_capped(torch.stack([capn[:, me], capp[:, me]], 1).reshape(-1).contiguous(), pos_recv, mp_recv, r.buf, r.acc, param)
-        M = counts.cpu()
-        ok = DomainRun.caps_hold(M, capn, capp, G, S)
-        for r in runs:
-            r.eng.dist_let_settle(ok)
-        if not ok:
-            self.let_redos += 1
-            return False
-        self._prevM = M
-        self.let_capped_evals += 1
-        for r in runs:
-            r.last_exchange_bytes = (G - 1) * (cb + 8 * S) + 16 * int(capp[:, r.rank].sum()) + 4 * r.rec * int(capn[:, r.rank].sum())
-            if elastic and param is not None:
-                r.eng.add_elastic(r.pos, r.acc, r.n_local, param[3:])
-            r.evals += 1
-        return True
+    def leapfrog_steps(self, param, dt, steps, elastic=True):
+        self._lockstep("_leapfrog_steps", param, dt, steps, elastic)
 
-    def force_let(self, param=None, elastic=True, tamper=None, capped=False, squeeze=None):
-        """the LET exchange in lockstep; tamper(rank, pos_recv, mp_recv) may damage what a rank received (guard tests);
-        capped: the form without a host round trip in the middle (after a first evaluation in the exact form)"""
-        runs, G = self.runs, self.G
-        cb, S = runs[0].csz_bytes, int(runs[0].lay.let_counts)
-        if capped and self._prevM is not None and self._force_let_capped(param, elastic, squeeze):
-            return
-        for _ in range(6):
-            for r in runs:
-                r.eng.dist_let_local_geom(r.buf, r.n_local, r.nodes_send[:cb])
-            csz = torch.cat([r.nodes_send[:cb] for r in runs])
-            for r in runs:
-                r.eng.dist_let_local_mpole(r.buf, r.n_local)
-                r.nodes_all[: G * cb].copy_(csz)
-            for _ in range(8):
-                for r in runs:
-                    r.eng.dist_let_select(r.nodes_all[: G * cb], r.counts_send)
-                M = torch.cat([r.counts_send for r in runs]).cpu()
-                if not bool(M.view(G, S)[:, 2 * G].any()):
-                    break
-            else:
-                raise RuntimeError("LET exchange: the traversal lists kept overflowing")
-            if not bool(M.view(G, S)[:, 2 * G + 1].any()):
-                break   # (else: some rank's build was flagged and everybody starts over)
-        else:
-            raise RuntimeError("LET exchange: a tree build kept being flagged")
-        M2 = M.view(G, S)
-        self._prevM = M
-        sends = []
-        for r in runs:
-            send_n, send_p, _, _ = r._let_splits(M)
-            ps, ms = r._rows("ps", sum(send_p), 4), r._rows("ms", sum(send_n), r.rec)
-            r.eng.dist_let_pack(M, ps, ms)
-            sends.append((ps, ms, send_p, send_n))
-        for r in runs:
-            me = r.rank
-            pp, mm = [], []
-            for s_, (ps, ms, send_p, send_n) in enumerate(sends):
-                op, on = sum(send_p[:me]), sum(send_n[:me])
-                pp.append(ps[op: op + send_p[me]])
-                mm.append(ms[on: on + send_n[me]])
-            pos_recv, mp_recv = torch.cat(pp).contiguous(), torch.cat(mm).contiguous()
-            if tamper is not None:
-                tamper(me, pos_recv, mp_recv)
-            r.eng.dist_let_finish(M, pos_recv, mp_recv, r.buf, r.acc, param)
-            r.last_exchange_bytes = (G - 1) * (cb + 8 * S) + 16 * int(M2[:, 2 * me + 1].sum()) + 4 * r.rec * int(M2[:, 2 * me].sum())
-            if elastic and param is not None:
-                r.eng.add_elastic(r.pos, r.acc, r.n_local, param[3:])
-            r.evals += 1
+    def minmax(self):
+        """every rank's DomainRun.minmax()"""
+        return self._lockstep("_minmax")
+
+    def energy(self, param):
+        """every rank's DomainRun.energy()"""
+        return self._lockstep("_energy", param)
 
     def force(self, param=None, elastic=True, split=None, let=False, capped=False, squeeze=None):
         """split=None: the two-stage exchange (records, then multipoles) when the engines offer it; False: one node block;
         let=True: the LET exchange (capped=True: its form without a host round trip, see force_let)"""
         if let:
             return self.force_let(param, elastic, capped=capped, squeeze=squeeze)
-        runs = self.runs
-        if split is None:
-            split = all(hasattr(r.eng, "dist_finish_traverse") and r.csz_bytes > 0 for r in runs)
-        if not split:
-            for r in runs:
-                r.local()
-            nodes = torch.cat([r.nodes_send for r in runs])
-            pos = torch.cat([r.pos_send for r in runs])
-            for r in runs:
-                r.nodes_all.copy_(nodes)
-                r.pos_all.copy_(pos)
-                r.finish(param, elastic)
-            return
-        cb, G = runs[0].csz_bytes, self.G
-        for r in runs:
-            r.eng.dist_local_geom(r.buf, r.n_local, r.pos_send, r.nodes_send[:cb])
-        pos = torch.cat([r.pos_send for r in runs])
-        csz = torch.cat([r.nodes_send[:cb] for r in runs])
-        for r in runs:
-            r.eng.dist_local_mpole(r.buf, r.n_local, r.nodes_send[cb:])
-        mp = torch.cat([r.nodes_send[cb:] for r in runs])
-        for r in runs:
-            r.pos_all.copy_(pos)
-            r.nodes_all[: G * cb].copy_(csz)
-            r.eng.dist_finish_traverse(r.nodes_all[: G * cb], r.pos_all)
-        for r in runs:
-            r.nodes_all[G * cb:].copy_(mp)
-            r.eng.dist_finish_rest(r.nodes_all[G * cb:], r.buf, r.acc, param)
-            if elastic and param is not None:
-                r.eng.add_elastic(r.pos, r.acc, r.n_local, param[3:])
-            r.evals += 1
+        self._lockstep("_force", param, elastic, let=[False] * self.G, split=[r.split if split is None else split for r in self.runs])
+
+    def force_let(self, param=None, elastic=True, tamper=None, capped=False, squeeze=None):
+        """the LET exchange in lockstep; tamper(rank, pos_recv, mp_recv) may damage what a rank received (guard tests);
+        capped: the form without a host round trip in the middle (after a first evaluation in the exact form);
+        squeeze(capn, capp) may shrink the segment table of a capped attempt, once per attempt for all ranks (tests of the void path)"""
+        G = self.G
+        this_call = dict(let=[True] * G, capped=[capped] * G)
+        if tamper is not None:
+            this_call["eng"] = [_Tampered(r.eng, tamper, r.rank) for r in self.runs]
+        if squeeze is not None:
+            table = []
+
+            def cap_table(*args):
+                if not table:   # (the first rank to start the attempt)
+                    table.append(DomainRun.cap_table(*args))
+                    squeeze(*table[0])
+                return table[0]
+            this_call["cap_table"] = [cap_table] * G
+        self._lockstep("_force", param, elastic, **this_call)
 
 
 class SlabRun:
@@ -787,62 +716,57 @@ class SlabRun:
         mx = max(b - a for a, b in zip(self.bounds[:-1], self.bounds[1:]))
         return (self.world - 1) * 12 * mx
 
-    def slab(self, param):
-        """this rank's part of the evaluation; returns (send block, largest slab, boundaries)"""
+    def force(self, param=None, elastic=True):
+        return _run(self._force(param, elastic), self.comm)
+
+    def _force(self, param, elastic):
         b = self.eng.fmm_oct_shard(self.buf, self.acc, self.n, param, self.world, self.rank, symmetric=self.symmetric)
         self.bounds = b
-        mx = max(max(y - x for x, y in zip(b[:-1], b[1:])), 1)
-        if self._pad is None or self._pad[0].numel() < 3 * mx:
-            cap = int(3 * mx * 1.25) + 64
-            self._pad = (torch.zeros(cap, dtype=torch.float32, device=self.device), torch.zeros(self.world * cap, dtype=torch.float32, device=self.device))
-        send = self._pad[0][: 3 * mx]
-        lo, hi = b[self.rank], b[self.rank + 1]
-        send[: 3 * (hi - lo)].copy_(self.acc[3 * lo: 3 * hi])
-        return send, mx, b
-
-    def assemble(self, recv, mx, b):
-        for r in range(self.world):
-            if r != self.rank and b[r + 1] > b[r]:
-                self.acc[3 * b[r]: 3 * b[r + 1]].copy_(recv[3 * mx * r: 3 * mx * r + 3 * (b[r + 1] - b[r])])
-
-    def force(self, param=None, elastic=True):
-        send, mx, b = self.slab(param)
         if self.world > 1:
-            recv = self._pad[1][: self.world * 3 * mx]
-            self.comm.all_gather(recv, send)
-            self.assemble(recv, mx, b)
+            # the own slab, padded to the largest, goes to every rank; the others' slabs are copied into place
+            mx = max(max(y - x for x, y in zip(b[:-1], b[1:])), 1)
+            if self._pad is None or self._pad[0].numel() < 3 * mx:
+                cap = int(3 * mx * 1.25) + 64
+                self._pad = (torch.zeros(cap, dtype=torch.float32, device=self.device), torch.zeros(self.world * cap, dtype=torch.float32, device=self.device))
+            send, recv = self._pad[0][: 3 * mx], self._pad[1][: self.world * 3 * mx]
+            lo, hi = b[self.rank], b[self.rank + 1]
+            send[: 3 * (hi - lo)].copy_(self.acc[3 * lo: 3 * hi])
+            yield "all_gather", recv, send
+            for r in range(self.world):
+                if r != self.rank and b[r + 1] > b[r]:
+                    self.acc[3 * b[r]: 3 * b[r + 1]].copy_(recv[3 * mx * r: 3 * mx * r + 3 * (b[r + 1] - b[r])])
         if elastic and param is not None:
             self.eng.add_elastic(self.pos, self.acc, self.n, param[3:])
 
     def leapfrog(self, param, dt, elastic=True):
+        return _run(self._leapfrog(param, dt, elastic), self.comm)
+
+    def _leapfrog(self, param, dt, elastic):
         n = self.n
         self.eng.step(self.vel, self.acc, 0.5 * dt, n)
         self.eng.step(self.pos, self.vel, dt, n)
-        self.force(param, elastic)
+        yield from self._force(param, elastic)
         self.eng.step(self.vel, self.acc, 0.5 * dt, n)
 
 
 class LoopbackSlabs:
-    """G SlabRuns in lockstep on one card (tests): the all-gather becomes a concatenation"""
-
-    class _Comm:
-        def __init__(self, world, rank):
-            self.world, self.rank = world, rank
+    """G SlabRuns in lockstep on one card (tests): every rank runs SlabRun's own protocol, the all-gather of the slabs is done
+    across the ranks"""
 
     def __init__(self, engines, n, device=None, symmetric=False):
         G = len(engines)
-        self.runs = [SlabRun(e, n, LoopbackSlabs._Comm(G, r), device=device, symmetric=symmetric) for r, e in enumerate(engines)]
+        self.runs = [SlabRun(e, n, _LockstepRank(G, r), device=device, symmetric=symmetric) for r, e in enumerate(engines)]
 
     def set_state(self, pos, vel):
         for r in self.runs:
             r.set_state(pos, vel)
 
+    def _lockstep(self, method, *args):
+        _run_lockstep([getattr(r, method)(*args) for r in self.runs])
+        assert all(r.bounds == self.runs[0].bounds for r in self.runs), "the ranks disagree on the slab boundaries"
+
     def force(self, param=None, elastic=True):
-        parts = [r.slab(param) for r in self.runs]
-        mx, b = parts[0][1], parts[0][2]
-        assert all(p[1] == mx and p[2] == b for p in parts), "the ranks disagree on the slab boundaries"
-        recv = torch.cat([p[0] for p in parts])
-        for r in self.runs:
-            r.assemble(recv, mx, b)
-            if elastic and param is not None:
-                r.eng.add_elastic(r.pos, r.acc, r.n, param[3:])
+        self._lockstep("_force", param, elastic)
+
+    def leapfrog(self, param, dt, elastic=True):
+        self._lockstep("_leapfrog", param, dt, elastic)

@@ -3,8 +3,9 @@
 The compute stages of the C-ABI library need a GPU, so here a small numpy test double speaks the same
 three-stage protocol (partition / local / finish) with an O(n^2) sum; what is under test is the host logic
 that the GPU box cannot rehearse with one card: buffer layout of the exchanges, rank order of the gathered
-blocks, the rebalance cadence and the leapfrog sequencing across real processes.  The sharded numerics
-themselves are checked bit for bit on the GPU (tests/test_gpu_dist.py)."""
+blocks, the rebalance cadence and the leapfrog sequencing across real processes.  The same doubles also run
+in lockstep inside one process (LoopbackWorld / LoopbackSlabs, the driver of the GPU tests), with the same
+assertions.  The sharded numerics themselves are checked bit for bit on the GPU (tests/test_gpu_dist.py)."""
 import os
 import socket
 import tempfile
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from coulomb_oscillators_amd.dist import DomainRun, SingleComm, SlabRun, TorchComm
+from coulomb_oscillators_amd.dist import DomainRun, LoopbackSlabs, LoopbackWorld, SingleComm, SlabRun, TorchComm
 
 
 class _Layout:
@@ -366,11 +367,34 @@ def _system(n, seed=11):
     return pos, vel, par
 
 
+def _state(run):
+    """rows [x y z vx vy vz ax ay az] of a domain"""
+    return torch.cat([run.pos.view(-1, 3), run.vel.view(-1, 3), run.acc.view(-1, 3)], dim=1).numpy()
+
+
 def _drive(run, par, steps, dt):
     run.force(par)
     for _ in range(steps):
         run.leapfrog(par, dt)
-    return torch.cat([run.pos.view(-1, 3), run.vel.view(-1, 3), run.acc.view(-1, 3)], dim=1).numpy()
+    return _state(run)
+
+
+def _engine(split, let, repart, capped):
+    """the numpy double of the protocol form under test"""
+    if repart:
+        return NumpyRepartEngine()
+    if capped:
+        return NumpyCappedLetEngine()
+    if let:
+        return NumpyLetEngine()
+    return NumpySplitEngine() if split else NumpyDomainEngine()
+
+
+def _single_process(n, steps, dt, rebalance):
+    pos, vel, par = _system(n)
+    one = DomainRun(NumpyDomainEngine(), n, SingleComm(), device=torch.device("cpu"), rebalance=rebalance)
+    one.partition(torch.from_numpy(pos).reshape(-1), torch.from_numpy(vel).reshape(-1))
+    return _drive(one, torch.from_numpy(par), steps, dt)
 
 
 def _worker(rank, world, port, n, steps, dt, rebalance, outdir, split=False, let=False, repart=False, capped=False):
@@ -381,7 +405,7 @@ def _worker(rank, world, port, n, steps, dt, rebalance, outdir, split=False, let
     try:
         pos, vel, par = _system(n)
         nl = n // world
-        eng = NumpyRepartEngine() if repart else (NumpyCappedLetEngine() if capped else NumpyLetEngine() if let else (NumpySplitEngine() if split else NumpyDomainEngine()))
+        eng = _engine(split, let, repart, capped)
         run = DomainRun(eng, n, TorchComm(), device=torch.device("cpu"), rebalance=rebalance)
         assert (run.world, run.rank, run.n_local) == (world, rank, nl) and run.split == split and run.let == let and run.dpart == repart and run.capped == capped
         if let:
@@ -407,23 +431,28 @@ def _free_port():
     return port
 
 
+# (world, split, let, repart, capped): the protocol forms of DomainRun, each with the numpy double that speaks it
+FORMS = [(2, False, False, False, False), (4, False, False, False, False), (2, True, False, False, False), (4, True, False, False, False),
+         (2, True, True, False, False), (4, True, True, False, False), (2, True, False, True, False), (4, True, False, True, False),
+         (2, True, True, False, True), (4, True, True, False, True)]
+
+
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("world,split,let,repart,capped", [(2, False, False, False, False), (4, False, False, False, False), (2, True, False, False, False),
-                                                           (4, True, False, False, False), (2, True, True, False, False), (4, True, True, False, False),
-                                                           (2, True, False, True, False), (4, True, False, True, False), (2, True, True, False, True),
-                                                           (4, True, True, False, True)])
+@pytest.mark.parametrize("world,split,let,repart,capped", FORMS)
 def test_domain_run_over_gloo_matches_single_process(world, split, let, repart, capped):
     import torch.multiprocessing as mp
     n, steps, dt, rebalance = 512, 5, 1e-2, 2
-    pos, vel, par = _system(n)
-    one = DomainRun(NumpyDomainEngine(), n, SingleComm(), device=torch.device("cpu"), rebalance=rebalance)
-    one.partition(torch.from_numpy(pos).reshape(-1), torch.from_numpy(vel).reshape(-1))
-    ref = _drive(one, torch.from_numpy(par), steps, dt)
+    ref = _single_process(n, steps, dt, rebalance)
     with tempfile.TemporaryDirectory() as d:
         mp.spawn(_worker, args=(world, _free_port(), n, steps, dt, rebalance, d, split, let, repart, capped), nprocs=world, join=True)
         got = np.concatenate([np.load(os.path.join(d, "rank%d.npy" % r)) for r in range(world)])
         calls = [open(os.path.join(d, "calls%d.txt" % r)).read().split() for r in range(world)]
         scal = [np.load(os.path.join(d, "scal%d.npy" % r)) for r in range(world)]
+    _check_domains(got, ref, calls, scal, steps, rebalance, split, let, capped)
+
+
+def _check_domains(got, ref, calls, scal, steps, rebalance, split, let, capped):
+    """states of all domains against the single-process run, per-rank engine calls against the protocol, bounds and energies"""
     # reductions over the domains: every rank holds the same global bounds and energies
     for sc in scal:
         np.testing.assert_array_equal(sc, scal[0])
@@ -458,6 +487,28 @@ def test_domain_run_over_gloo_matches_single_process(world, split, let, repart, 
             want += ["geom", "mpole", "traverse", "rest"] if split else ["local", "finish"]
         ev += 1
     assert all(c == want for c in calls), calls
+
+
+@pytest.mark.parametrize("world,split,let,repart,capped", FORMS)
+def test_loopback_world_matches_single_process(world, split, let, repart, capped):
+    """the same ranks driven in lockstep inside one process (LoopbackWorld, as the GPU tests drive the HIP engine): DomainRun's
+    own protocol, the same engine calls on every rank, the same states, bounds and energies as over gloo"""
+    n, steps, dt, rebalance = 512, 5, 1e-2, 2
+    ref = _single_process(n, steps, dt, rebalance)
+    pos, vel, par = _system(n)
+    par = torch.from_numpy(par)
+    nl = n // world
+    engines = [_engine(split, let, repart, capped) for _ in range(world)]
+    w = LoopbackWorld(engines, n, device=torch.device("cpu"), rebalance=rebalance)
+    assert all(r.split == split and r.let == let and r.dpart == repart and r.capped == capped for r in w.runs)
+    w.partition([torch.from_numpy(pos[r * nl:(r + 1) * nl]).reshape(-1) for r in range(world)],
+                [torch.from_numpy(vel[r * nl:(r + 1) * nl]).reshape(-1) for r in range(world)])
+    w.leapfrog(par, dt, first=True)
+    for _ in range(steps - 1):
+        w.leapfrog(par, dt)
+    got = np.concatenate([_state(r) for r in w.runs])
+    scal = [np.concatenate([mm.numpy().ravel(), [kin, ela]]) for mm, (kin, ela, _) in zip(w.minmax(), w.energy(par))]
+    _check_domains(got, ref, [e.calls for e in engines], scal, steps, rebalance, split, let, capped)
 
 
 def test_exchange_bytes_and_views():
@@ -544,3 +595,23 @@ def test_slab_run_over_gloo_matches_single_process(world):
         np.testing.assert_array_equal(got[r], ref)
         b = meta[r][1:]
         assert b[0] == 0 and b[-1] == n and meta[r][0] == (world - 1) * 12 * np.diff(b).max()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_loopback_slabs_match_single_process(world):
+    """the same slabs driven in lockstep inside one process (LoopbackSlabs): SlabRun's own protocol, the same results as over gloo"""
+    n, steps, dt = 600, 3, 1e-2
+    pos, vel, par = _system(n, seed=5)
+    par = torch.from_numpy(par)
+    ref = _slab_drive(SlabRun(NumpySlabEngine(), n, SingleComm(), device=torch.device("cpu")), pos, vel, par, steps, dt)
+    w = LoopbackSlabs([NumpySlabEngine() for _ in range(world)], n, device=torch.device("cpu"))
+    w.set_state(torch.from_numpy(pos), torch.from_numpy(vel))
+    for r in w.runs:
+        r.acc.fill_(float("nan"))
+    w.force(par)
+    for _ in range(steps):
+        w.leapfrog(par, dt)
+    for r in w.runs:
+        np.testing.assert_array_equal(r.buf.numpy(), ref)
+        b = r.bounds
+        assert b[0] == 0 and b[-1] == n and r.exchange_bytes() == (world - 1) * 12 * np.diff(b).max()

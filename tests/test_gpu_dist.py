@@ -1,6 +1,8 @@
 """GPU tests of the multi-GPU kd-domain sharding on ONE card: G domains, one context each, driven in
-lockstep by LoopbackWorld (the all-gathers become concatenations; everything else is the production path,
-through the C ABI).  Bar: the sharded evaluation equals the single-GPU evaluation -- tree order of the particles and
+lockstep by LoopbackWorld: every rank runs DomainRun's own protocol through the C ABI, and only the collectives are
+done inside the process, across the ranks (concatenations, reductions, the segments of an all-to-all).  The exchange
+form is chosen per call of force() / force_let(); leapfrog() / leapfrog_steps() run the form DomainRun chose at
+construction.  Bar: the sharded evaluation equals the single-GPU evaluation -- tree order of the particles and
 velocities carried along BIT FOR BIT; accelerations bit for bit with the one-directional near-field kernel
 (opts.p2p_mutual = 0) and to summation-order rounding (2e-6) with the mutual one, where a cross-domain leaf pair is
 evaluated by the target's owner instead of arriving as the other leaf's reaction -- and so inherits its parity with the
@@ -775,6 +777,42 @@ def test_sharded_turnaround_equals_step_kernels(oracle32, tree_steps, recut):
         torch.cuda.synchronize()
         # (the fused pass does not write the accelerations of the steps in between: compare positions, velocities and the last ones)
         out.append(torch.cat([r.buf for r in w.runs]))
+    assert torch.equal(out[0], out[1])
+
+
+@pytest.mark.parametrize("let", [True, False])
+def test_sharded_leapfrog_steps_equal_leapfrog_calls(oracle32, let):
+    """DomainRun.leapfrog_steps at G = 4 (nbco_dist_turnaround between the evaluations) against as many calls of
+    DomainRun.leapfrog, both in lockstep with a re-cut of the domains every 3 evaluations, i.e. inside the steps: same state
+    bit for bit (let=True: the form DomainRun ships, capped LET exchange; False: the two-stage all-gather)"""
+    import torch
+    from coulomb_oscillators_amd import Engine, LoopbackWorld
+    n, G, p, steps, dt = 1 << 17, 4, 4, 7, 5e-4
+    pos, vel = make_state(oracle32, n, "reference")
+    par = torch.from_numpy(oracle32.params(n)).cuda()
+    nl = n // G
+    out = []
+    for fused in (False, True):
+        world = LoopbackWorld([Engine(fmm_order=p, unsort=0, tree_steps=1) for _ in range(G)], n, rebalance=3)
+        for r in world.runs:
+            r.let = let
+        world.partition([torch.from_numpy(pos[r * nl:(r + 1) * nl]).cuda() for r in range(G)], [torch.from_numpy(vel[r * nl:(r + 1) * nl]).cuda() for r in range(G)])
+        world.leapfrog(par, dt, first=True)
+        if fused:
+            world.leapfrog_steps(par, dt, steps)
+        else:
+            for _ in range(steps):
+                world.leapfrog(par, dt)
+        torch.cuda.synchronize()
+        assert all(r.evals == 3 for r in world.runs)   # (9 evaluations: cut again before the 4th and the 7th)
+        if let:
+            assert world.let_capped_evals > 0
+            for r in world.runs:
+                r.eng.dist_let_check()
+        out.append(torch.cat([r.buf for r in world.runs]))
+        for r in world.runs:
+            r.eng.close()
+    assert bool(torch.isfinite(out[0]).all())
     assert torch.equal(out[0], out[1])
 
 
