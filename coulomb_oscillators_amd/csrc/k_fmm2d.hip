@@ -590,13 +590,20 @@ static int f2d_fmm_run(nbco_ctx *c, double *p, double *a, long long n, const dou
 	return f2d_done(c);
 }
 
+// what nbco_2d_fmm asks of n and the options; the integrators ask it before their first launch, so that a refused step moves nothing
+static int f2d_fmm_check(nbco_ctx *c, long long n)
+{
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: n must be below 2^31");
+	if (c->o.tree_radius < 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_radius must be >= 1");
+	if (c->o.tree_L == 1 || c->o.tree_L > kMaxL2 || c->o.tree_L < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_L must be 0 or 2..15");
+	return NBCO_OK;
+}
+
 static int f2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param)
 {
 	if (!c) return NBCO_ERR_ARG;
 	if (!p || !a || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: bad arguments");
-	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: n must be below 2^31");
-	if (c->o.tree_radius < 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_radius must be >= 1");
-	if (c->o.tree_L == 1 || c->o.tree_L > kMaxL2 || c->o.tree_L < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_L must be 0 or 2..15");
+	NBCO_TRY(f2d_fmm_check(c, n));
 	switch (c->o.fmm_order)
 	{
 	case 1: return f2d_fmm_run<1>(c, p, a, n, param);
@@ -680,6 +687,8 @@ int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long 
 	if (!c) return NBCO_ERR_ARG;
 	if (!buf || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: bad arguments");
 	if (kind < NBCO_2D_EVAL_DIRECT || kind > NBCO_2D_EVAL_FMM) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown evaluator kind");
+	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown scheme");
+	if (kind == NBCO_2D_EVAL_FMM) NBCO_TRY(f2d_fmm_check(c, n));
 	double *x = buf, *v = buf + 2 * n, *a = buf + 4 * n;
 	const long double dt = dt_, scale = scale_;
 	auto K = [&](long double s) { return f2d_step(c, v, a, s, n); };

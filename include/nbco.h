@@ -424,7 +424,8 @@ int nbco_2d_direct3(nbco_ctx *c, const double *p, double *a, long long n, const 
 int nbco_2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param);             /* fmm_cart.cuh:395 fmm_cart; v at p + 2n */
 /* integrator.cuh:22 compute_force: a = f(x), then a -= k o x when `elastic` (main.cu:85-89 coulombOscillatorFMM) */
 int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic);
-/* integrator.cuh:32-167 (NBCO_INTEG_*): long double coefficient arithmetic, each step b += a * ds in double */
+/* integrator.cuh:32-167 (NBCO_INTEG_*): long double coefficient arithmetic, each step b += a * ds in double.  Arguments and, for
+ * NBCO_2D_EVAL_FMM, the options nbco_2d_fmm would refuse are checked before the first launch: a refused step leaves buf as it was */
 int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
                       int elastic);
 /* `steps` calls of nbco_2d_integrate, bit for bit (main.cu:855-893 loop body) */
