@@ -3,6 +3,8 @@
 // CPU restatement of the reference's N-body "Coulomb oscillator" force / integrate path
 // (locuoco/coulomb_oscillators @ 2024_08_07, Simulation/*.cuh, the `*_cpu` functions).
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
+// The kd-tree evaluator also restates the two things the reference's GPU driver does differently from the CPU one (Opts::m2l_first,
+// Opts::reuse; fmm_cart3_kdtree.cuh:504-542, :1619-1645): that is the configuration the nbco3 binary runs.
 //
 // PARITY STATUS: the reference cannot be built in this image (it needs the CUDA runtime headers,
 // CUB and helper_math's CUDA vector types; writing stand-ins for them is not allowed), and it ships
@@ -398,6 +400,8 @@ struct Opts
 	int unsort;       // b_unsort
 	real dens_inhom;  // dens_inhom
 	int threads;      // CPU_THREADS
+	int m2l_first;    // 0: CPU traversal order (:586-609); 1: the GPU kernel's, fmm_dualTraversal<true> (:504-542, launched at :1668)
+	int reuse;        // 1: a non-rebuild evaluation of the GPU driver (:1619-1645) on the tree of the previous fmm_kd call
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -410,6 +414,7 @@ struct KdTree
 	std::vector<real> mpole, local;
 	std::vector<int> mult, index, splitdim, unsort;
 	std::vector<int> p2p, m2l; // flattened int2 lists
+	bool tree_order = false;   // the last evaluation left the caller's state in tree order (b_unsort = false)
 };
 static KdTree g_kd;
 
@@ -530,8 +535,13 @@ static bool kd_admissible(const KdTree& t, int n1, int n2, real par)
 	return parM * parM * std::max(sz1, sz2) < dist2;
 }
 
-// fmm_cart3_kdtree.cuh:569-611 (serial; leaf-leaf test first)
-static void kd_traverse(KdTree& t, real par)
+// fmm_cart3_kdtree.cuh:569-611 (serial; leaf-leaf test first).  m2l_first: the order of the GPU kernel with
+// b_m2l_first = true (:504-542): a self pair with children splits in three, then the admissibility test, and only a pair that
+// fails it is looked at as a leaf pair.  The kernel's blocks and its shared stack only change the order of the list entries
+// (atomic appends there); this serial stack gives the same sets.  The opening criterion stays the host branch of :401-414
+// (pow in SCAL): the device branch's __powf has no canonical rounding to restate, and the engine follows the host form.  The GPU
+// driver passes tree_radius on as a SCAL (:1617), the CPU driver truncates it to int (:1775): the caller chooses through o.radius.
+static void kd_traverse(KdTree& t, real par, bool m2l_first)
 {
 	t.p2p.clear();
 	t.m2l.clear();
@@ -545,7 +555,30 @@ static void kd_traverse(KdTree& t, real par)
 		auto np = stack.back();
 		stack.pop_back();
 		int a = np.first, b = np.second;
-		if (lc(a) >= ntot && lc(b) >= ntot)
+		if (m2l_first)
+		{
+			const bool leaves = lc(a) >= ntot && lc(b) >= ntot;
+			if (a == b && lc(a) < ntot)                                                                  // :513-519
+			{
+				stack.push_back({lc(a), lc(a)});
+				stack.push_back({lc(a), rc(a)});
+				stack.push_back({rc(a), rc(a)});
+			}
+			// (a leaf with itself gets here too: distance 0, never admissible)
+			else if (kd_admissible(t, a, b, par)) { t.m2l.push_back(a); t.m2l.push_back(b); }            // :520-525
+			else if (leaves) { if (a != b) { t.p2p.push_back(a); t.p2p.push_back(b); } }                 // :526-534
+			else if (lc(a) >= ntot || (lc(b) < ntot && kd_size(t, a) <= kd_size(t, b)))                  // :537-541
+			{
+				stack.push_back({a, lc(b)});
+				stack.push_back({a, rc(b)});
+			}
+			else
+			{
+				stack.push_back({lc(a), b});
+				stack.push_back({rc(a), b});
+			}
+		}
+		else if (lc(a) >= ntot && lc(b) >= ntot)
 		{
 			if (a != b) { t.p2p.push_back(a); t.p2p.push_back(b); }
 		}
@@ -587,21 +620,12 @@ static void p2p_block(vec3* a1, const vec3* p1, const vec3* p2, int m1, int m2, 
 	}
 }
 
-// The CPU driver, fmm_cart3_kdtree.cuh:1773-1929.  p points at [pos n | vel n], a at acc.
-static int fmm_kd(vec3* p, vec3* a, int n, const real* param, const Opts& o)
+// The rebuild block of the drivers (CPU :1833-1873, GPU :1619-1640): root box, level sorts, boxes and ranges of every node
+static void kd_build(KdTree& t, vec3* p, int n, int L, int T_)
 {
-	KdTree& t = g_kd;
-	const int P = o.p, T_ = std::max(1, o.threads);
-	const bool atomic = T_ > 1;
-	if (n <= 0 || P < 1 || P > 16) return -1;
-	const int L = kd_levels(n, P, o.dens_inhom), ntot = kd_ntot(L);
-	const int offM = sym_off(P), offL = tl_off(P + 1);
-	t.L = L; t.ntot = ntot; t.p = P; t.n = n;
-	t.center.assign(ntot, vec3{0, 0, 0});
+	const int ntot = t.ntot;
 	t.lbound.assign(ntot, vec3{0, 0, 0});
 	t.rbound.assign(ntot, vec3{0, 0, 0});
-	t.mpole.assign((size_t)ntot * offM, 0);
-	t.local.assign((size_t)ntot * offL, 0);
 	t.mult.assign(ntot, 0);
 	t.index.assign(ntot, 0);
 	t.splitdim.assign(ntot, 0);
@@ -625,6 +649,33 @@ static int fmm_kd(vec3* p, vec3* a, int n, const real* param, const Opts& o)
 		kd_sort_level(p, n, l, t.splitdim.data() + kd_beg(l), t.unsort, T_);
 	}
 	kd_eval_box(t, p, n, L, T_);
+}
+
+// The CPU driver, fmm_cart3_kdtree.cuh:1773-1929.  p points at [pos n | vel n], a at acc.
+//
+// o.m2l_first and o.reuse restate the two things the GPU driver (:1478-1771) does differently.  o.reuse is one evaluation for
+// which `b_unsort || counter % tree_steps == 0` (:1619) is false: everything inside that block is skipped -- the level sorts, and
+// evalBox with them, so index, splitdim, lbound, rbound and the permutation stay those of the last rebuild (the boxes are STALE:
+// particles may have left them) -- and the caller's positions are taken as already in tree order.  From centerLeaves (:1644) on
+// the evaluation is the usual one: leaf centroids, P2M, M2M with the parents' centres, a new traversal on the new centres and the
+// old boxes, near and far field.  The velocities are not touched (:1755 permutes them on a rebuild only).  A reuse call is refused
+// (return -3, nothing evaluated, the tree left as it was) unless the previous call left its state in tree order (unsort = 0) and
+// n, p and the number of levels are unchanged.
+static int fmm_kd(vec3* p, vec3* a, int n, const real* param, const Opts& o)
+{
+	KdTree& t = g_kd;
+	const int P = o.p, T_ = std::max(1, o.threads);
+	const bool atomic = T_ > 1;
+	if (n <= 0 || P < 1 || P > 16) return -1;
+	const int L = kd_levels(n, P, o.dens_inhom), ntot = kd_ntot(L);
+	const int offM = sym_off(P), offL = tl_off(P + 1);
+	const bool reuse = o.reuse != 0;
+	if (reuse && (o.unsort || !t.tree_order || t.ntot != ntot || t.L != L || t.p != P || t.n != n)) return -3;
+	t.L = L; t.ntot = ntot; t.p = P; t.n = n;
+	t.center.assign(ntot, vec3{0, 0, 0});
+	t.mpole.assign((size_t)ntot * offM, 0);   // :1648
+	t.local.assign((size_t)ntot * offL, 0);
+	if (!reuse) kd_build(t, p, n, L, T_);
 
 	const int beg = kd_beg(L), m = kd_cnt(L);
 	// multLeaves (appel.cuh:184-197), centerLeaves (appel.cuh:226-243)
@@ -684,7 +735,7 @@ static int fmm_kd(vec3* p, vec3* a, int n, const real* param, const Opts& o)
 			}
 		});
 
-	kd_traverse(t, o.radius);
+	kd_traverse(t, o.radius, o.m2l_first != 0);
 
 	// a = 0 (:1890 multiplies by the zero padding param[1])
 	for (int i = 0; i < n; ++i) a[i] = vec3{0, 0, 0};
@@ -771,12 +822,13 @@ static int fmm_kd(vec3* p, vec3* a, int n, const real* param, const Opts& o)
 		for (int i = 0; i < n; ++i) tmp[t.unsort[i]] = a[i];
 		std::memcpy(a, tmp.data(), sizeof(vec3) * n);
 	}
-	else
+	else if (!reuse)
 	{
-		// bring the velocities into tree order (:1919-1924)
+		// bring the velocities into tree order (:1919-1924; the GPU driver on a rebuild only, :1755-1760)
 		for (int i = 0; i < n; ++i) tmp[i] = p[n + t.unsort[i]];
 		std::memcpy(p + n, tmp.data(), sizeof(vec3) * n);
 	}
+	t.tree_order = !o.unsort;
 	return 0;
 }
 
@@ -1101,13 +1153,15 @@ struct oracle_opts
 	int unsort;
 	real dens_inhom;
 	int threads;
+	int m2l_first;
+	int reuse;
 };
 
 static Opts to_opts(const oracle_opts* o)
 {
 	Opts r;
 	r.p = o->p; r.radius = o->radius; r.eps2 = o->eps2; r.coll = o->coll; r.unsort = o->unsort;
-	r.dens_inhom = o->dens_inhom; r.threads = o->threads;
+	r.dens_inhom = o->dens_inhom; r.threads = o->threads; r.m2l_first = o->m2l_first; r.reuse = o->reuse;
 	return r;
 }
 

@@ -42,7 +42,8 @@ class Oracle:
 
         class Opts(C.Structure):
             _fields_ = [("p", C.c_int), ("radius", r), ("eps2", r), ("coll", C.c_int),
-                        ("unsort", C.c_int), ("dens_inhom", r), ("threads", C.c_int)]
+                        ("unsort", C.c_int), ("dens_inhom", r), ("threads", C.c_int),
+                        ("m2l_first", C.c_int), ("reuse", C.c_int)]
         self.Opts = Opts
         L = self.lib
         P = C.c_void_p
@@ -92,8 +93,9 @@ class Oracle:
     def ptr(a):
         return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
-    def opts(self, p=3, radius=1.0, eps2=1e-18, coll=True, unsort=True, dens_inhom=1.0, threads=1):
-        return self.Opts(int(p), radius, eps2, int(coll), int(unsort), dens_inhom, int(threads))
+    def opts(self, p=3, radius=1.0, eps2=1e-18, coll=True, unsort=True, dens_inhom=1.0, threads=1, m2l_first=0, reuse=0):
+        """m2l_first / reuse: the two things the reference's GPU driver does differently from its CPU driver (see fmm_kd)"""
+        return self.Opts(int(p), radius, eps2, int(coll), int(unsort), dens_inhom, int(threads), int(m2l_first), int(reuse))
 
     def params(self, n, xi=XI, omega0=OMEGA0):
         """par[] of main3.cu:685-692, arithmetic in SCAL."""
@@ -126,12 +128,28 @@ class Oracle:
         self.lib.oracle_direct3(self.ptr(pos), self.ptr(a), len(pos), self.ptr(param), eps2, threads)
         return a
 
-    def fmm_kd(self, posvel, param, **kw):
-        """posvel: (2, n, 3) array [pos|vel]; returns (posvel_out, acc) after the evaluation."""
+    def fmm_kd_rc(self, posvel, param, **kw):
+        """fmm_kd that hands the library's status back instead of asserting it: (rc, posvel_out, acc)"""
         pv = self.arr(posvel).copy(); n = pv.shape[1]
         a = np.zeros((n, 3), dtype=self.dtype)
         o = self.opts(**kw)
         rc = self.lib.oracle_fmm_kd(self.ptr(pv), self.ptr(a), n, self.ptr(param), C.byref(o))
+        return rc, pv, a
+
+    def fmm_kd(self, posvel, param, **kw):
+        """posvel: (2, n, 3) array [pos|vel]; returns (posvel_out, acc) after the evaluation.
+
+        m2l_first=1: the traversal order of the reference's GPU kernel (admissibility before the leaf test,
+        fmm_cart3_kdtree.cuh:504-542) instead of its CPU traversal (:586-609).
+
+        reuse=1: a non-rebuild evaluation of the GPU driver (:1619-1645) on the tree of the PREVIOUS fmm_kd call of this library:
+        posvel is taken as already in tree order; index / splitdim / lbound / rbound / unsort stay as they are (the boxes are
+        stale, as in the reference, which calls evalBox on a rebuild only); leaf centroids, multipoles, parent centres and both
+        interaction lists are recomputed; the velocities are not permuted (:1755).  It needs unsort=False here and in the call
+        that built the tree, and the same n, p and number of levels; otherwise the library refuses (status -3) and evaluates
+        nothing.  The library keeps ONE tree: any fmm_kd call in between (also through compute_force / integrate) replaces the
+        tree a later reuse call works on."""
+        rc, pv, a = self.fmm_kd_rc(posvel, param, **kw)
         assert rc == 0, rc
         return pv, a
 

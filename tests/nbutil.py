@@ -25,3 +25,69 @@ def canon_pairs(pairs):
     p = np.sort(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), axis=1)
     keys = p[:, 0] * (1 << 32) + p[:, 1]
     return np.sort(keys)
+
+
+def list_entries_changed(t0, t1):
+    """number of P2P / M2L list entries (unordered node pairs) that are in one of two trees' lists and not in the other's"""
+    return int(sum(len(np.setxor1d(canon_pairs(t0[k]), canon_pairs(t1[k]))) for k in ("p2p", "m2l")))
+
+
+def leaf_pair_cover(t):
+    """nleaf x nleaf matrix: how many times the interaction lists of the tree dict `t` (Oracle.kd_tree) serve each ordered pair of
+    leaves.  A node pair of either list stands for all leaf pairs below it, in both directions; every leaf is served with itself
+    once (the self P2P).  A correct dual traversal gives ones everywhere, whatever its admissibility rule."""
+    L = int(t["L"])
+    nleaf = 1 << L
+    d = np.zeros((nleaf + 1, nleaf + 1), dtype=np.int64)
+
+    def leaves_below(node):
+        node = np.asarray(node, dtype=np.int64)
+        lev = np.floor(np.log2(node + 1)).astype(np.int64)
+        w = 1 << (L - lev)
+        j = node + 1 - (1 << lev)
+        return j * w, (j + 1) * w
+
+    for key in ("p2p", "m2l"):
+        pairs = np.asarray(t[key], dtype=np.int64).reshape(-1, 2)
+        a0, a1 = leaves_below(pairs[:, 0])
+        b0, b1 = leaves_below(pairs[:, 1])
+        for r0, r1, c0, c1 in ((a0, a1, b0, b1), (b0, b1, a0, a1)):
+            np.add.at(d, (r0, c0), 1)
+            np.add.at(d, (r0, c1), -1)
+            np.add.at(d, (r1, c0), -1)
+            np.add.at(d, (r1, c1), 1)
+    cover = d.cumsum(axis=0).cumsum(axis=1)[:nleaf, :nleaf]
+    cover[np.arange(nleaf), np.arange(nleaf)] += 1
+    return cover
+
+
+def _powf(x, y):
+    """the C library's powf, which the opening criterion is written with (numpy's float32 power may be a vector routine that rounds
+    differently)"""
+    import ctypes
+    import ctypes.util
+    libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    libm.powf.argtypes = [ctypes.c_float, ctypes.c_float]
+    libm.powf.restype = ctypes.c_float
+    return np.float32(libm.powf(float(np.float32(x)), float(np.float32(y))))
+
+
+def kd_admissible_f32(t, pairs, p, par=1.0):
+    """The opening criterion (fmm_cart3_kdtree.cuh:401-414) of the node pairs `pairs`, recomputed in float32 from the tree dict's
+    center / lbound / rbound / mult, every product and sum rounded where the scalar code rounds it."""
+    f = np.float32
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n1, n2 = pairs[:, 0], pairs[:, 1]
+    c, lb, rb = (np.asarray(t[k], dtype=f) for k in ("center", "lbound", "rbound"))
+    mult = np.asarray(t["mult"], dtype=np.int64)
+
+    def dot3(v):
+        return (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+
+    dist2 = dot3(c[n2] - c[n1])
+    sz = np.maximum(dot3(rb[n1] - lb[n1]), dot3(rb[n2] - lb[n2]))
+    big = np.maximum(mult[n1], mult[n2])
+    expo = f(1) / f(3 * p + 6)
+    tab = {int(m): _powf(f(m) / f(mult[0]), expo) for m in np.unique(big)}
+    parm = f(par) * np.array([tab[int(m)] for m in big], dtype=f)
+    return (parm * parm) * sz < dist2
