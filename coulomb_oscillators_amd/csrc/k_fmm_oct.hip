@@ -528,6 +528,9 @@ static int oct_eval(nbco_ctx *c, float *p, float *a, long long n, const float *p
 		t.index = (int *)q;   // ntot + 1 entries
 		t.L = L; t.ntot = ntot; t.side = side; t.n = n;
 	}
+	// the tree-ordered positions and the sorted M2L keys of the last kd evaluation are overwritten below (pos4, m2l_keys_alt):
+	// nbco_energy_fmm must follow a kd evaluation, as after the direct sums (k_direct.hip)
+	c->last_eval.valid = false;
 	NBCO_TRY(c->reserve(c->pos4, sizeof(float4) * (size_t)n));
 	NBCO_TRY(c->reserve(c->pos4_alt, sizeof(float4) * (size_t)n));
 	NBCO_TRY(c->reserve(c->keys, sizeof(uint64_t) * (size_t)n));       // uint32 keys in / out share this buffer's halves

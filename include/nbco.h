@@ -69,7 +69,15 @@ typedef struct nbco_opts {
 	                       reference's CPU driver does (fmm_cart3_kdtree.cuh:1773-1929).  Setting a different
 	                       value (nbco_set_opts) starts a new schedule: the next evaluation rebuilds -- which
 	                       is also how a caller that puts a NEW state into an old context gets rid of the
-	                       tree of the state before. */
+	                       tree of the state before.  So does a change of fmm_order, dens_inhom, tree_L, unsort,
+	                       p2p_mutual or track_order.  A change of far_fp64, of n or of the level count also makes
+	                       the next evaluation rebuild, but does NOT restart the schedule: the context keeps
+	                       counting its evaluations, and the next scheduled rebuild is the one whose number since
+	                       the schedule began is a multiple of tree_steps (far_fp64 toggled before evaluation 3 of
+	                       a tree_steps = 8 schedule: 3 rebuilds, 4..7 reuse its tree, 8 rebuilds).  tree_radius,
+	                       m2l_first, coll and eps2 do not enter the tree build: changed between two evaluations
+	                       they leave the tree and the schedule alone and take effect on the next evaluation's
+	                       traversal and kernels. */
 	int   m2l_first;    /* 0: leaf-leaf pairs go to P2P before the admissibility test (reference CPU
 	                       traversal, fmm_cart3_kdtree.cuh:586-598); 1: admissibility first
 	                       (reference GPU traversal <true>, :520-534) */
@@ -157,7 +165,10 @@ int nbco_energy(nbco_ctx *c, const float *buf, long long n, const float *param, 
 /* the same with the Coulomb part from the interaction lists and multipoles of the LAST nbco_fmm_kdtree evaluation (which must
  * have been made at the positions in buf): near field pair by pair over the P2P list, far field by evaluating the multipole
  * expansions of the M2L sources at the particles (the reference's m2p_pot3, fmm_cart_base3.cuh:1474-1490), fp64, O(N log N)
- * instead of O(N^2).  Sharded runs: n = the domain's particles, every rank gets its share of the three sums. */
+ * instead of O(N^2).  Sharded runs: n = the domain's particles, every rank gets its share of the three sums.
+ * The kd evaluation must be the context's LAST evaluator call: nbco_direct / nbco_direct3 / nbco_energy and the octree evaluators
+ * (nbco_fmm_traceless, nbco_fmm_symmetric, nbco_fmm_oct_shard) reuse its position and list scratch, and after any of them this
+ * call is refused with NBCO_ERR_ARG until nbco_fmm_kdtree has run again. */
 int nbco_energy_fmm(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host);
 
 /* ---- introspection of the last kd-tree evaluation (parity tests, benchmarks) ----------------- */

@@ -91,3 +91,63 @@ def kd_admissible_f32(t, pairs, p, par=1.0):
     tab = {int(m): _powf(f(m) / f(mult[0]), expo) for m in np.unique(big)}
     parm = f(par) * np.array([tab[int(m)] for m in big], dtype=f)
     return (parm * parm) * sz < dist2
+
+
+NBCO_P2P_CHUNK = 16      # csrc/kd_list_kernels.hpp:67: entries of a target leaf's list per near-field work unit
+
+
+def p2p_work_units(t, coll=True):
+    """Work units of the near field of the tree dict `t` and the launch estimate for them, as (units, estimate(h_prev), longest target list).
+
+    units: the sum over leaves of ceil(entries / NBCO_P2P_CHUNK), entries = the leaf's directed P2P entries plus its self entry.
+    estimate: what k_fmm_kd.hip:498-501 derives from the PREVIOUS evaluation's list of h_prev leaf pairs for a tree of this one's
+    nleaf leaves: (2 (h + h / 4 + 1024) + nleaf) / NBCO_P2P_CHUNK + nleaf in integer arithmetic (its min() with the list capacity
+    is left out: the capacity is 48 x the node count and never binds on these inputs).  launch_p2p starts one wave per estimated
+    unit; a wave takes a second unit only where units > estimate."""
+    L = int(t["L"])
+    nleaf, first = 1 << L, (1 << L) - 1
+    pairs = np.asarray(t["p2p"], dtype=np.int64).reshape(-1, 2)
+    assert (pairs >= first).all(), "the P2P list of a complete kd-tree holds leaf pairs only"
+    entries = np.bincount((pairs - first).ravel(), minlength=nleaf) + (1 if coll else 0)
+    units = int(((entries + NBCO_P2P_CHUNK - 1) // NBCO_P2P_CHUNK).sum())
+
+    def estimate(h_prev):
+        h = int(h_prev)
+        return (2 * (h + h // 4 + 1024) + nleaf) // NBCO_P2P_CHUNK + nleaf
+
+    return units, estimate, int(entries.max())
+
+
+# ---- shared by the kd-driver and the long-lived-context modules -----------------------------------------------------------
+def expansion_err(got, want, nodes=None):
+    """largest deviation of a multipole / local array, relative to the largest component of its column over the whole tree;
+    nodes: the rows looked at (default: all)"""
+    scale = np.abs(want).max(axis=0, keepdims=True).clip(1e-30 if want.dtype == np.float32 else 1e-300)
+    err = np.abs(got - want) / scale
+    return float((err if nodes is None else err[nodes]).max())
+
+
+def assert_same_tree(engine, want, n, perm):
+    info = engine.kd_info()
+    assert (info.L, info.ntot, info.n) == (want["L"], want["ntot"], n)
+    for name in ("index", "mult", "splitdim", "lbound", "rbound", "center"):
+        np.testing.assert_array_equal(engine.kd_array(name), want[name], err_msg=name)
+    np.testing.assert_array_equal(engine.kd_array("unsort"), perm, err_msg="unsort")
+    for name in ("p2p", "m2l"):
+        np.testing.assert_array_equal(canon_pairs(engine.kd_array(name)), canon_pairs(want[name]), err_msg=name)
+    assert info.directed_p2p == directed_pairs(want["mult"], want["p2p"], want["L"])
+
+
+def drive_by_hand(eng, d, n, prm, dt, evals, force, on_eval=None):
+    """Leapfrog as the reference's loop runs it (main3.cu:832-846 over integrator.cuh:68-80: force; then per step kick, drift,
+    force, kick), spelled out so that the caller sees the state that enters every force evaluation."""
+    for k in range(evals):
+        if k:
+            eng.step(d[1], d[2], dt / 2, n)
+            eng.step(d[0], d[1], dt, n)
+        x_in = d[:2].cpu().numpy() if on_eval else None
+        force()
+        if on_eval:
+            on_eval(k, x_in)
+        if k:
+            eng.step(d[1], d[2], dt / 2, n)

@@ -6,6 +6,9 @@ unwritten, the next launch read it up to its capacity and classified whatever th
 tree -- and faulted.  A fresh process gets zero-filled memory, which is why the test passed when it was run alone.  The poisoned
 allocations make that situation deterministic, the device-side checks turn any such read into a count instead of a fault.
 
+Part 3 of the script puts the walks of tests/test_gpu_context_reuse.py that aim at stale launch estimates and shared scratch (its
+parts A, first alternation, and D) through the same build: a stale index then shows up as a count in one of the eight sites.
+
 Runs once, in a subprocess (the checked library is selected with NBCO_LIB before the package loads)."""
 import json
 import os
@@ -84,21 +87,40 @@ SCRIPT = textwrap.dedent('''
     torch.cuda.synchronize()
     assert all(torch.isfinite(r.acc).all() for r in w.runs)
     out["violations_total"] = en.violations()
+
+    # 3. one long-lived context (tests/test_gpu_context_reuse.py): the launch estimate taken from a small evaluation in front of
+    #    each large one, so that the waves of the near-field kernel take later work units through their prefetching hand-off, and
+    #    a reuse schedule with other calls of the same context between its steps -- each with that module's own assertions
+    sys.path.insert(0, %r)
+    import test_gpu_context_reuse as T
+    T.run_alternation(o, T.VARIANTS["one_directional"])
+    out["interrupted_schedule_identical"] = True
+    for mutual in (0, 1):
+        opts = dict(T.NBCO3, p2p_mutual=mutual)
+        plain = T.run_schedule(o, opts)
+        for block, interrupted in ((0, True), (4, False), (4, True)):     # as test_calls_in_between_do_not_disturb_a_schedule
+            same = bool(torch.equal(T.run_schedule(o, opts, block=block, interrupted=interrupted), plain))
+            out["interrupted_schedule_identical"] = out["interrupted_schedule_identical"] and same
+            out["schedule mutual {} block {} interrupted {}".format(mutual, block, interrupted)] = same
+    last = Engine()
+    out["violations_context_reuse"] = last.violations()
     print(json.dumps(out))
-''') % ROOT
+''') % (ROOT, os.path.join(ROOT, "tests"))
 
 
 def test_checked_build_with_poisoned_allocations():
     if not os.path.exists(CHECKED):
         pytest.fail("libnbco_hip_checked.so is not built (make -C coulomb_oscillators_amd/csrc)")
     env = dict(os.environ, NBCO_LIB=CHECKED, NBCO_POISON="1")
-    r = subprocess.run([sys.executable, "-c", SCRIPT], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, "-c", SCRIPT], capture_output=True, text=True, env=env, timeout=2400)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["overflow_reported"] and out["state_untouched"]
     assert out["violations_after_overflow"] == [0] * 8, out       # no launch read a slot that nothing had written
     assert out["err_after_recovery"] < 1e-5
     assert out["violations_total"] == [0] * 8, out
+    assert out["interrupted_schedule_identical"], out
+    assert out["violations_context_reuse"] == [0] * 8, out
 
 
 def test_production_build_has_no_checks(engine):

@@ -24,7 +24,7 @@ accelerations, which are what all of them feed, meet 1e-5 with a factor of ten t
 import numpy as np
 import pytest
 
-from nbutil import canon_pairs, directed_pairs, force_err, list_entries_changed
+from nbutil import assert_same_tree, canon_pairs, drive_by_hand, expansion_err, force_err, list_entries_changed
 
 pytestmark = pytest.mark.gpu
 
@@ -34,28 +34,9 @@ def dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
-def expansion_err(got, want, nodes=None):
-    """largest deviation of a multipole / local array, relative to the largest component of its column over the whole tree;
-    nodes: the rows looked at (default: all)"""
-    scale = np.abs(want).max(axis=0, keepdims=True).clip(1e-30 if want.dtype == np.float32 else 1e-300)
-    err = np.abs(got - want) / scale
-    return float((err if nodes is None else err[nodes]).max())
-
-
 def m2l_nodes(tree):
     """the nodes whose multipoles the far field reads (module docstring)"""
     return np.unique(np.asarray(tree["m2l"]).ravel())
-
-
-def assert_same_tree(engine, want, n, perm):
-    info = engine.kd_info()
-    assert (info.L, info.ntot, info.n) == (want["L"], want["ntot"], n)
-    for name in ("index", "mult", "splitdim", "lbound", "rbound", "center"):
-        np.testing.assert_array_equal(engine.kd_array(name), want[name], err_msg=name)
-    np.testing.assert_array_equal(engine.kd_array("unsort"), perm, err_msg="unsort")
-    for name in ("p2p", "m2l"):
-        np.testing.assert_array_equal(canon_pairs(engine.kd_array(name)), canon_pairs(want[name]), err_msg=name)
-    assert info.directed_p2p == directed_pairs(want["mult"], want["p2p"], want["L"])
 
 
 # ---- a. fresh builds with the M2L-first traversal ---------------------------------------------------------------------------
@@ -144,21 +125,6 @@ SCHEDULES = [
     (20000, 8, 8, 1, 5e-3, 4, dict(far_fp64=1)),
 ]
 _hand_driven = {}     # final host state of the schedules of (b) that have run in this session, for (c)
-
-
-def drive_by_hand(eng, d, n, prm, dt, evals, force, on_eval=None):
-    """Leapfrog as the reference's loop runs it (main3.cu:832-846 over integrator.cuh:68-80: force; then per step kick, drift,
-    force, kick), spelled out so that the caller sees the state that enters every force evaluation."""
-    for k in range(evals):
-        if k:
-            eng.step(d[1], d[2], dt / 2, n)
-            eng.step(d[0], d[1], dt, n)
-        x_in = d[:2].cpu().numpy() if on_eval else None
-        force()
-        if on_eval:
-            on_eval(k, x_in)
-        if k:
-            eng.step(d[1], d[2], dt / 2, n)
 
 
 @pytest.mark.parametrize("n,p,tree_steps,m2l_first,dt,evals,extra", SCHEDULES, ids=lambda v: str(v).replace(" ", "") if isinstance(v, dict) else None)

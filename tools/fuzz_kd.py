@@ -1,15 +1,30 @@
 #!/usr/bin/env python3
-"""Randomised differential run of the kd-tree evaluator against the oracle (GPU box): python tools/fuzz_kd.py [seed] [cases]
+"""Randomised differential run of the kd-tree evaluator against the oracle (GPU box): python tools/fuzz_kd.py [--one-context] [seed] [cases]
 Tree arrays and interaction lists must be identical; forces are compared with the fp32 oracle (1e-5) and, when they differ
 more, with the fp64 oracle.  Both traversal orders are drawn (m2l_first), and a share of the cases runs
 a short leapfrog sequence with tree reuse (unsort = 0, tree_steps = T) instead of one evaluation: at every evaluation the oracle is
 given the positions the engine is about to evaluate and rebuilds / reuses its tree as the engine must
-(tests/test_gpu_fmm_kd_driver.py has the scheme)."""
+(tests/test_gpu_fmm_kd_driver.py has the scheme).  --one-context keeps ONE context for the whole run and takes it from case to case
+with nbco_set_opts, as nbco3 does, instead of creating one per case: the walk through random (n, p, r) then also meets the launch
+estimates, grown scratch and sticky build modes that the case before left behind (tests/test_gpu_context_reuse.py)."""
 import sys, time, numpy as np, torch
 import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from coulomb_oscillators_amd import Engine
 from oracle.pyoracle import Oracle
 from nbutil import force_err, canon_pairs
+ONE_CONTEXT = "--one-context" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--one-context"]
+_shared = None
+def context(**opts):
+    """the context of a case: a new one, or (--one-context) the run's only one, set to the case's options"""
+    global _shared
+    if not ONE_CONTEXT: return Engine(**opts)
+    full = dict(unsort=1, tree_steps=1, tree_radius=1.0, dens_inhom=1.0, m2l_first=0); full.update(opts)
+    if _shared is None: _shared = Engine(**full)
+    else: _shared.set(**full)
+    return _shared
+def release(e):
+    if not ONE_CONTEXT: e.close()
 o = Oracle(np.float32)
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 bad = 0
@@ -22,7 +37,7 @@ def arbitrate(got, want, pv, par, okw):
     return eg <= 2 * ec + 1e-6, f" [vs fp64: gpu {eg:.2e}, fp32 oracle {ec:.2e}]"
 def reuse_case(n, p, buf, par, radius, dens, m2l_first, T, evals, dt):
     """0 = every evaluation of the sequence agrees with the oracle, 1 otherwise"""
-    e = Engine(fmm_order=p, unsort=0, tree_steps=T, tree_radius=radius, dens_inhom=dens, m2l_first=m2l_first)
+    e = context(fmm_order=p, unsort=0, tree_steps=T, tree_radius=radius, dens_inhom=dens, m2l_first=m2l_first)
     d = torch.from_numpy(buf.copy()).cuda(); prm = torch.from_numpy(par).cuda()
     ok, worst, changed, built = True, 0.0, 0, None
     for k in range(evals):
@@ -44,7 +59,7 @@ def reuse_case(n, p, buf, par, radius, dens, m2l_first, T, evals, dt):
         e.add_elastic(d[0], d[2], n, prm[3:])
         if k: e.step(d[1], d[2], dt / 2, n)
     print("OK " if ok else "BAD", f"n={n} p={p} r={radius} i={dens} m2l_first={m2l_first} reuse T={T} evals={evals} dt={dt:g} L={e.kd_info().L} worst err={worst:.2e} list entries changed {changed}", flush=True)
-    e.close()
+    release(e)
     return 0 if ok else 1
 for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 40):
     n = int(rng.choice([rng.integers(2, 300), rng.integers(300, 9000), rng.integers(9000, 70000), rng.integers(70000, 300000)]))
@@ -74,7 +89,7 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 40):
     except Exception as ex:
         print("oracle failed", n, p, kind, ex); continue
     tree = o.kd_tree()
-    e = Engine(fmm_order=p, unsort=1, tree_radius=radius, dens_inhom=dens, m2l_first=m2l_first)
+    e = context(fmm_order=p, unsort=1, tree_radius=radius, dens_inhom=dens, m2l_first=m2l_first)
     d = torch.from_numpy(buf[:2].copy()).cuda(); a = torch.zeros((n, 3), device="cuda"); prm = torch.from_numpy(par).cuda()
     try:
         e.fmm_cart3_kdtree(d, a, n, prm); torch.cuda.synchronize()
@@ -98,5 +113,5 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 40):
         print("OK " if ok else "BAD", f"n={n} p={p} {kind} r={radius} i={dens} m2l_first={m2l_first} L={info.L} mode={info.build_mode} err={err:.2e} lists={same_lists} tree={same_tree}{note}", flush=True)
     except Exception as ex:
         bad += 1; print("EXC", n, p, kind, radius, dens, ex, flush=True)
-    e.close()
+    release(e)
 print("bad:", bad)
