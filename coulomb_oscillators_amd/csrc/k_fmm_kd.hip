@@ -25,14 +25,14 @@
 //             dimensionless gradient tensors (no fp32 overflow for p = 10).
 //   L2P       one thread per particle; fused with the near-field sum, the final rescale by param[0] and the scatter
 //             back to the caller's order.
-//   multi-GPU kd-domain sharding: the same two stages (kd_build_upward on the own subtree, kd_interact on the
-//             assembled global tree, pruned to the own domain), see the section at the end of this file.
+//   multi-GPU kd-domain sharding: the same stages (kd_build, kd_upward on the own subtree; kd_traverse, kd_fields on
+//             the assembled global tree, pruned to the own domain), see the section at the end of this file.
+// host side: fmm_kdtree_eval loops over kd_build, kd_upward, kd_traverse and kd_fields until kd_retry finds nothing to repeat.
 #include "nbco_internal.hpp"
 #include "k_p2p.hpp"
 #include "kd_common.hpp"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
-#include <functional>
 #include <cmath>
 #include <algorithm>
 #include <vector>
@@ -78,7 +78,6 @@ __host__ __device__ inline bool dom_touch(const Dom dm, int node)
 	const int pos = node - ((1 << l) - 1);
 	return l >= dm.d ? (pos >> (l - dm.d)) == dm.g : (dm.g >> (dm.d - l)) == pos;
 }
-
 
 #include "kd_build_kernels.hpp"   // tree geometry (rounded like the oracle), build prologue, the fused turnaround pass, per-level kernels of the sorting build, the in-LDS subtree build
 #include "kd_traverse_kernels.hpp"   // dual tree traversal: admissibility, the level-synchronous frontier kernel, its init / finish kernels
@@ -238,7 +237,7 @@ static int kd_carve(nbco_ctx *c, DevBuf &buf, KdTreeDev &k, int ntot, int offM, 
 // overflow, one global stable radix sort per level.  The root's box / split axis must be in place; on return
 // pos / unsort point at the buffers holding the result and the boxes of level l0 are written.
 static int kd_build_top(nbco_ctx *c, const TreeView &tv, float4 *&pos, float4 *&pos_alt, int *&unsort, int *&unsort_alt, long long n, int l0,
-                        bool use_select, bool select_ready = false, bool warm = false)
+                        bool use_select, bool select_ready = false, bool warm = false, const KdRoot &root = KdRoot{})
 {
 	hipStream_t st = c->stream;
 	if (use_select && l0 > 0 && !select_ready) NBCO_TRY(kd_select_begin(c, l0));
@@ -246,7 +245,7 @@ static int kd_build_top(nbco_ctx *c, const TreeView &tv, float4 *&pos, float4 *&
 	{
 		if (use_select)
 			NBCO_TRY(kd_select_level(c, l, n, pos, unsort, pos_alt, unsort_alt, tv.lbound, tv.rbound, tv.splitdim, tv.index,
-			                         c->counters.as<int>() + 110, warm));
+			                         c->counters.as<int>() + 110, warm, root));
 		else
 		{
 			if (l > 0) hipLaunchKernelGGL(kd_box_kernel, dim3(grid1d(kd_cnt(l))), dim3(kBlock), 0, st, tv, pos, n, l);
@@ -277,111 +276,113 @@ static int kd_reserve_particles(nbco_ctx *c, long long n)
 	return NBCO_OK;
 }
 
-// ---- stage 1: tree over p[0..n) with L levels + upward pass ---------------------------------------------
-// root6 (device, {lbound, rbound}) overrides the root box: the box of a kd-domain is inherited from the
-// global tree's top splits.  On return c->pos4 / c->unsort hold the tree-ordered positions and the map
-// back to the caller's order.
-// stage: 0 = build + upward, 1 = build only, 2 = upward only (of the tree built by the previous stage-1 call)
-static int kd_build_upward(nbco_ctx *c, const float *p, long long n, int L, const float *root6, bool &rebuild, int stage = 0)
+// levels whose nodes exceed the LDS slice of the subtree kernel: built by selection (or by the sorting build)
+static int kd_top_levels(long long n, int L)
+{
+	int l0 = 0;
+	while (l0 < L && (n + (1LL << l0) - 1) / (1LL << l0) > kSubS) ++l0;
+	return l0;
+}
+
+// ---- build: tree over p[0..n) with L levels below `root`, its leaves, centres and traversal records ---------
+// On return c->pos4 / c->unsort hold the tree-ordered positions and the map back to the caller's order.
+static int kd_build(nbco_ctx *c, const float *p, long long n, int L, const KdRoot &root, bool &rebuild, KdStepLink *link)
 {
 	const int P = c->o.fmm_order;
 	const int ntot = (1 << (L + 1)) - 1, nleaf = 1 << L;
 	const int mlt_max = (int)((n - 1) / nleaf + 1);
 	hipStream_t st = c->stream;
-	if (stage != 2)
-	{
-		NBCO_TRY(c->join_aux());   // e.g. the multipole chain of an evaluation that is being redone
-		KdTreeDev &k = c->kd;
-		const int old_real = k.real_bytes;
-		NBCO_TRY(kd_carve(c, c->treebuf, k, ntot, sym_off(P), tl_off(P + 1)));
-		const bool topo_change = k.L != L || k.ntot != ntot || k.order != P || k.n != n || k.real_bytes != old_real;
-		if (topo_change) c->tree_valid = false;
-		k.L = L; k.ntot = ntot; k.order = P; k.mlt_max = mlt_max; k.n = n;
-		NBCO_TRY(kd_reserve_particles(c, n));
-		rebuild = c->o.unsort || !c->tree_valid || (c->eval_counter % c->o.tree_steps) == 0;
-	}
+	NBCO_TRY(c->join_aux());   // e.g. the multipole chain of an evaluation that is being redone
+	KdTreeDev &k = c->kd;
+	const int old_real = k.real_bytes;
+	NBCO_TRY(kd_carve(c, c->treebuf, k, ntot, sym_off(P), tl_off(P + 1)));
+	const bool topo_change = k.L != L || k.ntot != ntot || k.order != P || k.n != n || k.real_bytes != old_real;
+	if (topo_change) c->tree_valid = false;
+	k.L = L; k.ntot = ntot; k.order = P; k.mlt_max = mlt_max; k.n = n;
+	NBCO_TRY(kd_reserve_particles(c, n));
+	rebuild = c->o.unsort || !c->tree_valid || (c->eval_counter % c->o.tree_steps) == 0;
 	TreeView tv = view_of(c->kd);
 	float4 *pos = c->pos4.as<float4>(), *pos_alt = c->pos4_alt.as<float4>();
 	int *unsort = c->unsort.as<int>(), *unsort_alt = c->unsort_alt.as<int>();
-	if (stage != 2)
+	PhaseScope ph(c, NBCO_PH_BUILD);
+	const int prep_done = link ? link->prep_done : 0;
+	if (rebuild)
 	{
-		PhaseScope ph(c, NBCO_PH_BUILD);
-		if (rebuild)
+		const int l0 = kd_top_levels(n, L);
+		const bool use_select = !c->force_sort_build;
+		long long words_a = 0, words_b = 0;
+		if (use_select && l0 > 0) NBCO_TRY(kd_select_begin(c, l0, false, &words_a, &words_b));
+		if (!c->prep_state.ptr)
 		{
-			// levels whose nodes exceed the LDS slice
-			int l0 = 0;
-			while (l0 < L && (n + (1LL << l0) - 1) / (1LL << l0) > kSubS) ++l0;
-			const bool use_select = !c->force_sort_build;
-			long long words_a = 0, words_b = 0;
-			if (use_select && l0 > 0) NBCO_TRY(kd_select_begin(c, l0, false, &words_a, &words_b));
-			if (!c->prep_state.ptr)
-			{
-				NBCO_TRY(c->reserve(c->prep_state, 64));
-				const unsigned arm[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-				NBCO_HIP(hipMemcpyAsync(c->prep_state.ptr, arm, sizeof arm, hipMemcpyHostToDevice, st));
-				NBCO_HIP(hipStreamSynchronize(st));   // `arm` lives on this stack frame; happens once per context
-			}
-			// A pivot with more ties than the resolver takes (flag -> the sorting build redoes the evaluation) leaves slots
-			// of a level's output unwritten, and the rest of this evaluation still runs on them: every slot of both
-			// permutation buffers must hold an index below n at all times.  From the second level on the buffers hold older
-			// permutations; the alternate buffer is primed once per particle count.
-			if (c->perm_primed_n != n)
-			{
-				hipLaunchKernelGGL(iota_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, unsort_alt, n);
-				hipLaunchKernelGGL(iota_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, unsort, n);
-				c->perm_primed_n = n;
-			}
-			// pack + identity permutation + bounding box + root node + cleared selection state: one launch
-			// (nbco_integrate_steps: the pass between two steps has done all of it, kd_turnaround)
-			if (c->skip_prep != 1)
+			NBCO_TRY(c->reserve(c->prep_state, 64));
+			const unsigned arm[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
+			NBCO_HIP(hipMemcpyAsync(c->prep_state.ptr, arm, sizeof arm, hipMemcpyHostToDevice, st));
+			NBCO_HIP(hipStreamSynchronize(st));   // `arm` lives on this stack frame; happens once per context
+		}
+		// A pivot with more ties than the resolver takes (flag -> the sorting build redoes the evaluation) leaves slots
+		// of a level's output unwritten, and the rest of this evaluation still runs on them: every slot of both
+		// permutation buffers must hold an index below n at all times.  From the second level on the buffers hold older
+		// permutations; the alternate buffer is primed once per particle count.
+		if (c->perm_primed_n != n)
+		{
+			hipLaunchKernelGGL(iota_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, unsort_alt, n);
+			hipLaunchKernelGGL(iota_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, unsort, n);
+			c->perm_primed_n = n;
+		}
+		// pack + identity permutation + bounding box + root node + cleared selection state: one launch
+		// (nbco_integrate_steps: the pass between two steps has done all of it, kd_turnaround)
+		if (prep_done != 1)
 			hipLaunchKernelGGL(kd_prep_kernel, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, p, n, pos, unsort, c->sel_hist.as<uint32_t>(), words_a,
-			                   c->sel_nodes.as<uint32_t>(), words_b, c->counters.as<int>() + 110, c->prep_state.as<unsigned>(), tv, root6);
-			// the previous build's boxes are still in the tree arrays: select around its pivots (one pass per level instead of two)
-			bool warm = use_select && l0 > 0 && c->sel_warm_enabled && c->tree_valid && !c->sel_three_pass;
-			if (warm && c->sel_warm_cooldown > 0) { --c->sel_warm_cooldown; warm = false; }
-			c->sel_warm_used = warm;
-			if (warm) ++c->sel_warm_builds;
-			NBCO_TRY(kd_build_top(c, tv, pos, pos_alt, unsort, unsort_alt, n, l0, use_select, true, warm));
-			// the rest of every level-l0 subtree inside one workgroup's LDS
-			hipLaunchKernelGGL(kd_subtree_kernel, dim3(kd_cnt(l0)), dim3(kSubT), 0, st, tv, (const float4 *)pos, (const int *)unsort, pos_alt, unsort_alt, n, l0,
-			                   use_select ? 1 : 0, c->sel_three_pass ? 0 : 1, c->counters.as<int>() + 110, c->top_sd, c->top_root1);
+			                   c->sel_nodes.as<uint32_t>(), words_b, c->counters.as<int>() + 110, c->prep_state.as<unsigned>(), tv, root.root6);
+		// the previous build's boxes are still in the tree arrays: select around its pivots (one pass per level instead of two)
+		bool warm = use_select && l0 > 0 && c->sel_warm_enabled && c->tree_valid && !c->sel_three_pass;
+		if (warm && c->sel_warm_cooldown > 0) { --c->sel_warm_cooldown; warm = false; }
+		c->sel_warm_used = warm;
+		if (warm) ++c->sel_warm_builds;
+		NBCO_TRY(kd_build_top(c, tv, pos, pos_alt, unsort, unsort_alt, n, l0, use_select, true, warm, root));
+		// the rest of every level-l0 subtree inside one workgroup's LDS
+		int launches = 1;
 #ifdef NBCO_SUBTREE_PROF
-			// the kernel only reads its inputs: a second launch right behind the first one repeats it with warm instruction caches
-			if (std::getenv("NBCO_SUBTREE_TWICE"))
-				hipLaunchKernelGGL(kd_subtree_kernel, dim3(kd_cnt(l0)), dim3(kSubT), 0, st, tv, (const float4 *)pos, (const int *)unsort, pos_alt, unsort_alt, n, l0,
-				                   use_select ? 1 : 0, c->sel_three_pass ? 0 : 1, c->counters.as<int>() + 110, c->top_sd, c->top_root1);
+		// the kernel only reads its inputs: a second launch right behind the first one repeats it with warm instruction caches
+		if (std::getenv("NBCO_SUBTREE_TWICE")) launches = 2;
 #endif
-			std::swap(pos, pos_alt);
-			std::swap(unsort, unsort_alt);
-			NBCO_HIP(hipGetLastError());
-			// keep the "current" buffers in the primary slots
-			if (pos != c->pos4.as<float4>()) { std::swap(c->pos4, c->pos4_alt); std::swap(c->unsort, c->unsort_alt); }
-			pos = c->pos4.as<float4>();
-		}
-		else
-		{
-			// tree reused: the caller's positions are already in tree order
-			c->sel_warm_used = false;
-			if (c->skip_prep == 0)
-			{
-				NBCO_TRY(launch_pack4(c, pos, p, n));
-				NBCO_HIP(hipMemsetAsync(c->counters.as<int>() + 110, 0, sizeof(int), st));
-			}
-		}
-		c->skip_prep = 0;
-		if (!rebuild) hipLaunchKernelGGL(kd_leaf_kernel, dim3(grid1d(nleaf)), dim3(kBlock), 0, st, tv, pos, n);   // (a rebuild's subtree kernel did it)
-		// centres and traversal records of all nodes first (2 launches): that is all the traversal needs, so the multipole
-		// chain (P2M + M2M, generated register-resident bodies of k_farfield.hip) runs beside it on the second stream
-		NBCO_TRY(launch_kd_centres(c, tv.center, tv.mult, L, tv.lbound, tv.rbound, tv.csz));
+		for (int i = 0; i < launches; ++i)
+			hipLaunchKernelGGL(kd_subtree_kernel, dim3(kd_cnt(l0)), dim3(kSubT), 0, st, tv, (const float4 *)pos, (const int *)unsort, pos_alt, unsort_alt, n, l0,
+			                   use_select ? 1 : 0, c->sel_three_pass ? 0 : 1, c->counters.as<int>() + 110, root.top_sd, root.top_root1);
+		std::swap(pos, pos_alt);
+		std::swap(unsort, unsort_alt);
 		NBCO_HIP(hipGetLastError());
+		// keep the "current" buffers in the primary slots
+		if (pos != c->pos4.as<float4>()) { std::swap(c->pos4, c->pos4_alt); std::swap(c->unsort, c->unsort_alt); }
 	}
-	if (stage == 1) return NBCO_OK;
+	else
 	{
-		NBCO_TRY(c->fork_aux());
-		StreamScope on_aux(c, c->aux);
-		PhaseScope ph(c, NBCO_PH_P2M_M2M);
-		NBCO_TRY(launch_upward_gen(c, P, pos, tv.center, tv.mpole, tv.mult, tv.index, L, 0, c->kd.real_bytes == 8));
+		// tree reused: the caller's positions are already in tree order
+		c->sel_warm_used = false;
+		if (prep_done == 0)
+		{
+			NBCO_TRY(launch_pack4(c, pos, p, n));
+			NBCO_HIP(hipMemsetAsync(c->counters.as<int>() + 110, 0, sizeof(int), st));
+		}
+		hipLaunchKernelGGL(kd_leaf_kernel, dim3(grid1d(nleaf)), dim3(kBlock), 0, st, tv, pos, n);   // (a rebuild's subtree kernel does it)
 	}
+	if (link) link->prep_done = 0;   // (a repeat of this build finds nothing done)
+	// centres and traversal records of all nodes (2 launches): that is all the traversal needs, so the multipole chain runs
+	// beside it on the second stream (kd_upward)
+	NBCO_TRY(launch_kd_centres(c, tv.center, tv.mult, L, tv.lbound, tv.rbound, tv.csz));
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// ---- upward pass of the tree that kd_build has left in c->kd: P2M + M2M (generated register-resident bodies of
+// k_farfield.hip) on the second stream
+static int kd_upward(nbco_ctx *c)
+{
+	const KdTreeDev &k = c->kd;
+	NBCO_TRY(c->fork_aux());
+	StreamScope on_aux(c, c->aux);
+	PhaseScope ph(c, NBCO_PH_P2M_M2M);
+	NBCO_TRY(launch_upward_gen(c, k.order, c->pos4.as<float4>(), k.center, k.mpole, k.mult, k.index, k.L, 0, k.real_bytes == 8));
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }
@@ -411,8 +412,7 @@ static int launch_let_guard(nbco_ctx *c, const uint64_t *keys, const int *total,
 	return NBCO_OK;
 }
 
-
-// ---- stage 2: traversal, lists, P2P, M2L, L2L, L2P on the tree `tv` over pos[0..n) --------------------------
+// ---- traversal, lists, P2P, M2L, L2L, L2P on the tree `tv` over pos[0..n) -----------------------------------
 // Only targets touching the domain `dm` are served; accelerations come out for the particles
 // [own0, own0 + own_n) (tree order, or scattered through `unsort` when opts.unsort is set).
 struct KdCounts
@@ -421,23 +421,12 @@ struct KdCounts
 	int sel_overflow = 0, react_overflow = 0;
 };
 
-// phase 0: everything; 1: up to and including the traversal (its flags on their way to the host); 2: the rest, for a tree on
-// which phase 1 has run.  `pre_far` (phase 0 / 2) is called on the second stream ahead of the far-field chain: the sharded
-// evaluation unpacks the multipoles there, which arrive after the traversal has started.
-static int kd_interact(nbco_ctx *c, const TreeView &tv, const float4 *pos, long long n, int mlt_max, const Dom dm, long long own0, long long own_n,
-                       const int *unsort, float *a, const float *param, KdCounts &out, int phase = 0, const std::function<int()> *pre_far = nullptr,
-                       const LetHave *let = nullptr)
+// capacity of the frontier and of the two pair lists, split into kTravK regions (regions fill unevenly: each gets twice its
+// share of list_factor * ntot pairs); kd_traverse and kd_fields both take their numbers from here
+static int kd_list_room(nbco_ctx *c, int ntot, long long &capR, long long &cap)
 {
-	const int P = c->o.fmm_order;
-	const int L = tv.L, ntot = tv.ntot, nleaf = 1 << L, beg = kd_beg(L);
-	const int offL = tl_off(P + 1);
-	out = KdCounts{};
-	const int self0 = dm.g << (L - dm.d), nself = 1 << (L - dm.d);   // the domain's own leaves
-	hipStream_t st = c->stream;
-
-	// capacity of the frontier and of the two pair lists, split into kTravK regions
-	// (regions fill unevenly: each gets twice its share of list_factor * ntot pairs)
-	const long long capR = 2 * (((long long)c->o.list_factor * c->list_growth * ntot + 4096 + kTravK - 1) / kTravK), cap = capR * kTravK;
+	capR = 2 * (((long long)c->o.list_factor * c->list_growth * ntot + 4096 + kTravK - 1) / kTravK);
+	cap = capR * kTravK;
 	NBCO_TRY(c->reserve(c->frontier_a, sizeof(int2) * (size_t)cap));
 	NBCO_TRY(c->reserve(c->frontier_b, sizeof(int2) * (size_t)cap));
 	// pairs [0, cap) and, behind them, the slot of either direction inside its target's range [cap, 2 cap)
@@ -445,52 +434,75 @@ static int kd_interact(nbco_ctx *c, const TreeView &tv, const float4 *pos, long 
 	NBCO_TRY(c->reserve(c->m2l_list, sizeof(int2) * 2 * (size_t)cap));
 	NBCO_TRY(c->reserve(c->counters, sizeof(int) * 128));
 	c->list_cap = cap;
+	return NBCO_OK;
+}
 
-	// ---- dual tree traversal ----------------------------------------------------------------------------
-	if (phase != 2)
+// dual tree traversal, up to and including the event behind which its counts and flags are in pinned host memory
+static int kd_traverse(nbco_ctx *c, const TreeView &tv, long long n, const Dom dm)
+{
+	const int L = tv.L, ntot = tv.ntot, nleaf = 1 << L;
+	const int self0 = dm.g << (L - dm.d), nself = 1 << (L - dm.d);   // the domain's own leaves
+	hipStream_t st = c->stream;
+	long long capR, cap;
+	NBCO_TRY(kd_list_room(c, ntot, capR, cap));
+	PhaseScope ph(c, NBCO_PH_TRAVERSE);
+	AdmTab tab;
+	for (int l = 0; l < 32; ++l)
 	{
-		PhaseScope ph(c, NBCO_PH_TRAVERSE);
-		AdmTab tab;
-		for (int l = 0; l < 32; ++l)
-		{
-			long long lo = l <= L ? (n >> l) : 0;
-			long long hi = l <= L ? ((n + (1LL << l) - 1) >> l) : 0;
-			tab.lo[l] = (int)lo;
-			const float e = 1.f / (float)(3 * P + 6);
-			tab.Mlo[l] = lo > 0 ? std::pow((float)lo / (float)n, e) : 0.f;   // fmm_cart3_kdtree.cuh:410
-			tab.Mhi[l] = hi > 0 ? std::pow((float)hi / (float)n, e) : 0.f;
-		}
-		int *ctr = c->counters.as<int>();
-		int2 *fa = c->frontier_a.as<int2>(), *fb = c->frontier_b.as<int2>();
-		// per-target entry counters / fill cursors of the two directed lists: [cnt_p2p | fill_p2p | cnt_m2l | fill_m2l]
-		const size_t np_ = (size_t)nleaf + 2, nm_ = (size_t)ntot + 2;
-		NBCO_TRY(c->reserve(c->list_cnt, sizeof(unsigned) * 2 * (np_ + nm_)));
-
-		unsigned *cnt_p2p = c->list_cnt.as<unsigned>(), *cnt_m2l = cnt_p2p + 2 * np_;
-		NBCO_TRY(c->reserve(c->trav_ctr, sizeof(int) * 1024));
-		static_assert(kTcInts <= 1024, "traversal counter block");
-		int *tctr = c->trav_ctr.as<int>();
-		NBCO_TRY(c->flags_begin());
-		hipLaunchKernelGGL(traverse_init_kernel, dim3(grid1d((long long)(2 * (np_ + nm_)) / 8 + 1, 256)), dim3(kBlock), 0, st, fa, ctr, 104, tctr,
-		                   c->list_cnt.as<unsigned>(), (long long)(2 * (np_ + nm_)), (long long)self0, (long long)(c->o.coll ? nself : 0));
-		// (counters[110] is the selection-build flag)
-		const int iters = L + NBCO_TRAV_EXTRA;   // every launch performs two traversal steps; traverse_finish_kernel checks that none is left
-		for (int it = 0; it < iters; ++it)
-		{
-			hipLaunchKernelGGL(traverse_kernel, dim3(1024), dim3(kBlock), 0, st, tv, tab, (const int2 *)fa, fb, c->p2p_list.as<int2>(),
-			                   c->m2l_list.as<int2>(), c->p2p_list.as<int2>() + cap, c->m2l_list.as<int2>() + cap, ctr, tctr, it, capR,
-			                   c->o.tree_radius, c->o.m2l_first, cnt_p2p, cnt_m2l, dm);
-			std::swap(fa, fb);
-		}
-		hipLaunchKernelGGL(traverse_finish_kernel, dim3(1), dim3(1024), 0, st, ctr, tctr, capR, c->list_cnt.as<unsigned>(), (long long)(2 * (np_ + nm_)),
-		                   cnt_p2p + self0, c->o.coll ? nself : 0, c->h_flags, iters, ++c->flags_seq);
-		NBCO_HIP(hipGetLastError());
-		// counts and flags are in pinned host memory once this event has passed; the host looks at them only after it has
-		// enqueued the rest of the evaluation (every later kernel takes its counts from the device), so the GPU never
-		// waits for a host round trip
-		NBCO_HIP(hipEventRecord(c->ev_flags, st));
+		long long lo = l <= L ? (n >> l) : 0;
+		long long hi = l <= L ? ((n + (1LL << l) - 1) >> l) : 0;
+		tab.lo[l] = (int)lo;
+		const float e = 1.f / (float)(3 * c->o.fmm_order + 6);
+		tab.Mlo[l] = lo > 0 ? std::pow((float)lo / (float)n, e) : 0.f;   // fmm_cart3_kdtree.cuh:410
+		tab.Mhi[l] = hi > 0 ? std::pow((float)hi / (float)n, e) : 0.f;
 	}
-	if (phase == 1) return NBCO_OK;
+	int *ctr = c->counters.as<int>();
+	int2 *fa = c->frontier_a.as<int2>(), *fb = c->frontier_b.as<int2>();
+	// per-target entry counters / fill cursors of the two directed lists: [cnt_p2p | fill_p2p | cnt_m2l | fill_m2l]
+	const size_t np_ = (size_t)nleaf + 2, nm_ = (size_t)ntot + 2;
+	NBCO_TRY(c->reserve(c->list_cnt, sizeof(unsigned) * 2 * (np_ + nm_)));
+	unsigned *cnt_p2p = c->list_cnt.as<unsigned>(), *cnt_m2l = cnt_p2p + 2 * np_;
+	NBCO_TRY(c->reserve(c->trav_ctr, sizeof(int) * 1024));
+	static_assert(kTcInts <= 1024, "traversal counter block");
+	int *tctr = c->trav_ctr.as<int>();
+	NBCO_TRY(c->flags_begin());
+	hipLaunchKernelGGL(traverse_init_kernel, dim3(grid1d((long long)(2 * (np_ + nm_)) / 8 + 1, 256)), dim3(kBlock), 0, st, fa, ctr, 104, tctr,
+	                   c->list_cnt.as<unsigned>(), (long long)(2 * (np_ + nm_)), (long long)self0, (long long)(c->o.coll ? nself : 0));
+	// (counters[110] is the selection-build flag)
+	const int iters = L + NBCO_TRAV_EXTRA;   // every launch performs two traversal steps; traverse_finish_kernel checks that none is left
+	for (int it = 0; it < iters; ++it)
+	{
+		hipLaunchKernelGGL(traverse_kernel, dim3(1024), dim3(kBlock), 0, st, tv, tab, (const int2 *)fa, fb, c->p2p_list.as<int2>(),
+		                   c->m2l_list.as<int2>(), c->p2p_list.as<int2>() + cap, c->m2l_list.as<int2>() + cap, ctr, tctr, it, capR,
+		                   c->o.tree_radius, c->o.m2l_first, cnt_p2p, cnt_m2l, dm);
+		std::swap(fa, fb);
+	}
+	hipLaunchKernelGGL(traverse_finish_kernel, dim3(1), dim3(1024), 0, st, ctr, tctr, capR, c->list_cnt.as<unsigned>(), (long long)(2 * (np_ + nm_)),
+	                   cnt_p2p + self0, c->o.coll ? nself : 0, c->h_flags, iters, ++c->flags_seq);
+	NBCO_HIP(hipGetLastError());
+	// counts and flags are in pinned host memory once this event has passed; the host looks at them only after it has
+	// enqueued the rest of the evaluation (every later kernel takes its counts from the device), so the GPU never
+	// waits for a host round trip
+	NBCO_HIP(hipEventRecord(c->ev_flags, st));
+	return NBCO_OK;
+}
+
+static int kd_no_pre_far() { return NBCO_OK; }
+
+// Everything behind the traversal of the same tree: directed lists, near field, far-field chain, L2P, and -- with all of that
+// queued -- the look at what the traversal reported.  `pre_far` is called on the second stream ahead of the far-field chain: the
+// sharded evaluation unpacks the multipoles there, which arrive after the traversal has started.
+template <class PreFar>
+static int kd_fields(nbco_ctx *c, const TreeView &tv, const float4 *pos, long long n, int mlt_max, const Dom dm, long long own0, long long own_n,
+                     const int *unsort, float *a, const float *param, KdCounts &out, PreFar pre_far, const LetHave *let = nullptr)
+{
+	const int P = c->o.fmm_order;
+	const int L = tv.L, ntot = tv.ntot, nleaf = 1 << L, beg = kd_beg(L);
+	const int offL = tl_off(P + 1);
+	out = KdCounts{};
+	const int self0 = dm.g << (L - dm.d), nself = 1 << (L - dm.d);   // the domain's own leaves
+	long long capR, cap;
+	NBCO_TRY(kd_list_room(c, ntot, capR, cap));
 	const int *p2p_pref = c->trav_ctr.as<int>() + kTcP2PPref, *m2l_pref = c->trav_ctr.as<int>() + kTcM2LPref;
 	const int shift = L + 1;
 	// capacities (the traversal never writes more than `cap` pairs) and launch-size hints from the previous evaluation
@@ -585,7 +597,7 @@ static int kd_interact(nbco_ctx *c, const TreeView &tv, const float4 *pos, long 
 		NBCO_TRY(c->fork_wait());
 		{
 			StreamScope on_aux(c, c->aux);
-			if (pre_far) NBCO_TRY((*pre_far)());
+			NBCO_TRY(pre_far());
 			unsigned *cm = c->list_cnt.as<unsigned>() + 2 * ((size_t)nleaf + 2);
 			NBCO_TRY(build_directed_list(c, c->m2l_list.as<int2>(), c->m2l_list.as<int2>() + cap, m2l_pref, capR, nm2l_hint, 0, 0, 0, ntot, shift, cm,
 			                             c->m2l_start.as<int>(), c->m2l_keys.as<uint64_t>(), c->m2l_keys_alt.as<uint64_t>(), c->scan_tmp_aux));
@@ -644,7 +656,7 @@ static int kd_interact(nbco_ctx *c, const TreeView &tv, const float4 *pos, long 
 }
 
 // positions in tree order; velocities follow (fmm_cart3_kdtree.cuh:1755-1760)
-static int kd_finish_order(nbco_ctx *c, float *p, long long n)
+static int kd_finish_order(nbco_ctx *c, float *p, long long n, KdStepLink *link)
 {
 	PhaseScope ph(c, NBCO_PH_FINISH);
 	hipStream_t st = c->stream;
@@ -663,7 +675,7 @@ static int kd_finish_order(nbco_ctx *c, float *p, long long n)
 	hipLaunchKernelGGL(reorder_state_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, (const float4 *)c->pos4.as<float4>(), (const int *)c->unsort.as<int>(),
 	                   (const float *)(p + 3 * n), p, c->tmp3.as<float>(), n, order_in, order_out);
 	if (order_out) { std::swap(c->order, c->order_alt); c->order_n = n; }
-	if (c->defer_v_copy) c->v_deferred = c->tmp3.as<float>();   // the caller's next pass over the velocities reads them from here
+	if (link && link->defer_v_copy) link->v_now = c->tmp3.as<float>();   // the caller's next pass over the velocities reads them from here
 	else NBCO_HIP(hipMemcpyAsync(p + 3 * n, c->tmp3.ptr, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, st));
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
@@ -705,33 +717,65 @@ int kd_energy_fmm(nbco_ctx *c, long long n_own, double *half_phi_sum)
 	return NBCO_OK;
 }
 
-namespace {
-} // namespace
-
-// the re-ordering an evaluation with defer_order set has left undone (nbco_integrate_steps, last step)
-int kd_finish_pending_order(nbco_ctx *c, float *p, long long n)
+// kd_fields has returned `rc`: twice the room for the lists (the caller's arrays are untouched), or reaction records sized from the
+// pair count just seen, and the same evaluation once more?  On the same rebuild schedule: a forced rebuild here would make the
+// trees of the following tree_steps - 1 evaluations depend on when a buffer happened to fill up.
+static bool kd_wants_room(nbco_ctx *c, int rc, const KdCounts &cnt, int ntot)
 {
-	if (!c->order_pending) return NBCO_OK;
-	c->order_pending = false;
-	return kd_finish_order(c, p, n);
+	if (rc == NBCO_ERR_CAPACITY) return c->grow_lists(ntot);
+	return rc == NBCO_OK && cnt.react_overflow && !cnt.sel_overflow;
 }
 
-// nbco_integrate_steps, between the force evaluation of one leapfrog step and that of the next (kd_turnaround_kernel).  v_in: where
-// the current velocities are (the caller's array or the scratch copy of the turnaround before); returns where they are now.
-int kd_turnaround(nbco_ctx *c, float *p, const float *v_in, const float **v_now, const float *param, float ks, float ds, bool elastic, long long n,
-                  const float *root6)
+// What is left to decide after kd_fields, in this order: an error is passed on; more room or a flagged build (repeated more
+// conservatively) mean the same evaluation again; a warm build that was not flagged is booked as a hit.
+static int kd_retry(nbco_ctx *c, int rc, const KdCounts &cnt, bool rebuild, int ntot, bool &again)
 {
-	const bool gather = c->order_pending;
-	c->order_pending = false;
+	again = true;
+	if (kd_wants_room(c, rc, cnt, ntot)) return NBCO_OK;
+	if (rc != NBCO_OK) return rc;
+	if (cnt.sel_overflow)
+		return c->demote_build() ? NBCO_OK : c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
+	if (rebuild && c->sel_warm_used) c->note_warm_ok();
+	again = false;
+	return NBCO_OK;
+}
+
+// books a finished evaluation of the tree `k` (n: particles of the tree the context keeps, c->kd)
+static void kd_commit(nbco_ctx *c, const KdTreeDev &k, long long n, const KdCounts &cnt, bool rebuilt)
+{
+	c->tree_valid = true;
+	c->tree_n = n;
+	c->tree_order = k.order;
+	c->eval_counter += 1;
+	nbco_kd_info &info = c->info;
+	info.L = k.L; info.ntot = k.ntot; info.order = k.order; info.mlt_max = k.mlt_max; info.n = k.n;
+	info.p2p_pairs = cnt.np2p; info.m2l_pairs = cnt.nm2l; info.rebuilt = rebuilt ? 1 : 0;
+	info.directed_p2p = -1;   // read back from the device counter on demand (nbco_kd_get_info)
+}
+
+// the re-ordering that an evaluation asked to defer it has left undone (nbco_integrate_steps, last step)
+int kd_finish_pending_order(nbco_ctx *c, float *p, long long n, KdStepLink *link)
+{
+	if (!link->order_pending) return NBCO_OK;
+	link->order_pending = false;
+	return kd_finish_order(c, p, n, link);
+}
+
+// nbco_integrate_steps, between the force evaluation of one leapfrog step and that of the next (kd_turnaround_kernel).  link->v_now:
+// where the velocities are (the caller's array or the scratch copy of the turnaround before), and where they are afterwards.
+int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6)
+{
+	const bool gather = link->order_pending;
+	link->order_pending = false;
 	float *x = p, *v = p + 3 * n, *a = p + 6 * n;
+	const float *v_in = link->v_now ? link->v_now : v;
 	const int L = c->kd.L;
-	// will the next evaluation rebuild?  (kd_build_upward's rule; the options cannot change inside nbco_integrate_steps)
+	// will the next evaluation rebuild?  (kd_build's rule; the options cannot change inside nbco_integrate_steps)
 	const bool next_rebuild = (c->eval_counter % c->o.tree_steps) == 0;
 	long long words_a = 0, words_b = 0;
 	if (next_rebuild)
 	{
-		int l0 = 0;
-		while (l0 < L && (n + (1LL << l0) - 1) / (1LL << l0) > kSubS) ++l0;
+		const int l0 = kd_top_levels(n, L);
 		if (!c->force_sort_build && l0 > 0) NBCO_TRY(kd_select_begin(c, l0, false, &words_a, &words_b));
 	}
 	float *v_out = v;
@@ -751,66 +795,36 @@ int kd_turnaround(nbco_ctx *c, float *p, const float *v_in, const float **v_now,
 	else hipLaunchKernelGGL(kd_turnaround_kernel<false>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS);
 #undef NBCO_TURN_ARGS
 	NBCO_HIP(hipGetLastError());
-	c->skip_prep = next_rebuild ? 1 : 2;
+	link->prep_done = next_rebuild ? 1 : 2;
 	c->order_n = -1;
 	c->last_eval.valid = false;   // the particles have moved (and pos4 may hold the next build's input): nbco_energy_fmm must follow an evaluation
-	*v_now = v_out;
+	link->v_now = v_out == v ? nullptr : v_out;
 	return NBCO_OK;
 }
 
-int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param)
+int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link)
 {
 	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_fmm_kdtree: n must be positive");
 	if (n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_kdtree: n too large for 32-bit tree indices");
-	const int P = c->o.fmm_order;
-	const int L = kd_levels(n, P, c->o.dens_inhom, c->o.tree_L);
-	bool rebuild = false;
-	NBCO_TRY(kd_build_upward(c, p, n, L, nullptr, rebuild));
-	KdCounts cnt;
+	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
 	const Dom whole{0, 0};
+	bool rebuild = false;
+	KdCounts cnt;
+	for (bool again = true; again;)
 	{
-		const int rc = kd_interact(c, view_of(c->kd), c->pos4.as<float4>(), n, c->kd.mlt_max, whole, 0, n, c->unsort.as<int>(), a, param, cnt);
-		if (rc == NBCO_ERR_CAPACITY && c->grow_lists(c->kd.ntot))
-		{
-			// the lists have outgrown their buffers (the caller's arrays are untouched): twice the room, same evaluation -- on the
-			// same rebuild schedule (a forced rebuild here would make the trees of the following tree_steps - 1 evaluations depend
-			// on when a buffer happened to fill up)
-			return fmm_kdtree_eval(c, p, a, n, param);
-		}
-		if (rc != NBCO_OK) return rc;
+		NBCO_TRY(kd_build(c, p, n, L, KdRoot{}, rebuild, link));
+		NBCO_TRY(kd_upward(c));
+		const TreeView tv = view_of(c->kd);
+		int rc = kd_traverse(c, tv, n, whole);
+		if (rc == NBCO_OK) rc = kd_fields(c, tv, c->pos4.as<float4>(), n, c->kd.mlt_max, whole, 0, n, c->unsort.as<int>(), a, param, cnt, kd_no_pre_far);
+		NBCO_TRY(kd_retry(c, rc, cnt, rebuild, c->kd.ntot, again));
 	}
-	if (cnt.react_overflow && !cnt.sel_overflow) return fmm_kdtree_eval(c, p, a, n, param);   // (same schedule, see above)
-	if (cnt.sel_overflow && c->sel_warm_used)
-	{
-		// the one-pass select missed a median (or what it left behind tripped the tie flag): the same evaluation with the cold
-		// two-pass select, nothing escalated
-		c->note_warm_miss();
-		c->tree_valid = false;
-		return fmm_kdtree_eval(c, p, a, n, param);
-	}
-	if (rebuild && c->sel_warm_used) c->note_warm_ok();
-	if (cnt.sel_overflow)
-	{
-		// next more conservative build: three radix passes, then the sorting build
-		if (!c->escalate_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
-		c->tree_valid = false;
-		return fmm_kdtree_eval(c, p, a, n, param);
-	}
-	c->order_pending = false;
 	if (!c->o.unsort && rebuild)
 	{
-		if (c->defer_order) c->order_pending = true;   // nbco_integrate_steps folds the re-ordering into its pass between two steps
-		else NBCO_TRY(kd_finish_order(c, p, n));
+		if (link && link->defer_order) link->order_pending = true;   // nbco_integrate_steps folds the re-ordering into its pass between two steps
+		else NBCO_TRY(kd_finish_order(c, p, n, link));
 	}
-
-	c->tree_valid = true;
-	c->tree_n = n;
-	c->tree_order = P;
-	c->eval_counter += 1;
-	nbco_kd_info &info = c->info;
-	info.L = L; info.ntot = c->kd.ntot; info.order = P; info.mlt_max = c->kd.mlt_max; info.n = n;
-	info.p2p_pairs = cnt.np2p; info.m2l_pairs = cnt.nm2l; info.rebuilt = rebuild ? 1 : 0;
-	info.directed_p2p = -1;   // read back from the device counter on demand (nbco_kd_get_info)
+	kd_commit(c, c->kd, n, cnt, rebuild);
 	return NBCO_OK;
 }
 

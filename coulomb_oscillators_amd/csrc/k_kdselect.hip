@@ -783,7 +783,7 @@ int kd_select_begin(nbco_ctx *c, int l0, bool zero, long long *words_a, long lon
 // l + 1.  `flag` (device int) is set when a node had more ties than the resolver handles.
 template <int BLOCK, int NP>
 static void select_level_launch(nbco_ctx *c, int l, long long n, const float4 *pos_in, const int *unsort_in, float4 *pos_out, int *unsort_out,
-                                float *lbound, float *rbound, int *splitdim, int *index, int *flag, int warm_drop)
+                                float *lbound, float *rbound, int *splitdim, int *index, int *flag, int warm_drop, const KdRoot &root)
 {
 	const int m = 1 << l;
 	// level l uses the slices [m - 1, 2m - 1) of the per-build arrays
@@ -805,7 +805,7 @@ static void select_level_launch(nbco_ctx *c, int l, long long n, const float4 *p
 		hipLaunchKernelGGL((sel_hist_warm_kernel<BLOCK, EPT>), dim3(wchunks), dim3(BLOCK), 0, st, pos_in, sd_l, hist, nodes, (const float *)lbound, (const float *)rbound,
 		                   n, l, warm_drop);
 		hipLaunchKernelGGL((sel_partition_kernel<BLOCK, 2, true, EPT>), dim3(wchunks), dim3(BLOCK), 0, st, pos_in, unsort_in, pos_out, unsort_out, sd_l, nodes, ties, n, l,
-		                   lbound, rbound, splitdim, index, flag, (const uint32_t *)hist, warm_drop, c->top_sd, c->top_root1);
+		                   lbound, rbound, splitdim, index, flag, (const uint32_t *)hist, warm_drop, root.top_sd, root.top_root1);
 		return;
 	}
 	hipLaunchKernelGGL((sel_hist_kernel<0, BLOCK, NP == 2>), dim3(gchunks), dim3(BLOCK), 0, st, pos_in, sd_l, hist, nodes, (const float *)lbound, (const float *)rbound, n, l);
@@ -813,11 +813,11 @@ static void select_level_launch(nbco_ctx *c, int l, long long n, const float4 *p
 	if (NP >= 3)
 		hipLaunchKernelGGL((sel_hist_kernel<2, BLOCK, false>), dim3(gchunks), dim3(BLOCK), 0, st, pos_in, sd_l, hist, nodes, (const float *)lbound, (const float *)rbound, n, l);
 	hipLaunchKernelGGL((sel_partition_kernel<BLOCK, NP>), dim3(gchunks), dim3(BLOCK), 0, st, pos_in, unsort_in, pos_out, unsort_out, sd_l, nodes, ties, n, l,
-	                   lbound, rbound, splitdim, index, flag, (const uint32_t *)hist, 10, c->top_sd, c->top_root1);
+	                   lbound, rbound, splitdim, index, flag, (const uint32_t *)hist, 10, root.top_sd, root.top_root1);
 }
 
 int kd_select_level(nbco_ctx *c, int l, long long n, const float4 *pos_in, const int *unsort_in, float4 *pos_out, int *unsort_out,
-                    float *lbound, float *rbound, int *splitdim, int *index, int *flag, bool warm)
+                    float *lbound, float *rbound, int *splitdim, int *index, int *flag, bool warm, const KdRoot &root)
 {
 	// Two radix passes over a bucket key that is linear across the node's box (lin_key) leave the pivot's bucket with about
 	// node size / 2^22 elements times the density contrast inside the box; the tie resolver orders them exactly as long as
@@ -836,7 +836,7 @@ int kd_select_level(nbco_ctx *c, int l, long long n, const float4 *pos_in, const
 		// (after misses: 2 bits coarser per miss, i.e. a window 4x as wide, down to 12 bits -- the resolver takes 64 candidates)
 		warm_drop = 32 - std::max(12, std::min(22, std::max(16, lg + 6)) - 2 * c->sel_warm_coarsen);
 	}
-#define NBCO_SEL_ARGS c, l, n, pos_in, unsort_in, pos_out, unsort_out, lbound, rbound, splitdim, index, flag, warm_drop
+#define NBCO_SEL_ARGS c, l, n, pos_in, unsort_in, pos_out, unsort_out, lbound, rbound, splitdim, index, flag, warm_drop, root
 	if (big)
 	{
 		if (np == 2) select_level_launch<kBlockBig, 2>(NBCO_SEL_ARGS);

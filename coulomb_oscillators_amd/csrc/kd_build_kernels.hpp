@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kPrepBlock) void kd_prep_kernel(const float *__rest
 		__hip_atomic_store(&state[c], c < 3 ? 0xFFFFFFFFu : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
 	__hip_atomic_store(&state[6], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	if (root6)   // a kd-domain keeps the union of its inherited box and the current bounds (see kd_build_upward)
+	if (root6)   // a kd-domain keeps the union of its inherited box and the current bounds (see kd_build)
 		for (int c = 0; c < 3; ++c) { b[c] = fminf(b[c], root6[c]); b[3 + c] = fmaxf(b[3 + c], root6[3 + c]); }
 	t.lbound[0] = b[0]; t.lbound[1] = b[1]; t.lbound[2] = b[2];
 	t.rbound[0] = b[3]; t.rbound[1] = b[4]; t.rbound[2] = b[5];

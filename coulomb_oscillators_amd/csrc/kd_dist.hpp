@@ -4,7 +4,7 @@
 // =====================================================================================================
 // Multi-GPU: kd-domain sharding.  GPU g of G = 2^d owns the subtree of node 2^d - 1 + g of
 // the GLOBAL balanced kd-tree: N / G particles, the global levels d .. L.  One force evaluation is
-//   local    build levels d .. L of the own subtree + P2M/M2M up to its root          (kd_dist_local)
+//   local    build levels d .. L of the own subtree + P2M/M2M up to its root          (kd_dist_local_build, _upward)
 //   exchange all-gather of {centre+size, multipoles} of every domain's nodes and of the
 //            tree-ordered positions -- done by the caller (RCCL), this library never communicates
 //   finish   assemble the global node arrays, M2M for levels d-1 .. 0, dual traversal pruned to pairs
@@ -132,7 +132,6 @@ int kd_dist_top_arrays(nbco_ctx *c, int ntop, float **lb, float **rb, int **sd, 
 	*lb = v.lbound; *rb = v.rbound; *sd = v.splitdim; *index = v.index;
 	return NBCO_OK;
 }
-// what nbco_dist_partition leaves behind besides the domain's state and the top boxes
 // between the force evaluation of one leapfrog step of a sharded run and that of the next: elastic term, both half kicks, drift and
 // the next local build's prologue in one pass over the domain's state (kd_turnaround_kernel; the state is in tree order already)
 int kd_dist_turnaround(nbco_ctx *c, float *buf_local, long long n_local, const float *param, float ks, float ds, bool elastic)
@@ -145,15 +144,15 @@ int kd_dist_turnaround(nbco_ctx *c, float *buf_local, long long n_local, const f
 	TopView top = top_view(c, ntop);
 	float *root6 = c->small.as<float>() + 80;
 	hipLaunchKernelGGL(dist_root6_kernel, dim3(1), dim3(64), 0, c->stream, (const float *)top.lbound, (const float *)top.rbound, (1 << d) - 1 + lay.rank, root6);
-	const float *v_now = nullptr;
-	c->order_pending = false;
-	NBCO_TRY(kd_turnaround(c, buf_local, buf_local + 3 * n_local, &v_now, param, ks, ds, elastic, n_local, root6));
+	KdStepLink link;   // (velocities in the caller's array, no re-ordering due: the state of a sharded run is in tree order)
+	NBCO_TRY(kd_turnaround(c, buf_local, param, ks, ds, elastic, n_local, &link, root6));
+	c->dist.prep_done = link.prep_done;   // for the next local build stage
 	return NBCO_OK;
 }
 
 int kd_dist_set_partitioned(nbco_ctx *c, long long n_global, int world, int rank)
 {
-	c->skip_prep = 0;   // (a prologue done by nbco_dist_turnaround belonged to the state before the cut)
+	c->dist.prep_done = 0;   // (a prologue done by nbco_dist_turnaround belonged to the state before the cut)
 	nbco_dist_layout lay;
 	NBCO_TRY(kd_dist_layout(c, n_global, world, rank, &lay));
 	c->dist.world = world; c->dist.rank = rank; c->dist.d = lay.d; c->dist.n_global = n_global; c->dist.n_local = lay.n_local; c->dist.L = lay.L;
@@ -218,91 +217,84 @@ int kd_dist_partition(nbco_ctx *c, const float *state_all, long long n_global, i
 	c->dist.world = world; c->dist.rank = rank; c->dist.d = d; c->dist.n_global = n_global; c->dist.n_local = nl; c->dist.L = lay.L;
 	c->dist.partitioned = true;
 	c->tree_valid = false;
-	c->skip_prep = 0;
+	c->dist.prep_done = 0;
 	return NBCO_OK;
 }
 
-// stage 1 (pos_send != null): subtree build, tree-ordered positions into pos_send; stage 2 (nodes_send != null): upward
-// pass, node block into nodes_send.  Both pointers: the whole local stage.  The split lets the caller start the all-gather
-// of the positions while the multipoles are still being computed.
-// csz_send / mpole_send: the two halves of the node block on their own (the traversal records are known after the build,
-// ahead of the multipoles)
-// let_stage (LET exchange, nothing but the traversal records is copied out): 1 = build, 2 = upward pass
-int kd_dist_local(nbco_ctx *c, float *buf_local, long long n_local, void *nodes_send, void *pos_send, void *csz_send, void *mpole_send, int let_stage)
+// the state a local stage needs: a partition of this size, made under the options that hold now
+static int dist_local_layout(nbco_ctx *c, long long n_local, nbco_dist_layout &lay)
 {
 	if (!c->dist.partitioned || n_local != c->dist.n_local)
 		return c->fail(NBCO_ERR_ARG, "nbco_dist_local: call nbco_dist_partition first (and pass its local particle count)");
 	if (c->o.unsort) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_dist: opts.unsort is not available with kd-domain sharding");
-	nbco_dist_layout lay;
 	NBCO_TRY(kd_dist_layout(c, c->dist.n_global, c->dist.world, c->dist.rank, &lay));
 	if (lay.L != c->dist.L) return c->fail(NBCO_ERR_ARG, "nbco_dist_local: options changed since nbco_dist_partition");
+	return NBCO_OK;
+}
+
+// Build stage: the own subtree; tree-ordered positions into pos_send and traversal records into csz_send, where given: the caller
+// can start their all-gathers while the multipoles are still being computed (upward stage).  let: the LET exchange follows.
+int kd_dist_local_build(nbco_ctx *c, float *buf_local, long long n_local, void *pos_send, void *csz_send, bool let)
+{
+	nbco_dist_layout lay;
+	NBCO_TRY(dist_local_layout(c, n_local, lay));
 	const int d = lay.d, ntop = (1 << (d + 1)) - 1;
 	hipStream_t st = c->stream;
 	bool rebuild = c->dist.rebuilt;
-	if (pos_send || let_stage == 1)
+	TopView top = top_view(c, ntop);
+	float *root6 = c->small.as<float>() + 80;
+	hipLaunchKernelGGL(dist_root6_kernel, dim3(1), dim3(64), 0, st, (const float *)top.lbound, (const float *)top.rbound, (1 << d) - 1 + lay.rank, root6);
+	if (let && c->dist.let_selected)
 	{
-		TopView top = top_view(c, ntop);
-		float *root6 = c->small.as<float>() + 80;
-		hipLaunchKernelGGL(dist_root6_kernel, dim3(1), dim3(64), 0, st, (const float *)top.lbound, (const float *)top.rbound, (1 << d) - 1 + lay.rank, root6);
-		if (let_stage == 1 && c->dist.let_selected)
-		{
-			// called again after a round in which some rank's build was flagged (the flags travel with the LET counts, so the LET
-			// path needs no host round trip behind the build): repeat this rank's build more conservatively if it was the one
-			NBCO_TRY(c->wait_flags());
-			if (c->h_flags[3] != 0)
-			{
-				if (c->sel_warm_used) c->note_warm_miss();
-				else if (!c->escalate_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
-				c->tree_valid = false;
-			}
-			c->dist.let_selected = c->dist.let_packed = c->dist.traversed = c->dist.local_done = false;
-		}
-		// the stable-sort chain's tie-breaking keys reach back to the GLOBAL root: the build takes the split axes above the domain
-		// root from the top tree (found at N = 2^24, where pivots with equal split coordinates are common: without them 531 leaves of
-		// one domain held other particles than the single-GPU tree's, `tests/test_gpu_dist.py::test_config_four_...`)
-		struct TopAxes
-		{
-			nbco_ctx *c;
-			TopAxes(nbco_ctx *c_, const int *sd, int root1) : c(c_) { c->top_sd = sd; c->top_root1 = root1; }
-			~TopAxes() { c->top_sd = nullptr; c->top_root1 = 1; }
-		} top_axes(c, d > 0 ? top.splitdim : nullptr, (1 << d) + lay.rank);
-		NBCO_TRY(kd_build_upward(c, buf_local, n_local, lay.L_local, root6, rebuild, 1));
-		while (rebuild && !c->force_sort_build && let_stage != 1)
-		{
-			// A tie overflow of the selection build has to be caught BEFORE the exchange (the other domains are
-			// about to consume these positions and nodes); the retry with a more conservative build is purely local.
-			int flag = 0;
-			NBCO_HIP(hipMemcpyAsync(&flag, c->counters.as<int>() + 110, sizeof(int), hipMemcpyDeviceToHost, st));
-			NBCO_HIP(hipStreamSynchronize(st));
-			if (!flag) { if (c->sel_warm_used) c->note_warm_ok(); break; }
-			// (a flagged build that ran the warm select is repeated cold first, nothing escalated)
-			if (c->sel_warm_used) c->note_warm_miss();
-			else c->escalate_build();
-			c->tree_valid = false;
-			NBCO_TRY(kd_build_upward(c, buf_local, n_local, lay.L_local, root6, rebuild, 1));
-		}
-		c->dist.rebuilt = rebuild;
-		if (pos_send) NBCO_HIP(hipMemcpyAsync(pos_send, c->pos4.ptr, sizeof(float4) * (size_t)n_local, hipMemcpyDeviceToDevice, st));
-		if (csz_send) NBCO_HIP(hipMemcpyAsync(csz_send, c->kd.csz, sizeof(float4) * (size_t)lay.ntot_local, hipMemcpyDeviceToDevice, st));
-		c->dist.build_done = true;
+		// called again after a round in which some rank's build was flagged (the flags travel with the LET counts, so the LET
+		// path needs no host round trip behind the build): repeat this rank's build more conservatively if it was the one
+		NBCO_TRY(c->wait_flags());
+		if (c->h_flags[3] != 0 && !c->demote_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
+		c->dist.let_selected = c->dist.let_packed = c->dist.traversed = c->dist.local_done = false;
 	}
-	if (nodes_send || mpole_send || let_stage == 2)
+	// the stable-sort chain's tie-breaking keys reach back to the GLOBAL root: the build takes the split axes above the domain
+	// root from the top tree (found at N = 2^24, where pivots with equal split coordinates are common: without them 531 leaves of
+	// one domain held other particles than the single-GPU tree's, `tests/test_gpu_dist.py::test_config_four_...`)
+	const KdRoot root{root6, d > 0 ? top.splitdim : nullptr, (1 << d) + lay.rank};
+	KdStepLink link;
+	std::swap(link.prep_done, c->dist.prep_done);   // nbco_dist_turnaround's mark: this is the build it was made for
+	NBCO_TRY(kd_build(c, buf_local, n_local, lay.L_local, root, rebuild, &link));
+	while (rebuild && !c->force_sort_build && !let)
 	{
-		if (!c->dist.build_done) return c->fail(NBCO_ERR_ARG, "nbco_dist_local_upward: the build stage has not run");
-		c->dist.build_done = false;
-		NBCO_TRY(kd_build_upward(c, buf_local, n_local, lay.L_local, nullptr, rebuild, 2));
-		c->dist.local_done = true;
-		if (let_stage == 2) return NBCO_OK;   // (nbco_dist_let_pack waits for the second stream)
-		NBCO_TRY(c->join_aux());   // the multipoles are about to leave the GPU
-		const int offM = sym_off(lay.order);
-		if (nodes_send)
-		{
-			NBCO_HIP(hipMemcpyAsync(nodes_send, c->kd.csz, sizeof(float4) * (size_t)lay.ntot_local, hipMemcpyDeviceToDevice, st));
-			mpole_send = (char *)nodes_send + sizeof(float4) * (size_t)lay.ntot_local;
-		}
-		NBCO_HIP(hipMemcpyAsync(mpole_send, c->kd.mpole, (size_t)c->kd.real_bytes * (size_t)lay.ntot_local * offM, hipMemcpyDeviceToDevice, st));
-		c->dist.local_done = true;
+		// A tie overflow of the selection build has to be caught BEFORE the exchange (the other domains are
+		// about to consume these positions and nodes); the retry with a more conservative build is purely local.
+		int flag = 0;
+		NBCO_HIP(hipMemcpyAsync(&flag, c->counters.as<int>() + 110, sizeof(int), hipMemcpyDeviceToHost, st));
+		NBCO_HIP(hipStreamSynchronize(st));
+		if (!flag) { if (c->sel_warm_used) c->note_warm_ok(); break; }
+		c->demote_build();   // (the loop ends with the sorting build)
+		NBCO_TRY(kd_build(c, buf_local, n_local, lay.L_local, root, rebuild, &link));
 	}
+	c->dist.rebuilt = rebuild;
+	if (pos_send) NBCO_HIP(hipMemcpyAsync(pos_send, c->pos4.ptr, sizeof(float4) * (size_t)n_local, hipMemcpyDeviceToDevice, st));
+	if (csz_send) NBCO_HIP(hipMemcpyAsync(csz_send, c->kd.csz, sizeof(float4) * (size_t)lay.ntot_local, hipMemcpyDeviceToDevice, st));
+	c->dist.build_done = true;
+	return NBCO_OK;
+}
+
+// Upward stage of the subtree the build stage has left.  The multipoles go into mpole_send, or -- one block per rank -- behind
+// the traversal records into nodes_send; let: nowhere (nbco_dist_let_pack takes what it needs, and waits for the second stream).
+int kd_dist_local_upward(nbco_ctx *c, long long n_local, void *nodes_send, void *mpole_send, bool let)
+{
+	nbco_dist_layout lay;
+	NBCO_TRY(dist_local_layout(c, n_local, lay));
+	if (!c->dist.build_done) return c->fail(NBCO_ERR_ARG, "nbco_dist_local_upward: the build stage has not run");
+	c->dist.build_done = false;
+	NBCO_TRY(kd_upward(c));
+	c->dist.local_done = true;
+	if (let) return NBCO_OK;
+	NBCO_TRY(c->join_aux());   // the multipoles are about to leave the GPU
+	if (nodes_send)
+	{
+		NBCO_HIP(hipMemcpyAsync(nodes_send, c->kd.csz, (size_t)lay.csz_bytes, hipMemcpyDeviceToDevice, c->stream));
+		mpole_send = (char *)nodes_send + lay.csz_bytes;
+	}
+	NBCO_HIP(hipMemcpyAsync(mpole_send, c->kd.mpole, (size_t)c->kd.real_bytes * (size_t)lay.ntot_local * sym_off(lay.order), hipMemcpyDeviceToDevice, c->stream));
 	return NBCO_OK;
 }
 

@@ -277,10 +277,7 @@ int kd_dist_let_select(nbco_ctx *c, const void *csz_all, long long *counts)
 	}
 	else NBCO_TRY(dist_geometry(c, lay, tv, (const char *)csz_all, (size_t)lay.csz_bytes));
 	NBCO_TRY(c->reserve(c->dist_pos, sizeof(float4) * (size_t)lay.n_global));
-	KdCounts cnt;
-	const Dom dm{d, lay.rank};
-	NBCO_TRY(kd_interact(c, tv, c->dist_pos.as<float4>(), lay.n_global, g.mlt_max, dm, (long long)lay.rank * lay.n_local, lay.n_local, c->unsort.as<int>(),
-	                     nullptr, nullptr, cnt, 1));
+	NBCO_TRY(kd_traverse(c, tv, lay.n_global, Dom{d, lay.rank}));
 	c->dist.pos_all = c->dist_pos.ptr;
 	c->dist.traversed = true;
 	LetView v;
@@ -438,8 +435,7 @@ int kd_dist_let_settle(nbco_ctx *c, int ok)
 	c->dist.let_ignore[(c->dist.let_epoch - 1) & 1] = true;
 	if (c->dist.let_flagged)
 	{
-		if (c->sel_warm_used) c->note_warm_miss();
-		else if (!c->escalate_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
+		if (!c->demote_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
 	}
 	else c->eval_counter -= 1;   // (the repeat takes the void attempt's place in the rebuild schedule of opts.tree_steps)
 	c->dist.let_flagged = false;
@@ -481,10 +477,7 @@ static int dist_finish_traverse(nbco_ctx *c, const char *csz_blocks, size_t csz_
 	NBCO_TRY(dist_global_tree(c, lay, g));
 	TreeView tv = view_of(g);
 	NBCO_TRY(dist_geometry(c, lay, tv, csz_blocks, csz_stride));
-	KdCounts cnt;
-	const Dom dm{lay.d, lay.rank};
-	NBCO_TRY(kd_interact(c, tv, (const float4 *)pos_all, lay.n_global, g.mlt_max, dm, (long long)lay.rank * lay.n_local, lay.n_local,
-	                     c->unsort.as<int>(), nullptr, nullptr, cnt, 1));
+	NBCO_TRY(kd_traverse(c, tv, lay.n_global, Dom{lay.d, lay.rank}));
 	c->dist.pos_all = pos_all;
 	c->dist.traversed = true;
 	return NBCO_OK;
@@ -529,7 +522,7 @@ static int dist_finish_rest(nbco_ctx *c, const char *mp_blocks, size_t mp_stride
 		NBCO_HIP(hipGetLastError());
 	}
 	// on the second stream, ahead of the M2L list: multipoles into the global arrays, M2M for the levels above the domains
-	const std::function<int()> pre_far = [&]() -> int {
+	const auto pre_far = [&]() -> int {
 		PhaseScope ph(c, NBCO_PH_P2M_M2M);
 		const bool f64 = g.real_bytes == 8;   // (dist_global_tree carved the global arrays under the same opts.far_fp64 as the local tree)
 		auto unpack_blocks = [&](const char *blocks, size_t stride, int nblocks, int r0) {
@@ -558,13 +551,15 @@ static int dist_finish_rest(nbco_ctx *c, const char *mp_blocks, size_t mp_stride
 	};
 	const LetHave *let = let_counts ? &have : nullptr;
 	KdCounts cnt;
-	int rc = kd_interact(c, tv, (const float4 *)c->dist.pos_all, lay.n_global, g.mlt_max, dm, (long long)lay.rank * nl, nl, c->unsort.as<int>(), a_local, param,
-	                     cnt, 2, &pre_far, let);
-	while ((rc == NBCO_ERR_CAPACITY && c->grow_lists(g.ntot)) || (rc == NBCO_OK && cnt.react_overflow && !cnt.sel_overflow))
-		// twice the room (or reaction records sized from the count just seen), traversal and the rest again (the global arrays,
-		// multipoles included, are in place; purely local)
-		rc = kd_interact(c, tv, (const float4 *)c->dist.pos_all, lay.n_global, g.mlt_max, dm, (long long)lay.rank * nl, nl, c->unsort.as<int>(), a_local, param,
-		                 cnt, 0, nullptr, let);
+	const float4 *pos_all = (const float4 *)c->dist.pos_all;
+	const long long own0 = (long long)lay.rank * nl;
+	int rc = kd_fields(c, tv, pos_all, lay.n_global, g.mlt_max, dm, own0, nl, c->unsort.as<int>(), a_local, param, cnt, pre_far, let);
+	while (kd_wants_room(c, rc, cnt, g.ntot))
+	{
+		// traversal and the rest again (the global arrays, multipoles included, are in place; purely local)
+		rc = kd_traverse(c, tv, lay.n_global, dm);
+		if (rc == NBCO_OK) rc = kd_fields(c, tv, pos_all, lay.n_global, g.mlt_max, dm, own0, nl, c->unsort.as<int>(), a_local, param, cnt, kd_no_pre_far, let);
+	}
 	if (rc != NBCO_OK) return rc;
 	if (cnt.sel_overflow && c->dist.let_capped)
 	{
@@ -575,15 +570,8 @@ static int dist_finish_rest(nbco_ctx *c, const char *mp_blocks, size_t mp_stride
 		return NBCO_OK;
 	}
 	if (cnt.sel_overflow) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_dist_finish: unresolved tie overflow of the selection build");
-	if (c->dist.rebuilt) NBCO_TRY(kd_finish_order(c, buf_local, nl));
-	c->tree_valid = true;
-	c->tree_n = nl;
-	c->tree_order = P;
-	c->eval_counter += 1;
-	nbco_kd_info &info = c->info;
-	info.L = L; info.ntot = g.ntot; info.order = P; info.mlt_max = g.mlt_max; info.n = lay.n_global;
-	info.p2p_pairs = cnt.np2p; info.m2l_pairs = cnt.nm2l; info.rebuilt = c->dist.rebuilt ? 1 : 0;
-	info.directed_p2p = -1;
+	if (c->dist.rebuilt) NBCO_TRY(kd_finish_order(c, buf_local, nl, nullptr));
+	kd_commit(c, g, nl, cnt, c->dist.rebuilt);
 	return NBCO_OK;
 }
 

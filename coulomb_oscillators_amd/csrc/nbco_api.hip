@@ -128,6 +128,26 @@ static int check_opts(nbco_ctx *c, const nbco_opts *o)
 	return NBCO_OK;
 }
 
+// F K(ds) at the end of a leapfrog step.  `run` is what comes before the kick -- the force evaluation, or the re-ordering the last
+// evaluation of a fused run has left.  The elastic term and the kick share one pass over x, v, a, and when `run` has just
+// re-ordered the particles, the kick reads the tree-ordered velocities straight from the scratch copy.
+template <class Run>
+static int closing_kick(nbco_ctx *c, KdStepLink &link, Run run, float *buf, long long n, const float *param, float ds, bool elastic)
+{
+	float *x = buf, *v = buf + 3 * n, *a = buf + 6 * n;
+	link.defer_v_copy = true;
+	link.v_now = nullptr;
+	const int rc = run();
+	const float *v_in = link.v_now ? link.v_now : v;
+	if (rc != NBCO_OK)
+	{
+		if (v_in != v) hipMemcpyAsync(v, v_in, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream);   // leave a whole state behind
+		return rc;
+	}
+	PhaseScope ph(c, NBCO_PH_AXPY);
+	return launch_finish_kick(c, x, v_in, v, a, param, ds, n, elastic);
+}
+
 extern "C" {
 
 int nbco_opts_default(nbco_opts *o)
@@ -191,23 +211,14 @@ int nbco_destroy(nbco_ctx *c)
 		        1e6 * c->host_call_s / c->host_calls, 1e6 * c->host_wait_s / c->host_calls);
 	if (!c) return NBCO_OK;
 	hipStreamSynchronize(c->stream);
-	DevBuf *bufs[] = {&c->pos4, &c->pos4_alt, &c->part, &c->small, &c->tmp3, &c->keys, &c->keys_alt, &c->idx, &c->idx_alt,
-	                  &c->unsort, &c->unsort_alt, &c->sort_tmp, &c->treebuf, &c->frontier_a, &c->frontier_b, &c->p2p_list,
-	                  &c->m2l_list, &c->counters, &c->p2p_keys, &c->p2p_keys_alt, &c->m2l_keys, &c->m2l_keys_alt,
-	                  &c->p2p_start, &c->m2l_start, &c->p2p_chunk_off, &c->p2p_chunks, &c->sel_hist, &c->sel_nodes, &c->sel_ties, &c->list_cnt,
-	                  &c->dist_top, &c->dist_tree, &c->oct_tree, &c->oct_groups, &c->scan_tmp_aux, &c->p2p_desc, &c->trav_ctr, &c->prep_state, &c->p2p_sec, &c->p2p_react, &c->order, &c->order_alt,
-	                  &c->let_sel, &c->let_have, &c->dist_pos, &c->tmp3b, &c->dpart_buf,
-	                  &c->f2d_tree, &c->f2d_keys, &c->f2d_tmp, &c->f2d_part};
 	if (c->aux && !c->aux_is_main) { hipStreamSynchronize(c->aux); hipStreamDestroy(c->aux); }
 	if (c->ev_fork) hipEventDestroy(c->ev_fork);
 	if (c->ev_join) hipEventDestroy(c->ev_join);
 	if (c->ev_flags) hipEventDestroy(c->ev_flags);
 	if (c->h_flags) hipHostFree(c->h_flags);
-	for (DevBuf *b : bufs)
-		if (b->ptr) hipFree(b->ptr);
 	for (auto &t : c->timers)
 		for (auto &ev : t.pending) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-	delete c;
+	delete c;   // frees every buffer the context owns (DevBuf), behind the drained streams
 	return NBCO_OK;
 }
 
@@ -352,43 +363,44 @@ int nbco_dist_partition(nbco_ctx *c, const float *state_all, long long n_global,
 int nbco_dist_local(nbco_ctx *c, float *buf_local, long long n_local, void *nodes_send, void *pos_send)
 {
 	if (!c || !buf_local || !nodes_send || !pos_send) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_local: null pointer") : NBCO_ERR_ARG;
-	NBCO_TRY(kd_dist_local(c, buf_local, n_local, nodes_send, pos_send));
+	NBCO_TRY(kd_dist_local_build(c, buf_local, n_local, pos_send, nullptr, false));
+	NBCO_TRY(kd_dist_local_upward(c, n_local, nodes_send, nullptr, false));
 	return maybe_sync(c);
 }
 int nbco_dist_local_build(nbco_ctx *c, float *buf_local, long long n_local, void *pos_send)
 {
 	if (!c || !buf_local || !pos_send) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_local_build: null pointer") : NBCO_ERR_ARG;
-	NBCO_TRY(kd_dist_local(c, buf_local, n_local, nullptr, pos_send));
+	NBCO_TRY(kd_dist_local_build(c, buf_local, n_local, pos_send, nullptr, false));
 	return maybe_sync(c);
 }
 int nbco_dist_local_upward(nbco_ctx *c, float *buf_local, long long n_local, void *nodes_send)
 {
 	if (!c || !buf_local || !nodes_send) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_local_upward: null pointer") : NBCO_ERR_ARG;
-	NBCO_TRY(kd_dist_local(c, buf_local, n_local, nodes_send, nullptr));
+	NBCO_TRY(kd_dist_local_upward(c, n_local, nodes_send, nullptr, false));
 	return maybe_sync(c);
 }
 int nbco_dist_local_geom(nbco_ctx *c, float *buf_local, long long n_local, void *pos_send, void *csz_send)
 {
 	if (!c || !buf_local || !pos_send || !csz_send) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_local_geom: null pointer") : NBCO_ERR_ARG;
-	NBCO_TRY(kd_dist_local(c, buf_local, n_local, nullptr, pos_send, csz_send, nullptr));
+	NBCO_TRY(kd_dist_local_build(c, buf_local, n_local, pos_send, csz_send, false));
 	return maybe_sync(c);
 }
 int nbco_dist_local_mpole(nbco_ctx *c, float *buf_local, long long n_local, void *mpole_send)
 {
 	if (!c || !buf_local || !mpole_send) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_local_mpole: null pointer") : NBCO_ERR_ARG;
-	NBCO_TRY(kd_dist_local(c, buf_local, n_local, nullptr, nullptr, nullptr, mpole_send));
+	NBCO_TRY(kd_dist_local_upward(c, n_local, nullptr, mpole_send, false));
 	return maybe_sync(c);
 }
 int nbco_dist_let_local_geom(nbco_ctx *c, float *buf_local, long long n_local, void *csz_send)
 {
 	if (!c || !buf_local || !csz_send) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_let_local_geom: null pointer") : NBCO_ERR_ARG;
-	NBCO_TRY(kd_dist_local(c, buf_local, n_local, nullptr, nullptr, csz_send, nullptr, 1));
+	NBCO_TRY(kd_dist_local_build(c, buf_local, n_local, nullptr, csz_send, true));
 	return maybe_sync(c);
 }
 int nbco_dist_let_local_mpole(nbco_ctx *c, float *buf_local, long long n_local)
 {
 	if (!c || !buf_local) return c ? c->fail(NBCO_ERR_ARG, "nbco_dist_let_local_mpole: null pointer") : NBCO_ERR_ARG;
-	return kd_dist_local(c, buf_local, n_local, nullptr, nullptr, nullptr, nullptr, 2);
+	return kd_dist_local_upward(c, n_local, nullptr, nullptr, true);
 }
 int nbco_dist_let_select(nbco_ctx *c, const void *csz_all, long long *counts_send)
 {
@@ -475,13 +487,14 @@ int nbco_dist_finish(nbco_ctx *c, const void *nodes_all, const void *pos_all, fl
 	return maybe_sync(c);
 }
 
-static int eval_kind(nbco_ctx *c, int kind, float *p, float *a, long long n, const float *param)
+// link: the leapfrog drivers' hand-off with the kd-tree evaluator (KdStepLink); the other evaluators take no part in it
+static int eval_kind(nbco_ctx *c, int kind, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr)
 {
 	switch (kind)
 	{
 	case NBCO_EVAL_DIRECT: return launch_direct(c, p, a, n, param, false);
 	case NBCO_EVAL_DIRECT_KAHAN: return launch_direct(c, p, a, n, param, true);
-	case NBCO_EVAL_FMM_KDTREE: return fmm_kdtree_eval(c, p, a, n, param);
+	case NBCO_EVAL_FMM_KDTREE: return fmm_kdtree_eval(c, p, a, n, param, link);
 	case NBCO_EVAL_FMM_TRACELESS: return fmm_oct_traceless_eval(c, p, a, n, param, false);
 	case NBCO_EVAL_FMM_SYMMETRIC: return fmm_oct_traceless_eval(c, p, a, n, param, true);
 	default: return c->fail(NBCO_ERR_ARG, "unknown evaluator kind");
@@ -555,23 +568,8 @@ int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, c
 			PhaseScope ph(c, NBCO_PH_AXPY);
 			NBCO_TRY(launch_kick_drift(c, x, v, a, (float)ds, (float)dt, n3));
 		}
-		// F K(ds): the elastic term and the kick share one pass over x, v, a -- and when the evaluator has just re-ordered
-		// the particles, the kick reads the tree-ordered velocities straight from the evaluator's scratch copy
-		c->defer_v_copy = true;
-		c->v_deferred = nullptr;
-		const int rc = eval_kind(c, kind, x, a, n, param);
-		c->defer_v_copy = false;
-		const float *v_in = c->v_deferred ? c->v_deferred : v;
-		c->v_deferred = nullptr;
-		if (rc != NBCO_OK)
-		{
-			if (v_in != v) hipMemcpyAsync(v, v_in, sizeof(float) * (size_t)n3, hipMemcpyDeviceToDevice, c->stream);   // leave a whole state behind
-			return rc;
-		}
-		{
-			PhaseScope ph(c, NBCO_PH_AXPY);
-			NBCO_TRY(launch_finish_kick(c, x, v_in, v, a, param, (float)ds, n, elastic != 0));
-		}
+		KdStepLink link;
+		NBCO_TRY(closing_kick(c, link, [&] { return eval_kind(c, kind, x, a, n, param, &link); }, buf, n, param, (float)ds, elastic != 0));
 		break;
 	}
 	case NBCO_INTEG_FORESTRUTH:
@@ -626,38 +624,26 @@ int nbco_integrate_steps(nbco_ctx *c, int scheme, int kind, float *buf, long lon
 		PhaseScope ph(c, NBCO_PH_AXPY);
 		NBCO_TRY(launch_kick_drift(c, x, v, a, ds, dtf, n3));
 	}
-	const float *v_now = v;
+	KdStepLink link;
 	auto home = [&]() {   // the velocities back into the caller's array
-		if (v_now != v) hipMemcpyAsync(v, v_now, sizeof(float) * (size_t)n3, hipMemcpyDeviceToDevice, c->stream);
-		v_now = v;
+		if (link.v_now) hipMemcpyAsync(v, link.v_now, sizeof(float) * (size_t)n3, hipMemcpyDeviceToDevice, c->stream);
+		link.v_now = nullptr;
 	};
-	c->defer_order = true;
+	link.defer_order = true;
 	for (int s = 0; s < steps; ++s)
 	{
-		int rc = eval_kind(c, kind, x, a, n, param);
-		if (rc == NBCO_OK && s + 1 < steps) rc = kd_turnaround(c, buf, v_now, &v_now, param, ds, dtf, elastic != 0, n);
+		int rc = eval_kind(c, kind, x, a, n, param, &link);
+		if (rc == NBCO_OK && s + 1 < steps) rc = kd_turnaround(c, buf, param, ds, dtf, elastic != 0, n, &link);
 		if (rc != NBCO_OK)
 		{
-			c->defer_order = false;
 			home();
-			kd_finish_pending_order(c, x, n);   // leave a whole state behind
+			kd_finish_pending_order(c, x, n, &link);   // leave a whole state behind
 			return rc;
 		}
 	}
-	c->defer_order = false;
 	home();
 	// tail of the last step, as in nbco_integrate: tree order, then a -= k o x, v += a ds
-	c->defer_v_copy = true;
-	c->v_deferred = nullptr;
-	const int rc = kd_finish_pending_order(c, x, n);
-	c->defer_v_copy = false;
-	const float *v_in = c->v_deferred ? c->v_deferred : v;
-	c->v_deferred = nullptr;
-	if (rc != NBCO_OK) return rc;
-	{
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		NBCO_TRY(launch_finish_kick(c, x, v_in, v, a, param, ds, n, elastic != 0));
-	}
+	NBCO_TRY(closing_kick(c, link, [&] { return kd_finish_pending_order(c, x, n, &link); }, buf, n, param, ds, elastic != 0));
 	return maybe_sync(c);
 }
 
@@ -766,12 +752,12 @@ int nbco_profile_reset(nbco_ctx *c)
 	for (auto &t : c->timers) { t.total_ms = 0; t.launches = 0; }
 	return NBCO_OK;
 }
-int nbco_profile_get(nbco_ctx *c, int phase, double *total_ms, long long *launches)
+int nbco_profile_get(nbco_ctx *c, int ph, double *total_ms, long long *launches)
 {
-	if (!c || phase < 0 || phase >= NBCO_PH_COUNT) return NBCO_ERR_ARG;
+	if (!c || ph < 0 || ph >= NBCO_PH_COUNT) return NBCO_ERR_ARG;
 	NBCO_TRY(drain_timers(c));
-	if (total_ms) *total_ms = c->timers[phase].total_ms;
-	if (launches) *launches = c->timers[phase].launches;
+	if (total_ms) *total_ms = c->timers[ph].total_ms;
+	if (launches) *launches = c->timers[ph].launches;
 	return NBCO_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/nbco.h"
 
@@ -63,10 +64,15 @@ int nbco_checked_collect_far(unsigned *out);
 
 // device buffer that only grows (the reference's evaluators keep their scratch in function-local
 // statics that grow monotonically, fmm_cart3_kdtree.cuh:1480-1498)
+// Owns its allocation: move-only (std::swap exchanges two buffers), freed with the context once nbco_destroy has drained the streams.
 struct DevBuf
 {
 	void *ptr = nullptr;
 	size_t bytes = 0;
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); return *this; }
+	~DevBuf() { if (ptr) hipFree(ptr); }
 	template <class T> T *as() const { return (T *)ptr; }
 };
 
@@ -106,6 +112,21 @@ struct OctTreeDev
 	uint32_t *keys = nullptr, *perm = nullptr;
 };
 
+// What a leapfrog driver (nbco_integrate, nbco_integrate_steps) and the kd-tree evaluations of one ABI call hand each other.  It
+// lives on the driver's stack and goes down as a pointer; every other caller of the evaluator passes nullptr.
+struct KdStepLink
+{
+	bool defer_order = false, defer_v_copy = false;   // in: leave the re-ordering after a rebuild to me / the tree-ordered velocities in scratch
+	int prep_done = 0;              // in, consumed by the build: its prologue (1) / the packing for a reused tree (2) is already done
+	bool order_pending = false;     // out: a re-ordering is due
+	const float *v_now = nullptr;   // out: where the velocities are now; nullptr: in the caller's array
+};
+
+// The root of a local build; the default is the global root.  root6 (device, {lbound, rbound}): the box a kd-domain inherits from
+// the global tree's top splits.  top_sd, top_root1: the split axes of the root's ancestors in the GLOBAL tree (the top tree of the
+// partition step, device array) and the root's 1-based heap number there.
+struct KdRoot { const float *root6 = nullptr; const int *top_sd = nullptr; int top_root1 = 1; };
+
 struct nbco_ctx
 {
 	nbco_opts o;
@@ -115,8 +136,6 @@ struct nbco_ctx
 	hipStream_t aux = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	bool aux_pending = false;
-	// the kd evaluator may leave the tree-ordered velocities in tmp3 for the caller's next pass over v (leapfrog's closing
-	// kick) instead of copying them back itself: requested with defer_v_copy, reported in v_deferred
 	int list_growth = 1;   // the lists hold list_growth * opts.list_factor * nodes pairs (doubled after an overflow, opts.list_grow)
 	bool grow_lists(int ntot)   // false: growth is off or exhausted
 	{
@@ -128,13 +147,6 @@ struct nbco_ctx
 		list_growth *= 2;
 		return true;
 	}
-	bool defer_v_copy = false;
-	// nbco_integrate_steps: leave the re-ordering of the caller's state after a rebuild to the pass between two steps
-	// (order_pending: such a re-ordering is due); skip_prep: that pass has already done the next build's prologue (1) or
-	// packed the positions for a reused tree (2)
-	bool defer_order = false, order_pending = false;
-	int skip_prep = 0;
-	const float *v_deferred = nullptr;
 	long long perm_primed_n = -1;   // particle count for which both permutation buffers were last filled with valid indices
 	double host_wait_s = 0, host_call_s = 0;   // diagnostics (NBCO_HOST_TIMING): time blocked on the flags event / inside nbco_integrate
 	long long host_calls = 0;
@@ -146,10 +158,6 @@ struct nbco_ctx
 	hipEvent_t ev_flags = nullptr;
 	long long hint_np2p = 0, hint_nm2l = 0;   // list sizes of the previous evaluation (launch-size hints only)
 	int flags_begin();
-	// local build of a kd-domain: the split axes of the domain root's ancestors in the GLOBAL tree (the top tree of the partition
-	// step, device array) and the root's 1-based heap number there; nullptr / 1: the tree's root is the global root
-	const int *top_sd = nullptr;
-	int top_root1 = 1;
 	int flags_seq = 0;   // sequence number of the traversal whose results h_flags[0..3] hold (h_flags[4], written last)
 	int wait_flags();    // until the traversal enqueued last has reported: spins on the pinned word, no interrupt-driven wake-up
 	DevBuf scan_tmp_aux;
@@ -204,6 +212,8 @@ struct nbco_ctx
 		// declared void (nbco_dist_let_settle(ok = 0)) is dropped unread
 		long long let_epoch = 0;
 		bool let_ignore[2] = {false, false};
+		// KdStepLink::prep_done of nbco_dist_turnaround, the one mark that outlives an ABI call: the next local build consumes it, a (re-)partition discards it
+		int prep_done = 0;
 	} dist;
 	// warm select (k_kdselect.hip): one histogram pass per level around the previous build's pivots.  used: this build ran it;
 	// a flagged build that used it is repeated cold before anything is escalated, three misses in a row switch it off
@@ -244,6 +254,14 @@ struct nbco_ctx
 		if (!sel_three_pass) { sel_three_pass = true; return true; }
 		if (!force_sort_build) { force_sort_build = true; return true; }
 		return false;
+	}
+	// a flagged build (tie overflow, or a window of the warm select that missed its median) is not the reference's tree: repeat it
+	// cold if the warm select ran -- nothing escalated -- and one step more conservatively otherwise; false when nothing is left
+	bool demote_build()
+	{
+		tree_valid = false;
+		if (sel_warm_used) note_warm_miss();
+		return sel_warm_used || escalate_build();
 	}
 	long long list_cap = 0;
 	// distributed re-partition in progress (k_dpart.hip)
@@ -330,7 +348,7 @@ int launch_mean_relerr(nbco_ctx *c, const float *x, const float *ref, long long 
 int launch_pow_sum(nbco_ctx *c, const float *x, int expo, long long n, double *out3_host);
 int launch_energy(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host);
 // k_fmm_kd.hip
-int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param);
+int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);
 int kd_copy_out(nbco_ctx *c, int which, void *host_dst, long long host_bytes);
 int kd_count_pairs(nbco_ctx *c, long long *out);
 int kd_energy_fmm(nbco_ctx *c, long long n_own, double *half_phi_sum);
@@ -345,9 +363,8 @@ int kd_dist_partition(nbco_ctx *c, const float *state_all, long long n_global, i
 int dpart_workspace(nbco_ctx *c, long long n_global, int world, long long *bytes);
 int dpart_begin(nbco_ctx *c, float *state_local, long long n_global, int world, int rank, void *work, long long work_bytes, nbco_dist_step *out);
 int dpart_next(nbco_ctx *c, nbco_dist_step *out);
-int kd_finish_pending_order(nbco_ctx *c, float *p, long long n);
-int kd_turnaround(nbco_ctx *c, float *p, const float *v_in, const float **v_now, const float *param, float ks, float ds, bool elastic, long long n,
-                  const float *root6 = nullptr);
+int kd_finish_pending_order(nbco_ctx *c, float *p, long long n, KdStepLink *link);
+int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6 = nullptr);
 int kd_dist_turnaround(nbco_ctx *c, float *buf_local, long long n_local, const float *param, float ks, float ds, bool elastic);
 int kd_dist_let_select(nbco_ctx *c, const void *csz_all, long long *counts);
 int kd_dist_let_pack(nbco_ctx *c, const long long *counts_all, void *pos_send, void *mpole_send);
@@ -356,15 +373,16 @@ int kd_dist_let_check(nbco_ctx *c);
 int kd_dist_let_pack_capped(nbco_ctx *c, const long long *caps_out, void *pos_send, void *mpole_send);
 int kd_dist_let_finish_capped(nbco_ctx *c, const long long *caps_in, const void *pos_recv, const void *mpole_recv, float *buf_local, float *a_local, const float *param);
 int kd_dist_let_settle(nbco_ctx *c, int ok);
-int kd_dist_local(nbco_ctx *c, float *buf_local, long long n_local, void *nodes_send, void *pos_send, void *csz_send = nullptr,
-                  void *mpole_send = nullptr, int let_stage = 0);
+// the two stages of a domain's local evaluation; let: the LET exchange follows
+int kd_dist_local_build(nbco_ctx *c, float *buf_local, long long n_local, void *pos_send, void *csz_send, bool let);
+int kd_dist_local_upward(nbco_ctx *c, long long n_local, void *nodes_send, void *mpole_send, bool let);
 int kd_dist_finish(nbco_ctx *c, const void *nodes_all, const void *pos_all, float *buf_local, float *a_local, const float *param);
 int kd_dist_finish_traverse(nbco_ctx *c, const void *csz_all, const void *pos_all);
 int kd_dist_finish_rest(nbco_ctx *c, const void *mpole_all, float *buf_local, float *a_local, const float *param);
 // k_kdselect.hip
 int kd_select_begin(nbco_ctx *c, int l0, bool zero = true, long long *words_a = nullptr, long long *words_b = nullptr);
 int kd_select_level(nbco_ctx *c, int l, long long n, const float4 *pos_in, const int *unsort_in, float4 *pos_out, int *unsort_out,
-                    float *lbound, float *rbound, int *splitdim, int *index, int *flag, bool warm = false);
+                    float *lbound, float *rbound, int *splitdim, int *index, int *flag, bool warm = false, const KdRoot &root = KdRoot{});
 // k_farfield.hip
 int launch_upward_gen(nbco_ctx *c, int P, const float4 *pos, float *center, void *mpole, int *mult, const int *index, int L, int write_geom, int f64 = 0);
 int launch_kd_centres(nbco_ctx *c, float *center, int *mult, int L, const float *lbound, const float *rbound, float4 *csz);

@@ -541,7 +541,7 @@ class Leapfrog:
 
 def test_option_toggles_rebuild_and_match_a_fresh_context(oracle32, oracle64):
     """Part C1, tree_steps = 1, unsort = 0, N = 65536, leapfrog steps with dt = 5e-4.  Each option of the `topo` rule of nbco_set_opts
-    and of the topo_change rule of kd_build_upward is toggled between two evaluations: fmm_order 6 -> 10 -> 6 -> 9 -> 3 (generated
+    and of the topo_change rule of kd_build is toggled between two evaluations: fmm_order 6 -> 10 -> 6 -> 9 -> 3 (generated
     bodies <-> the workgroup-per-node far field of farfield_wide.hpp), far_fp64, p2p_mutual, track_order, dens_inhom, tree_L,
     list_factor.  The evaluation after each toggle reports rebuilt == 1 and satisfies (F); (O) after the changes of order and of
     far_fp64."""
@@ -675,7 +675,7 @@ def test_options_outside_the_tree_build_change_inside_a_schedule(oracle32, chang
 
 
 def test_far_fp64_toggle_inside_a_schedule_keeps_the_schedule(oracle32, oracle64):
-    """Part C3.  far_fp64 changes the width of the expansions, so kd_build_upward throws the tree away (topo_change): the evaluation
+    """Part C3.  far_fp64 changes the width of the expansions, so kd_build throws the tree away (topo_change): the evaluation
     after the toggle rebuilds.  The schedule itself does not restart (include/nbco.h, far_fp64): the context keeps counting its
     evaluations and the next scheduled rebuild is at the next multiple of tree_steps -- toggled at evaluation 3 of a tree_steps = 8
     schedule, evaluations 4..7 reuse the tree of evaluation 3 and evaluation 8 rebuilds.  (F) and (O) at evaluation 3."""

@@ -84,3 +84,37 @@ def test_one_step_and_zero_steps(oracle32):
     e2.integrate(INTEG_LEAPFROG, EVAL_FMM_KDTREE, d2, n, prm, 5e-4)
     torch.cuda.synchronize()
     assert torch.equal(d, d2)
+
+
+@pytest.mark.parametrize("tree_steps", [1, 3])
+def test_refused_evaluation_inside_a_fused_run_leaves_the_context_sound(oracle32, tree_steps):
+    """an evaluation refused in the middle of nbco_integrate_steps (list overflow with list_factor = 1, list_grow = 0; a rebuild with
+    tree_steps = 1, a tree-reuse evaluation with 3) leaves nothing behind in the context: with the state put back and the lists
+    at their default size, the engine carries on bit for bit like a twin that was never refused anything"""
+    import torch
+    from coulomb_oscillators_amd import Engine, EngineError, EVAL_FMM_KDTREE, INTEG_LEAPFROG
+    n, p, dt = 65536, 6, 5e-4
+    live, twin = (Engine(fmm_order=p, unsort=0, tree_steps=tree_steps) for _ in range(2))
+    d, prm = _state(oracle32, n)
+    states = {live: d, twin: d.clone()}
+    for e, s in states.items():
+        e.compute_force(EVAL_FMM_KDTREE, s, n, prm)
+        e.integrate_steps(INTEG_LEAPFROG, EVAL_FMM_KDTREE, s, n, prm, dt, 3)
+    torch.cuda.synchronize()
+    saved = states[live].clone()
+    live.set(list_factor=1, list_grow=0)
+    with pytest.raises(EngineError, match="list capacity"):
+        live.integrate_steps(INTEG_LEAPFROG, EVAL_FMM_KDTREE, states[live], n, prm, dt, 4)
+    live.set(list_factor=48, list_grow=1)
+    torch.cuda.synchronize()
+    states[live].copy_(saved)
+    for e, s in states.items():
+        e.integrate_steps(INTEG_LEAPFROG, EVAL_FMM_KDTREE, s, n, prm, dt, 5)
+        for _ in range(2):
+            e.integrate(INTEG_LEAPFROG, EVAL_FMM_KDTREE, s, n, prm, dt)
+    torch.cuda.synchronize()
+    assert torch.isfinite(states[live]).all()
+    for part, name in enumerate(("positions", "velocities", "accelerations")):
+        assert torch.equal(states[live][part], states[twin][part]), name + " differ"
+    live.close()
+    twin.close()
