@@ -15,7 +15,7 @@
 // collective to run on which part of the caller's workspace before the next call (a small state machine, nbco_dist_step).
 #include "nbco_internal.hpp"
 #include "kd_common.hpp"
-#include <rocprim/rocprim.hpp>
+#include "host_util.hpp"
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -533,11 +533,7 @@ static int dpart_advance(nbco_ctx *c, nbco_dist_step *out)
 			NBCO_HIP(hipGetLastError());
 			const unsigned bits = (unsigned)std::max(d, 1);
 			rocprim::counting_iterator<uint32_t> iota(0u);
-			size_t bytes = 0;
-			NBCO_HIP(rocprim::radix_sort_pairs(nullptr, bytes, dest, dest_sorted, iota, order, (size_t)nl, 0u, bits, st));
-			NBCO_TRY(c->reserve(c->sort_tmp, bytes));
-			bytes = c->sort_tmp.bytes;
-			NBCO_HIP(rocprim::radix_sort_pairs(c->sort_tmp.ptr, bytes, dest, dest_sorted, iota, order, (size_t)nl, 0u, bits, st));
+			NBCO_TRY(sort_pairs(c, c->sort_tmp, dest, dest_sorted, iota, order, nl, 0u, bits));
 			hipLaunchKernelGGL(dp_send_kernel, dim3(256), dim3(kB), 0, st, (const uint32_t *)order, (const float *)s.state, (const float *)(s.state + 3 * nl), nl, sendbuf);
 		}
 		NBCO_HIP(hipGetLastError());

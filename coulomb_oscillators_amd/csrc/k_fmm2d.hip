@@ -17,7 +17,7 @@
 // launch for all levels, L-2 L2L, and the near field fused with L2P and the rescale.  No atomics anywhere: every sum has a fixed
 // order, so results are bit-reproducible.
 #include "nbco_internal.hpp"
-#include <rocprim/rocprim.hpp>
+#include "host_util.hpp"
 #include <algorithm>
 #include <cmath>
 #include <random>
@@ -29,7 +29,7 @@ constexpr int kNear = 64;      // one wave per target cell in the near-field ker
 constexpr int kRedBlocks = 512;
 constexpr int kMaxL2 = 15;     // 2L <= 30: keys stay below 2^30
 
-static int grid_for(long long n, int cap = 1 << 20) { return (int)std::max<long long>(1, std::min<long long>((n + kB - 1) / kB, cap)); }
+constexpr int kGridCap = 1 << 20;   // blocks of a grid-stride launch
 __host__ __device__ inline long long quad_beg(int l) { return ((1LL << (2 * l)) - 1) / 3; }
 
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -535,9 +535,39 @@ static int f2d_levels(const nbco_opts &o, long long n)
 	return std::min(std::max(L, 2), kMaxL2);
 }
 
-template <int P>
+// ---- the five kernels that are compiled per order: each launch function is the one place where its kernel's order is chosen ----
+static void f2d_launch_leaf(nbco_ctx *c, int P, const Quad &q, const double2 *x, int m, long long beg)
+{
+	with_order(P, [&](auto p) { hipLaunchKernelGGL((f2d_leaf_kernel<decltype(p)::value>), dim3((m + kB - 1) / kB), dim3(kB), 0, c->stream, q, x, m, beg); });
+}
+static void f2d_launch_m2m(nbco_ctx *c, int P, const Quad &q, int l)
+{
+	with_order(P, [&](auto p) { hipLaunchKernelGGL((f2d_m2m_kernel<decltype(p)::value>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, c->stream, q, l); });
+}
+static void f2d_launch_m2l(nbco_ctx *c, int P, const Quad &q, int L, int radius, double eps2)
+{
+	const long long nm2l = quad_beg(L + 1) - quad_beg(2);
+	with_order(P, [&](auto p) {
+		hipLaunchKernelGGL((f2d_m2l_kernel<decltype(p)::value>), dim3((unsigned)((nm2l + kB - 1) / kB)), dim3(kB), 0, c->stream, q, L, radius, eps2);
+	});
+}
+static void f2d_launch_l2l(nbco_ctx *c, int P, const Quad &q, int l)
+{
+	with_order(P, [&](auto p) { hipLaunchKernelGGL((f2d_l2l_kernel<decltype(p)::value>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, c->stream, q, l); });
+}
+static void f2d_launch_near(nbco_ctx *c, int P, bool coll, const Quad &q, const double2 *x, double2 *a, int L, int radius, double eps2, const double *param)
+{
+	const int near_grid = std::min(1 << (2 * L), 1 << 22);
+	with_order(P, [&](auto p) {
+		if (coll) hipLaunchKernelGGL((f2d_near_kernel<decltype(p)::value, true>), dim3(near_grid), dim3(kNear), 0, c->stream, q, x, a, L, radius, eps2, param);
+		else hipLaunchKernelGGL((f2d_near_kernel<decltype(p)::value, false>), dim3(near_grid), dim3(kNear), 0, c->stream, q, x, a, L, radius, eps2, param);
+	});
+}
+
+// one evaluation; f2d_fmm has checked the arguments and the order
 static int f2d_fmm_run(nbco_ctx *c, double *p, double *a, long long n, const double *param)
 {
+	const int P = c->o.fmm_order;
 	const int L = f2d_levels(c->o, n);
 	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_L must be 0 or 2..15");
 	const int radius = (int)c->o.tree_radius;
@@ -546,12 +576,9 @@ static int f2d_fmm_run(nbco_ctx *c, double *p, double *a, long long n, const dou
 	const long long ntot = quad_beg(L + 1);
 	hipStream_t st = c->stream;
 
-	// scratch: keys in / out, indices in / out | gather and sort temp | tree | reduction partials + scalars
+	// scratch: keys in / out, indices in / out | tree | reduction partials + scalars (the gather and sort temp grows at the sort)
 	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
 	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
-	size_t sort_bytes = 0;
-	NBCO_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_in, keys, idx_in, idx, (size_t)n, 0u, (unsigned)(2 * L), st));
-	NBCO_TRY(c->reserve(c->f2d_tmp, std::max(sort_bytes, sizeof(double) * 4 * (size_t)n)));
 	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1) + P) + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
 	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
 	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
@@ -564,29 +591,22 @@ static int f2d_fmm_run(nbco_ctx *c, double *p, double *a, long long n, const dou
 	double *part = c->f2d_part.as<double>(), *scal = part + 4 * kRedBlocks;
 
 	double2 *x = (double2 *)p, *v = x + n;
-	const int nbr = std::min(kRedBlocks, grid_for(n));
+	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
 	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, (const double2 *)x, n, part);
 	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
-	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_for(n)), dim3(kB), 0, st, (const double2 *)x, n, (const double *)scal, side, keys_in, idx_in);
-	sort_bytes = c->f2d_tmp.bytes;
-	NBCO_HIP(rocprim::radix_sort_pairs(c->f2d_tmp.ptr, sort_bytes, keys_in, keys, idx_in, idx, (size_t)n, 0u, (unsigned)(2 * L), st));
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, (const double2 *)x, n, (const double *)scal, side, keys_in, idx_in);
+	// f2d_tmp is the sort's scratch and then the gather's destination: sized for the larger of the two
+	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * L), sizeof(double) * 4 * (size_t)n));
 	double2 *tmp = c->f2d_tmp.as<double2>();
-	hipLaunchKernelGGL(f2d_gather_kernel, dim3(grid_for(n)), dim3(kB), 0, st, (const double2 *)x, (const double2 *)v, (const uint32_t *)idx, tmp, n);
+	hipLaunchKernelGGL(f2d_gather_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, (const double2 *)x, (const double2 *)v, (const uint32_t *)idx, tmp, n);
 	NBCO_HIP(hipMemcpyAsync(p, tmp, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
 	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
 
-	hipLaunchKernelGGL((f2d_leaf_kernel<P>), dim3((m + kB - 1) / kB), dim3(kB), 0, st, q, (const double2 *)x, m, quad_beg(L));
-	for (int l = L - 1; l >= 2; --l)
-		hipLaunchKernelGGL((f2d_m2m_kernel<P>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, st, q, l);
-	const long long nm2l = quad_beg(L + 1) - quad_beg(2);
-	hipLaunchKernelGGL((f2d_m2l_kernel<P>), dim3((unsigned)((nm2l + kB - 1) / kB)), dim3(kB), 0, st, q, L, radius, eps2);
-	for (int l = 3; l <= L; ++l)
-		hipLaunchKernelGGL((f2d_l2l_kernel<P>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, st, q, l);
-	const int near_grid = std::min(m, 1 << 22);
-	if (c->o.coll)
-		hipLaunchKernelGGL((f2d_near_kernel<P, true>), dim3(near_grid), dim3(kNear), 0, st, q, (const double2 *)x, (double2 *)a, L, radius, eps2, param);
-	else
-		hipLaunchKernelGGL((f2d_near_kernel<P, false>), dim3(near_grid), dim3(kNear), 0, st, q, (const double2 *)x, (double2 *)a, L, radius, eps2, param);
+	f2d_launch_leaf(c, P, q, x, m, quad_beg(L));
+	for (int l = L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
+	f2d_launch_m2l(c, P, q, L, radius, eps2);
+	for (int l = 3; l <= L; ++l) f2d_launch_l2l(c, P, q, l);
+	f2d_launch_near(c, P, c->o.coll != 0, q, x, (double2 *)a, L, radius, eps2, param);
 	return f2d_done(c);
 }
 
@@ -604,25 +624,14 @@ static int f2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double 
 	if (!c) return NBCO_ERR_ARG;
 	if (!p || !a || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: bad arguments");
 	NBCO_TRY(f2d_fmm_check(c, n));
-	switch (c->o.fmm_order)
-	{
-	case 1: return f2d_fmm_run<1>(c, p, a, n, param);
-	case 2: return f2d_fmm_run<2>(c, p, a, n, param);
-	case 3: return f2d_fmm_run<3>(c, p, a, n, param);
-	case 4: return f2d_fmm_run<4>(c, p, a, n, param);
-	case 5: return f2d_fmm_run<5>(c, p, a, n, param);
-	case 6: return f2d_fmm_run<6>(c, p, a, n, param);
-	case 7: return f2d_fmm_run<7>(c, p, a, n, param);
-	case 8: return f2d_fmm_run<8>(c, p, a, n, param);
-	case 9: return f2d_fmm_run<9>(c, p, a, n, param);
-	case 10: return f2d_fmm_run<10>(c, p, a, n, param);
-	default: return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
-	}
+	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
+		return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
+	return f2d_fmm_run(c, p, a, n, param);
 }
 
 static int f2d_step(nbco_ctx *c, double *b, const double *a, long double ds, long long n)
 {
-	hipLaunchKernelGGL(f2d_axpy_kernel, dim3(grid_for(2 * n)), dim3(kB), 0, c->stream, b, a, (double)ds, 2 * n);
+	hipLaunchKernelGGL(f2d_axpy_kernel, dim3(grid_blocks(2 * n, kB, kGridCap)), dim3(kB), 0, c->stream, b, a, (double)ds, 2 * n);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }
@@ -644,7 +653,7 @@ static int f2d_eval(nbco_ctx *c, int kind, double *buf, long long n, const doubl
 	if (rc != NBCO_OK) return rc;
 	if (elastic)   // main.cu:85-89: a -= k o x, k = param + 2
 	{
-		hipLaunchKernelGGL(f2d_elastic_kernel, dim3(grid_for(n)), dim3(kB), 0, c->stream, (const double2 *)buf, (double2 *)a, n, param + 2);
+		hipLaunchKernelGGL(f2d_elastic_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, c->stream, (const double2 *)buf, (double2 *)a, n, param + 2);
 		NBCO_HIP(hipGetLastError());
 	}
 	return NBCO_OK;
@@ -755,7 +764,7 @@ int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long lo
 	if (!x || !ref || !out_host || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_mean_relerr: bad arguments");
 	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
 	double *part = c->f2d_part.as<double>();
-	const int nb = std::min(kRedBlocks, grid_for(n));
+	const int nb = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
 	hipLaunchKernelGGL(f2d_relerr_kernel, dim3(nb), dim3(kB), 0, c->stream, (const double2 *)x, (const double2 *)ref, n, part);
 	hipLaunchKernelGGL(f2d_relerr_final_kernel, dim3(1), dim3(kB), 0, c->stream, (const double *)part, nb, n, part + 4 * kRedBlocks);
 	NBCO_HIP(hipGetLastError());

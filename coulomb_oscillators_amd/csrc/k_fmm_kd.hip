@@ -31,7 +31,7 @@
 #include "nbco_internal.hpp"
 #include "k_p2p.hpp"
 #include "kd_common.hpp"
-#include <rocprim/rocprim.hpp>
+#include "host_util.hpp"
 #include <chrono>
 #include <cmath>
 #include <algorithm>
@@ -107,30 +107,6 @@ static TreeView view_of(const KdTreeDev &k)
 	return t;
 }
 
-static int sort_pairs_u64(nbco_ctx *c, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, long long n, int end_bit)
-{
-	size_t bytes = 0;
-	NBCO_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, 0u, (unsigned)end_bit, c->stream));
-	NBCO_TRY(c->reserve(c->sort_tmp, bytes));
-	bytes = c->sort_tmp.bytes;
-	NBCO_HIP(rocprim::radix_sort_pairs(c->sort_tmp.ptr, bytes, kin, kout, vin, vout, (size_t)n, 0u, (unsigned)end_bit, c->stream));
-	return NBCO_OK;
-}
-
-// directed, per-target sorted list of `pairs` (+ one self entry for each of the targets [self0, self0 + nself)) into
-// keys_out; start[0..T].  cnt[0..T) holds the per-target pair-entry counts accumulated by the traversal, fill[0..T) is zero.
-static int exclusive_scan_ints(nbco_ctx *c, int *in, int *out, size_t count, DevBuf &tmp)
-{
-	// (a one-workgroup scan in a single launch was tried for these 32K..64K-element arrays: 3x slower than rocPRIM's two launches)
-	hipStream_t st = c->stream;
-	size_t bytes = 0;
-	NBCO_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int>(), st));
-	NBCO_TRY(c->reserve(tmp, bytes));
-	bytes = tmp.bytes;
-	NBCO_HIP(rocprim::exclusive_scan(tmp.ptr, bytes, in, out, 0, count, rocprim::plus<int>(), st));
-	return NBCO_OK;
-}
-
 // One scan for two prefix sums of the P2P list: entries per target (low word -> start[]) and chunks per target (high
 // word -> chunk_off[]); the chunk count follows from the entry count, so the work-unit table no longer waits for the sort.
 struct PackCounts
@@ -158,18 +134,9 @@ struct SplitIter
 	__host__ __device__ SplitIter &operator++() { ++s; ++o; return *this; }
 	__host__ __device__ difference_type operator-(const SplitIter &b) const { return s - b.s; }
 };
-static int exclusive_scan_counts_and_chunks(nbco_ctx *c, const unsigned *cnt, int *start, int *chunk_off, size_t count, DevBuf &tmp)
-{
-	hipStream_t st = c->stream;
-	auto in = rocprim::make_transform_iterator(cnt, PackCounts{});
-	size_t bytes = 0;
-	NBCO_HIP(rocprim::exclusive_scan(nullptr, bytes, in, SplitIter{start, chunk_off}, (uint64_t)0, count, rocprim::plus<uint64_t>(), st));
-	NBCO_TRY(c->reserve(tmp, bytes));
-	bytes = tmp.bytes;
-	NBCO_HIP(rocprim::exclusive_scan(tmp.ptr, bytes, in, SplitIter{start, chunk_off}, (uint64_t)0, count, rocprim::plus<uint64_t>(), st));
-	return NBCO_OK;
-}
-
+// directed, per-target sorted list of `pairs` (+ one self entry for each of the targets [self0, self0 + nself)) into
+// keys_out; start[0..T].  cnt[0..T) holds the per-target pair-entry counts accumulated by the traversal, fill[0..T) is zero.
+// (a one-workgroup scan in a single launch was tried for these 32K..64K-element arrays: 3x slower than rocPRIM's two launches)
 static int build_directed_list(nbco_ctx *c, const int2 *pairs, const int2 *ranks, const int *pref_dev, long long capR, long long npairs_hint, int sub,
                                int self0, int nself, int ntargets, int shift, unsigned *cnt, int *start, uint64_t *keys_tmp, uint64_t *keys_out,
                                DevBuf &scan_tmp, const int *leaf_index = nullptr, const int *leaf_mult = nullptr, int2 *desc = nullptr,
@@ -179,10 +146,11 @@ static int build_directed_list(nbco_ctx *c, const int2 *pairs, const int2 *ranks
 	if (desc)
 	{
 		// P2P list: entry offsets and chunk offsets from one scan (the work-unit table is written by the fill kernel)
-		NBCO_TRY(exclusive_scan_counts_and_chunks(c, cnt, start, chunk_off, (size_t)(ntargets + 1), scan_tmp));
+		NBCO_TRY(exclusive_scan(c, scan_tmp, rocprim::make_transform_iterator((const unsigned *)cnt, PackCounts{}), SplitIter{start, chunk_off}, (uint64_t)0,
+		                        (size_t)(ntargets + 1)));
 	}
 	else
-		NBCO_TRY(exclusive_scan_ints(c, (int *)cnt, start, (size_t)(ntargets + 1), scan_tmp));
+		NBCO_TRY(exclusive_scan(c, scan_tmp, (int *)cnt, start, 0, (size_t)(ntargets + 1)));
 	hipLaunchKernelGGL(list_fill_kernel, dim3(grid1d(npairs_hint + nself)), dim3(kBlock), 0, st, pairs, ranks, pref_dev, capR, sub, self0, nself, shift,
 	                   (const int *)start, keys_tmp, (const int *)chunk_off, ntargets, leaf_index, leaf_mult,
 	                   (desc && !mutual) ? chunks : (int4 *)nullptr, mutual ? 1 : 0);
@@ -251,7 +219,8 @@ static int kd_build_top(nbco_ctx *c, const TreeView &tv, float4 *&pos, float4 *&
 			if (l > 0) hipLaunchKernelGGL(kd_box_kernel, dim3(grid1d(kd_cnt(l))), dim3(kBlock), 0, st, tv, pos, n, l);
 			hipLaunchKernelGGL(kd_keys_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, pos, tv.splitdim + kd_beg(l), n, l,
 			                   c->keys.as<uint64_t>(), c->idx.as<uint32_t>());
-			NBCO_TRY(sort_pairs_u64(c, c->keys.as<uint64_t>(), c->keys_alt.as<uint64_t>(), c->idx.as<uint32_t>(), c->idx_alt.as<uint32_t>(), n, 32 + l));
+			NBCO_TRY(sort_pairs(c, c->sort_tmp, c->keys.as<uint64_t>(), c->keys_alt.as<uint64_t>(), c->idx.as<uint32_t>(), c->idx_alt.as<uint32_t>(), n, 0u,
+			                    (unsigned)(32 + l)));
 			hipLaunchKernelGGL(kd_permute_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, pos, unsort, c->idx_alt.as<uint32_t>(), pos_alt, unsort_alt, n);
 		}
 		std::swap(pos, pos_alt);

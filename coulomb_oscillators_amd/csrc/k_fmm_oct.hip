@@ -20,7 +20,7 @@
 //   L2L/L2P   generated bodies shared with the kd-tree path; L2P is fused with the near-field sum and the rescale
 #include "nbco_internal.hpp"
 #include "k_p2p.hpp"
-#include <rocprim/rocprim.hpp>
+#include "host_util.hpp"
 #include <cmath>
 #include <algorithm>
 
@@ -46,8 +46,6 @@ struct OctView
 	int L, ntot, side;
 	long long n;
 };
-
-static int grid1d(long long n, int cap = 1 << 20) { return (int)std::min<long long>((n + kBlock - 1) / kBlock, cap); }
 
 // ---- keys -----------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
@@ -476,58 +474,95 @@ static int oct_levels(long long n, int p, float dens_inhom)   // fmm_cart3_trace
 	return std::max(L, 2);
 }
 
-static int scan_ints(nbco_ctx *c, int *in, int *out, size_t count)
-{
-	size_t bytes = 0;
-	NBCO_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int>(), c->stream));
-	NBCO_TRY(c->reserve(c->sort_tmp, bytes));
-	bytes = c->sort_tmp.bytes;
-	NBCO_HIP(rocprim::exclusive_scan(c->sort_tmp.ptr, bytes, in, out, 0, count, rocprim::plus<int>(), c->stream));
-	return NBCO_OK;
-}
+// ---- host side ------------------------------------------------------------------------------------------------------
+// One evaluation = oct_eval: the stages below in order, on c->stream, with one host round trip (inside oct_lists).  The host
+// code knows the order P and the multipole layout only as numbers; each of the four kernels that are compiled per order is
+// launched by one oct_launch_* function, the one place where P and `sym` become template arguments (with_order, host_util.hpp).
+constexpr int kGridCap = 1 << 20;
+constexpr int kOctFirst = 9;   // oct_beg(2): levels 0 and 1 carry no expansions
 
-static int m2l_lanes(nbco_ctx *c, int P, const float4 *csz, const float *mpole, float *local, const uint64_t *keys, const int *start, int shift, int ntot, int mstride)
+// what the stages of one evaluation hand each other; lives on oct_eval's stack
+template <typename T>
+struct OctRun
 {
-	return launch_m2l_lanes(c, P, csz, mpole, local, keys, start, shift, ntot, mstride);
-}
-static int m2l_lanes(nbco_ctx *c, int P, const float4 *csz, const double *mpole, double *local, const uint64_t *keys, const int *start, int shift, int ntot, int mstride)
-{
-	return launch_m2l_lanes_f64(c, P, csz, mpole, local, keys, start, shift, ntot, mstride);
-}
-
-// world > 1: this rank's slab of the cell order only (oct_slab_kernel); pbounds_host[world + 1] = the particle boundaries of all slabs
-template <int P, typename T, bool SYM>
-static int oct_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, int world = 1, int rank = 0, long long *pbounds_host = nullptr)
-{
-	// SYM: fmm_cart3 (fmm_cart3_symmetric.cuh:413-580) -- multipole tuples in the symmetric layout, orders 0..P (offMP reals);
-	// the M2L kernel reads their first offM reals (orders 0..P-1: an order-P multipole only meets the order-0 local, which is not
-	// formed, m2l_acc3 with minm = 1), everything from the M2L list on is shared with the traceless evaluator
-	constexpr int offL = NBCO_OFFL(P), offM = P * (P + 1) * (P + 2) / 6;
-	constexpr int offMP = SYM ? NBCO_OFFM(P + 1) : offL;   // reals per stored multipole tuple
-	hipStream_t st = c->stream;
-	const int radius = (int)c->o.tree_radius;   // fmm_cart3_traceless.cuh:439
-	if (radius < 1) return c->fail(NBCO_ERR_ARG, "nbco_fmm_traceless: tree_radius must be >= 1");
-	const int L = oct_levels(n, P, c->o.dens_inhom);
-	if (L > 8) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_traceless: more than 8 octree levels");
-	const int side = 1 << L, m = oct_cnt(L), beg = oct_beg(L), ntot = oct_beg(L + 1);
-	const int first = oct_beg(2);   // levels 0 and 1 carry no expansions
-
-	// ---- storage -----------------------------------------------------------------------------------------
-	{
-		size_t bytes = (size_t)ntot * (sizeof(float4) + sizeof(T) * ((size_t)offL + offMP + offM) + 2 * sizeof(int)) + 256;
-		NBCO_TRY(c->reserve(c->oct_tree, bytes));
-	}
 	OctView<T> t;
-	{
-		char *q = (char *)c->oct_tree.ptr;
-		t.csz = (float4 *)q; q += sizeof(float4) * (size_t)ntot;
-		t.mpole = (T *)q; q += sizeof(T) * (size_t)ntot * offMP;
-		t.local = (T *)q; q += sizeof(T) * (size_t)ntot * offL;
-		t.msym = (T *)q; q += sizeof(T) * (size_t)ntot * offM;
-		t.mult = (int *)q; q += sizeof(int) * (size_t)ntot;
-		t.index = (int *)q;   // ntot + 1 entries
-		t.L = L; t.ntot = ntot; t.side = side; t.n = n;
-	}
+	int P, radius, world, rank;
+	// sym: fmm_cart3 (fmm_cart3_symmetric.cuh:413-580) -- multipole tuples in the symmetric layout, orders 0..P (offMP reals); the M2L
+	// kernel reads their first offM reals (orders 0..P-1: an order-P multipole only meets the order-0 local, which is not formed,
+	// m2l_acc3 with minm = 1), everything from the M2L list on is shared with the traceless evaluator
+	bool sym;
+	int offL, offM, offMP;   // reals per local tuple, per symmetric tuple of orders 0..P-1 (what M2L reads), per stored multipole tuple
+	float4 *pos_in, *pos;                       // packed positions in the caller's order / in cell order
+	uint32_t *keys_in, *keys, *idx_in, *idx;    // cell keys and permutation before / after the sort
+	// per-cell work counters, m + 1 entries each, and the M2L entries per node (count, start), ntot + 2 entries each
+	int *ngroup, *ndesc, *nchunk, *group_off, *desc_off, *chunk_off, *m2l_cnt, *m2l_start;
+	int tpl, shift;                   // targets per P2P group; M2L key = target << shift | source
+	long long nm2l, ngr, nds, nck;    // M2L entries, P2P groups, descriptors, chunks (known after oct_lists' round trip)
+	bool have_near;
+	int *slab;            // device: this rank's slab, null = the whole cell order
+	long long *pbounds;   // device: particle boundaries of all slabs
+};
+
+static int oct_no_order(nbco_ctx *c, bool sym)
+{
+	// symmetric multipoles of orders 0..p come from the generated operators of order p + 1: p <= 9
+	if (sym) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_symmetric: orders 1..9");
+	return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_traceless: generated operators exist for orders 1..10");
+}
+
+template <typename T>
+static int oct_launch_leaf(nbco_ctx *c, int P, bool sym, const OctView<T> &t, const float4 *pos)
+{
+	const dim3 grid((oct_cnt(t.L) + kBlock / 64 - 1) / (kBlock / 64));
+	const bool ok = sym ? with_order<9>(P, [&](auto p) { hipLaunchKernelGGL((oct_leaf_kernel<decltype(p)::value, T, true>), grid, dim3(kBlock), 0, c->stream, t, pos); })
+	                    : with_order(P, [&](auto p) { hipLaunchKernelGGL((oct_leaf_kernel<decltype(p)::value, T, false>), grid, dim3(kBlock), 0, c->stream, t, pos); });
+	return ok ? NBCO_OK : oct_no_order(c, sym);
+}
+
+template <typename T>
+static int oct_launch_m2m(nbco_ctx *c, int P, bool sym, const OctView<T> &t, int l)
+{
+	const dim3 grid((oct_cnt(l) + kBlock - 1) / kBlock);
+	const bool ok = sym ? with_order<9>(P, [&](auto p) { hipLaunchKernelGGL((oct_m2m_kernel<decltype(p)::value, T, true>), grid, dim3(kBlock), 0, c->stream, t, l); })
+	                    : with_order(P, [&](auto p) { hipLaunchKernelGGL((oct_m2m_kernel<decltype(p)::value, T, false>), grid, dim3(kBlock), 0, c->stream, t, l); });
+	return ok ? NBCO_OK : oct_no_order(c, sym);
+}
+
+template <typename T>
+static int oct_launch_l2l(nbco_ctx *c, int P, const OctView<T> &t, int lchild, const int *slab)
+{
+	const dim3 grid((oct_cnt(lchild) + kBlock - 1) / kBlock);
+	const bool ok = with_order(P, [&](auto p) { hipLaunchKernelGGL((oct_l2l_kernel<decltype(p)::value, T>), grid, dim3(kBlock), 0, c->stream, t, lchild, slab); });
+	return ok ? NBCO_OK : oct_no_order(c, false);
+}
+
+template <typename T>
+static int oct_launch_l2p(nbco_ctx *c, const OctRun<T> &r, const float *param, float *a)
+{
+	const dim3 grid((unsigned)((r.t.n + kBlock - 1) / kBlock));
+	const bool ok = with_order(r.P, [&](auto p) {
+		hipLaunchKernelGGL((oct_l2p_kernel<decltype(p)::value, T>), grid, dim3(kBlock), 0, c->stream, r.t, (const float4 *)r.pos, (const uint32_t *)r.keys,
+		                   (const float4 *)c->part.as<float4>(), (const int *)r.group_off, (const int *)r.desc_off, (const int *)r.chunk_off, r.tpl,
+		                   r.have_near ? 1 : 0, param, a, (const int *)r.slab);
+	});
+	return ok ? NBCO_OK : oct_no_order(c, false);
+}
+
+// storage: the tree arrays in one allocation, the particle scratch, the per-cell counters
+template <typename T>
+static int oct_carve(nbco_ctx *c, OctRun<T> &r, long long n, int L)
+{
+	const int m = oct_cnt(L), ntot = oct_beg(L + 1);
+	NBCO_TRY(c->reserve(c->oct_tree, (size_t)ntot * (sizeof(float4) + sizeof(T) * ((size_t)r.offL + r.offMP + r.offM) + 2 * sizeof(int)) + 256));
+	OctView<T> &t = r.t;
+	char *q = (char *)c->oct_tree.ptr;
+	t.csz = (float4 *)q; q += sizeof(float4) * (size_t)ntot;
+	t.mpole = (T *)q; q += sizeof(T) * (size_t)ntot * r.offMP;
+	t.local = (T *)q; q += sizeof(T) * (size_t)ntot * r.offL;
+	t.msym = (T *)q; q += sizeof(T) * (size_t)ntot * r.offM;
+	t.mult = (int *)q; q += sizeof(int) * (size_t)ntot;
+	t.index = (int *)q;   // ntot + 1 entries
+	t.L = L; t.ntot = ntot; t.side = 1 << L; t.n = n;
 	// the tree-ordered positions and the sorted M2L keys of the last kd evaluation are overwritten below (pos4, m2l_keys_alt):
 	// nbco_energy_fmm must follow a kd evaluation, as after the direct sums (k_direct.hip)
 	c->last_eval.valid = false;
@@ -537,154 +572,225 @@ static int oct_eval(nbco_ctx *c, float *p, float *a, long long n, const float *p
 	NBCO_TRY(c->reserve(c->idx, sizeof(uint32_t) * (size_t)n));
 	NBCO_TRY(c->reserve(c->idx_alt, sizeof(uint32_t) * (size_t)n));
 	NBCO_TRY(c->reserve(c->counters, sizeof(int) * 128));
-	// per-cell work counters: [ngroup | ndesc | nchunk | group_off | desc_off | chunk_off], m + 1 entries each; M2L: cnt, start
 	NBCO_TRY(c->reserve(c->list_cnt, sizeof(int) * (6 * ((size_t)m + 1) + 2 * ((size_t)ntot + 2))));
-	int *ngroup = c->list_cnt.as<int>(), *ndesc = ngroup + (m + 1), *nchunk = ndesc + (m + 1);
-	int *group_off = nchunk + (m + 1), *desc_off = group_off + (m + 1), *chunk_off = desc_off + (m + 1);
-	int *m2l_cnt = chunk_off + (m + 1), *m2l_start = m2l_cnt + (ntot + 2);
+	r.ngroup = c->list_cnt.as<int>(); r.ndesc = r.ngroup + (m + 1); r.nchunk = r.ndesc + (m + 1);
+	r.group_off = r.nchunk + (m + 1); r.desc_off = r.group_off + (m + 1); r.chunk_off = r.desc_off + (m + 1);
+	r.m2l_cnt = r.chunk_off + (m + 1); r.m2l_start = r.m2l_cnt + (ntot + 2);
+	r.pos_in = c->pos4_alt.as<float4>(); r.pos = c->pos4.as<float4>();
+	r.keys_in = c->keys.as<uint32_t>(); r.keys = r.keys_in + n;
+	r.idx_in = c->idx.as<uint32_t>(); r.idx = c->idx_alt.as<uint32_t>();
+	r.slab = nullptr; r.pbounds = nullptr;
+	return NBCO_OK;
+}
 
-	int *slab = nullptr;            // device: this rank's slab, null = the whole cell order
-	long long *pbounds = nullptr;   // device: particle boundaries of all slabs
-	if (world > 64 || world < 1 || rank < 0 || rank >= world) return c->fail(NBCO_ERR_ARG, "nbco_fmm_oct_shard: 1 <= world <= 64, 0 <= rank < world");
-	float4 *pos_in = c->pos4_alt.as<float4>(), *pos = c->pos4.as<float4>();
-	uint32_t *keys_in = c->keys.as<uint32_t>(), *keys = keys_in + n;
-	uint32_t *idx_in = c->idx.as<uint32_t>(), *idx = c->idx_alt.as<uint32_t>();
+// keys, sort, cell ranges; world > 1: this rank's slab of the cell order (oct_slab_kernel)
+template <typename T>
+static int oct_build(nbco_ctx *c, OctRun<T> &r, const float *p)
+{
+	PhaseScope ph(c, NBCO_PH_BUILD);
+	hipStream_t st = c->stream;
+	const OctView<T> &t = r.t;
+	const long long n = t.n;
+	NBCO_TRY(launch_pack4(c, r.pos_in, p, n));
+	float *mm = c->small.as<float>() + 64, *scal = c->small.as<float>() + 96;
+	NBCO_TRY(launch_minmax4(c, r.pos_in, n, mm));
+	hipLaunchKernelGGL(oct_scalars_kernel, dim3(1), dim3(64), 0, st, (const float *)mm, t.side, std::sqrt(c->o.eps2), scal);
+	hipLaunchKernelGGL(oct_keys_kernel, dim3(grid_blocks(n, kBlock, kGridCap)), dim3(kBlock), 0, st, (const float4 *)r.pos_in, n, (const float *)scal, t.side,
+	                   r.keys_in, r.idx_in);
+	NBCO_TRY(sort_pairs(c, c->sort_tmp, r.keys_in, r.keys, r.idx_in, r.idx, n, 0u, (unsigned)(3 * t.L)));
+	hipLaunchKernelGGL(oct_gather4_kernel, dim3(grid_blocks(n, kBlock, kGridCap)), dim3(kBlock), 0, st, (const float4 *)r.pos_in, (const uint32_t *)r.idx, r.pos, n);
+	hipLaunchKernelGGL(oct_index_kernel<T>, dim3(grid_blocks(oct_cnt(t.L) + 1, kBlock, kGridCap)), dim3(kBlock), 0, st, t, (const uint32_t *)r.keys);
+	if (r.world > 1)
+	{
+		r.slab = c->counters.as<int>() + 64;
+		r.pbounds = reinterpret_cast<long long *>(c->small.as<float>() + 128);
+		hipLaunchKernelGGL(oct_slab_kernel<T>, dim3(1), dim3(128), 0, st, t, r.world, r.rank, r.slab, r.pbounds);
+	}
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
 
-	// ---- build: keys, sort, cell ranges ----------------------------------------------------------------------
+// P2M, M2M, and for the traceless layout the symmetric copy that M2L reads
+template <typename T>
+static int oct_upward(nbco_ctx *c, OctRun<T> &r)
+{
+	PhaseScope ph(c, NBCO_PH_P2M_M2M);
+	const OctView<T> &t = r.t;
+	NBCO_TRY(oct_launch_leaf(c, r.P, r.sym, t, (const float4 *)r.pos));
+	for (int l = t.L - 1; l >= 2; --l) NBCO_TRY(oct_launch_m2m(c, r.P, r.sym, t, l));
+	if (!r.sym)
+		hipLaunchKernelGGL(oct_expand_kernel<T>, dim3(grid_blocks(t.ntot - kOctFirst, kBlock, kGridCap)), dim3(kBlock), 0, c->stream, t, r.P, kOctFirst);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// work lists: M2L stencil entries, P2P groups / descriptors / chunks.  A counting pass, the one host round trip of the evaluation
+// (the sizes of the lists), and the fill pass.  pbounds_host (world > 1): the particle boundaries of all slabs ride along.
+template <typename T>
+static int oct_lists(nbco_ctx *c, OctRun<T> &r, long long *pbounds_host)
+{
+	PhaseScope ph(c, NBCO_PH_LISTS);
+	hipStream_t st = c->stream;
+	const OctView<T> &t = r.t;
+	const int m = oct_cnt(t.L), ntot = t.ntot;
+	const bool coll = c->o.coll != 0;
+	const double avg = (double)t.n / (double)m;
+	r.tpl = 8;
+	while (r.tpl < 64 && r.tpl < 2 * avg) r.tpl <<= 1;
+	r.shift = 1;
+	while ((1LL << r.shift) < ntot) ++r.shift;
+	hipLaunchKernelGGL((oct_m2l_list_kernel<false, T>), dim3(grid_blocks(ntot, kBlock, kGridCap)), dim3(kBlock), 0, st, t, r.radius, kOctFirst, r.m2l_cnt,
+	                   (const int *)nullptr, r.shift, (uint64_t *)nullptr, (const int *)r.slab);
+	NBCO_TRY(exclusive_scan(c, c->sort_tmp, r.m2l_cnt, r.m2l_start, 0, (size_t)ntot + 1));
+	if (coll)
 	{
-		PhaseScope ph(c, NBCO_PH_BUILD);
-		NBCO_TRY(launch_pack4(c, pos_in, p, n));
-		float *mm = c->small.as<float>() + 64, *scal = c->small.as<float>() + 96;
-		NBCO_TRY(launch_minmax4(c, pos_in, n, mm));
-		hipLaunchKernelGGL(oct_scalars_kernel, dim3(1), dim3(64), 0, st, (const float *)mm, side, std::sqrt(c->o.eps2), scal);
-		hipLaunchKernelGGL(oct_keys_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, (const float4 *)pos_in, n, (const float *)scal, side, keys_in, idx_in);
-		size_t bytes = 0;
-		NBCO_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys, idx_in, idx, (size_t)n, 0u, (unsigned)(3 * L), st));
-		NBCO_TRY(c->reserve(c->sort_tmp, bytes));
-		bytes = c->sort_tmp.bytes;
-		NBCO_HIP(rocprim::radix_sort_pairs(c->sort_tmp.ptr, bytes, keys_in, keys, idx_in, idx, (size_t)n, 0u, (unsigned)(3 * L), st));
-		hipLaunchKernelGGL(oct_gather4_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, (const float4 *)pos_in, (const uint32_t *)idx, pos, n);
-		hipLaunchKernelGGL(oct_index_kernel<T>, dim3(grid1d(m + 1)), dim3(kBlock), 0, st, t, (const uint32_t *)keys);
-		if (world > 1)
-		{
-			slab = c->counters.as<int>() + 64;
-			pbounds = reinterpret_cast<long long *>(c->small.as<float>() + 128);
-			hipLaunchKernelGGL(oct_slab_kernel<T>, dim3(1), dim3(128), 0, st, t, world, rank, slab, pbounds);
-		}
-		NBCO_HIP(hipGetLastError());
+		hipLaunchKernelGGL(oct_p2p_count_kernel<T>, dim3(grid_blocks(m + 1, kBlock, kGridCap)), dim3(kBlock), 0, st, t, r.radius, r.tpl, r.ngroup, r.ndesc, r.nchunk,
+		                   (const int *)r.slab);
+		NBCO_TRY(exclusive_scan(c, c->sort_tmp, r.ngroup, r.group_off, 0, (size_t)m + 1));
+		NBCO_TRY(exclusive_scan(c, c->sort_tmp, r.ndesc, r.desc_off, 0, (size_t)m + 1));
+		NBCO_TRY(exclusive_scan(c, c->sort_tmp, r.nchunk, r.chunk_off, 0, (size_t)m + 1));
 	}
-	// ---- P2M, M2M ----------------------------------------------------------------------------------------
-	{
-		PhaseScope ph(c, NBCO_PH_P2M_M2M);
-		hipLaunchKernelGGL((oct_leaf_kernel<P, T, SYM>), dim3((m + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, st, t, (const float4 *)pos);
-		for (int l = L - 1; l >= 2; --l) hipLaunchKernelGGL((oct_m2m_kernel<P, T, SYM>), dim3((oct_cnt(l) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, t, l);
-		if (!SYM) hipLaunchKernelGGL(oct_expand_kernel<T>, dim3(grid1d(ntot - first)), dim3(kBlock), 0, st, t, P, first);
-		NBCO_HIP(hipGetLastError());
-	}
-	// ---- work lists: M2L stencil entries, P2P groups / descriptors / chunks -----------------------------------------
 	int h_tot[4] = {0, 0, 0, 0};   // M2L entries, groups, descriptors, chunks
-	const int tpl = [&] {
-		const double avg = (double)n / (double)m;
-		int v = 8;
-		while (v < 64 && v < 2 * avg) v <<= 1;
-		return v;
-	}();
-	int shift = 1;
-	while ((1LL << shift) < ntot) ++shift;
+	NBCO_HIP(hipMemcpyAsync(&h_tot[0], r.m2l_start + ntot, sizeof(int), hipMemcpyDeviceToHost, st));
+	if (coll)
 	{
-		PhaseScope ph(c, NBCO_PH_LISTS);
-		hipLaunchKernelGGL((oct_m2l_list_kernel<false, T>), dim3(grid1d(ntot)), dim3(kBlock), 0, st, t, radius, first, m2l_cnt, (const int *)nullptr, shift,
-		                   (uint64_t *)nullptr, (const int *)slab);
-		NBCO_TRY(scan_ints(c, m2l_cnt, m2l_start, (size_t)ntot + 1));
-		if (c->o.coll)
-		{
-			hipLaunchKernelGGL(oct_p2p_count_kernel<T>, dim3(grid1d(m + 1)), dim3(kBlock), 0, st, t, radius, tpl, ngroup, ndesc, nchunk, (const int *)slab);
-			NBCO_TRY(scan_ints(c, ngroup, group_off, (size_t)m + 1));
-			NBCO_TRY(scan_ints(c, ndesc, desc_off, (size_t)m + 1));
-			NBCO_TRY(scan_ints(c, nchunk, chunk_off, (size_t)m + 1));
-		}
-		NBCO_HIP(hipMemcpyAsync(&h_tot[0], m2l_start + ntot, sizeof(int), hipMemcpyDeviceToHost, st));
-		if (c->o.coll)
-		{
-			NBCO_HIP(hipMemcpyAsync(&h_tot[1], group_off + m, sizeof(int), hipMemcpyDeviceToHost, st));
-			NBCO_HIP(hipMemcpyAsync(&h_tot[2], desc_off + m, sizeof(int), hipMemcpyDeviceToHost, st));
-			NBCO_HIP(hipMemcpyAsync(&h_tot[3], chunk_off + m, sizeof(int), hipMemcpyDeviceToHost, st));
-		}
-		if (pbounds_host && world > 1) NBCO_HIP(hipMemcpyAsync(pbounds_host, pbounds, sizeof(long long) * (size_t)(world + 1), hipMemcpyDeviceToHost, st));
-		NBCO_HIP(hipStreamSynchronize(st));   // the one host round trip of the evaluation: sizes of the work lists
-		const long long nm2l = h_tot[0], ngr = h_tot[1], nds = h_tot[2], nck = h_tot[3];
-		if (nm2l < 0 || nck < 0) return c->fail(NBCO_ERR_CAPACITY, "nbco_fmm_traceless: work list size overflows 32 bits");
-		NBCO_TRY(c->reserve(c->m2l_keys_alt, sizeof(uint64_t) * (size_t)(nm2l + 1)));
-		if (nm2l > 0)
-			hipLaunchKernelGGL((oct_m2l_list_kernel<true, T>), dim3(grid1d(ntot)), dim3(kBlock), 0, st, t, radius, first, (int *)nullptr, (const int *)m2l_start,
-			                   shift, c->m2l_keys_alt.as<uint64_t>(), (const int *)slab);
-		if (c->o.coll)
-		{
-			NBCO_TRY(c->reserve(c->oct_groups, sizeof(int) * 3 * (size_t)(ngr + 1)));
-			NBCO_TRY(c->reserve(c->p2p_keys, sizeof(int2) * (size_t)(nds + 1)));
-			NBCO_TRY(c->reserve(c->p2p_chunks, sizeof(int4) * (size_t)(nck + 1)));
-			NBCO_TRY(c->reserve(c->part, sizeof(float4) * (size_t)nck * (size_t)tpl + 256));
-			int *grp_index = c->oct_groups.as<int>(), *grp_mult = grp_index + (ngr + 1), *grp_cell = grp_mult + (ngr + 1);
-			hipLaunchKernelGGL(oct_p2p_fill_kernel<T>, dim3(grid1d(m)), dim3(kBlock), 0, st, t, radius, tpl, (const int *)group_off, (const int *)desc_off,
-			                   grp_index, grp_mult, grp_cell, c->p2p_keys.as<int2>(), (const int *)slab);
-			hipLaunchKernelGGL(oct_p2p_chunk_kernel, dim3(grid1d(std::max<long long>(ngr, 1))), dim3(kBlock), 0, st, (const int *)(group_off + m),
-			                   (const int *)grp_cell, (const int *)group_off, (const int *)desc_off, (const int *)chunk_off, (const int *)grp_index,
-			                   (const int *)grp_mult, c->p2p_chunks.as<int4>());
-		}
-		NBCO_HIP(hipGetLastError());
+		NBCO_HIP(hipMemcpyAsync(&h_tot[1], r.group_off + m, sizeof(int), hipMemcpyDeviceToHost, st));
+		NBCO_HIP(hipMemcpyAsync(&h_tot[2], r.desc_off + m, sizeof(int), hipMemcpyDeviceToHost, st));
+		NBCO_HIP(hipMemcpyAsync(&h_tot[3], r.chunk_off + m, sizeof(int), hipMemcpyDeviceToHost, st));
 	}
-	const long long nm2l = h_tot[0], ngr = h_tot[1], nck = h_tot[3];
-	// ---- P2P -----------------------------------------------------------------------------------------------
+	if (pbounds_host && r.world > 1)
+		NBCO_HIP(hipMemcpyAsync(pbounds_host, r.pbounds, sizeof(long long) * (size_t)(r.world + 1), hipMemcpyDeviceToHost, st));
+	NBCO_HIP(hipStreamSynchronize(st));
+	r.nm2l = h_tot[0]; r.ngr = h_tot[1]; r.nds = h_tot[2]; r.nck = h_tot[3];
+	r.have_near = coll && r.nck > 0;
+	if (r.nm2l < 0 || r.nck < 0) return c->fail(NBCO_ERR_CAPACITY, "nbco_fmm_traceless: work list size overflows 32 bits");
+	NBCO_TRY(c->reserve(c->m2l_keys_alt, sizeof(uint64_t) * (size_t)(r.nm2l + 1)));
+	if (r.nm2l > 0)
+		hipLaunchKernelGGL((oct_m2l_list_kernel<true, T>), dim3(grid_blocks(ntot, kBlock, kGridCap)), dim3(kBlock), 0, st, t, r.radius, kOctFirst, (int *)nullptr,
+		                   (const int *)r.m2l_start, r.shift, c->m2l_keys_alt.as<uint64_t>(), (const int *)r.slab);
+	if (coll)
+	{
+		NBCO_TRY(c->reserve(c->oct_groups, sizeof(int) * 3 * (size_t)(r.ngr + 1)));
+		NBCO_TRY(c->reserve(c->p2p_keys, sizeof(int2) * (size_t)(r.nds + 1)));
+		NBCO_TRY(c->reserve(c->p2p_chunks, sizeof(int4) * (size_t)(r.nck + 1)));
+		NBCO_TRY(c->reserve(c->part, sizeof(float4) * (size_t)r.nck * (size_t)r.tpl + 256));
+		int *grp_index = c->oct_groups.as<int>(), *grp_mult = grp_index + (r.ngr + 1), *grp_cell = grp_mult + (r.ngr + 1);
+		hipLaunchKernelGGL(oct_p2p_fill_kernel<T>, dim3(grid_blocks(m, kBlock, kGridCap)), dim3(kBlock), 0, st, t, r.radius, r.tpl, (const int *)r.group_off,
+		                   (const int *)r.desc_off, grp_index, grp_mult, grp_cell, c->p2p_keys.as<int2>(), (const int *)r.slab);
+		hipLaunchKernelGGL(oct_p2p_chunk_kernel, dim3(grid_blocks(std::max<long long>(r.ngr, 1), kBlock, kGridCap)), dim3(kBlock), 0, st,
+		                   (const int *)(r.group_off + m), (const int *)grp_cell, (const int *)r.group_off, (const int *)r.desc_off, (const int *)r.chunk_off,
+		                   (const int *)grp_index, (const int *)grp_mult, c->p2p_chunks.as<int4>());
+	}
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// P2P: partial sums per (chunk, target) into c->part; oct_l2p adds them up
+template <typename T>
+static int oct_near(nbco_ctx *c, const OctRun<T> &r)
+{
+	if (!r.have_near) return NBCO_OK;
+	PhaseScope ph(c, NBCO_PH_P2P);
+	const int2 *pd = c->p2p_keys.as<int2>();
+	const int4 *pc = c->p2p_chunks.as<int4>();
+	const int *pt = r.chunk_off + oct_cnt(r.t.L);
 	float4 *near = c->part.as<float4>();
-	const bool have_near = c->o.coll && nck > 0;
-	if (have_near)
-	{
-		PhaseScope ph(c, NBCO_PH_P2P);
-		const int2 *pd = c->p2p_keys.as<int2>();
-		const int4 *pc = c->p2p_chunks.as<int4>();
-		const int *pt = chunk_off + m;
-		if (tpl == 8) launch_p2p<8>(c, pos, pd, pc, pt, nck, kSrcPiece, tpl, near, n);
-		else if (tpl == 16) launch_p2p<16>(c, pos, pd, pc, pt, nck, kSrcPiece, tpl, near, n);
-		else if (tpl == 32) launch_p2p<32>(c, pos, pd, pc, pt, nck, kSrcPiece, tpl, near, n);
-		else launch_p2p<64>(c, pos, pd, pc, pt, nck, kSrcPiece, tpl, near, n);
-		NBCO_HIP(hipGetLastError());
-	}
-	// ---- M2L, L2L ------------------------------------------------------------------------------------------
+	const long long n = r.t.n;
+	if (r.tpl == 8) launch_p2p<8>(c, r.pos, pd, pc, pt, r.nck, kSrcPiece, r.tpl, near, n);
+	else if (r.tpl == 16) launch_p2p<16>(c, r.pos, pd, pc, pt, r.nck, kSrcPiece, r.tpl, near, n);
+	else if (r.tpl == 32) launch_p2p<32>(c, r.pos, pd, pc, pt, r.nck, kSrcPiece, r.tpl, near, n);
+	else launch_p2p<64>(c, r.pos, pd, pc, pt, r.nck, kSrcPiece, r.tpl, near, n);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// M2L over the stencil list (the register-resident kernels of k_m2l.hip), then L2L down to the leaves
+template <typename T>
+static int oct_far(nbco_ctx *c, const OctRun<T> &r)
+{
+	const OctView<T> &t = r.t;
 	{
 		PhaseScope ph(c, NBCO_PH_M2L);
-		NBCO_HIP(hipMemsetAsync(t.local, 0, sizeof(T) * (size_t)ntot * offL, st));
-		if (nm2l > 0) NBCO_TRY(m2l_lanes(c, P, t.csz, SYM ? t.mpole : t.msym, t.local, c->m2l_keys_alt.as<uint64_t>(), m2l_start, shift, ntot, SYM ? offMP : 0));
+		NBCO_HIP(hipMemsetAsync(t.local, 0, sizeof(T) * (size_t)t.ntot * r.offL, c->stream));
+		if (r.nm2l > 0)
+		{
+			const T *mp = r.sym ? t.mpole : t.msym;
+			const uint64_t *keys = c->m2l_keys_alt.as<uint64_t>();
+			const int mstride = r.sym ? r.offMP : 0;
+			if constexpr (std::is_same<T, double>::value) NBCO_TRY(launch_m2l_lanes_f64(c, r.P, t.csz, mp, t.local, keys, r.m2l_start, r.shift, t.ntot, mstride));
+			else NBCO_TRY(launch_m2l_lanes(c, r.P, t.csz, mp, t.local, keys, r.m2l_start, r.shift, t.ntot, mstride));
+		}
 	}
-	{
-		PhaseScope ph(c, NBCO_PH_L2L);
-		for (int lc = 3; lc <= L; ++lc)
-			hipLaunchKernelGGL((oct_l2l_kernel<P, T>), dim3((oct_cnt(lc) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, t, lc, (const int *)slab);
-		NBCO_HIP(hipGetLastError());
-	}
-	// ---- L2P + near field + rescale -------------------------------------------------------------------------
-	{
-		PhaseScope ph(c, NBCO_PH_L2P);
-		hipLaunchKernelGGL((oct_l2p_kernel<P, T>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, t, (const float4 *)pos, (const uint32_t *)keys,
-		                   (const float4 *)near, (const int *)group_off, (const int *)desc_off, (const int *)chunk_off, tpl, have_near ? 1 : 0, param, a,
-		                   (const int *)slab);
-		NBCO_HIP(hipGetLastError());
-	}
-	// ---- positions and velocities in cell order (fmm_cart3_traceless.cuh:386-392, :530-535) ------------------------
-	{
-		PhaseScope ph(c, NBCO_PH_FINISH);
-		hipLaunchKernelGGL(oct_unpack4_kernel, dim3(grid1d(n)), dim3(kBlock), 0, st, (const float4 *)pos, p, n);
-		NBCO_TRY(c->reserve(c->tmp3, sizeof(float) * 3 * (size_t)n));
-		NBCO_TRY(launch_gather3(c, c->tmp3.as<float>(), p + 3 * n, (const int *)idx, n, false));
-		NBCO_HIP(hipMemcpyAsync(p + 3 * n, c->tmp3.ptr, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, st));
-		NBCO_HIP(hipGetLastError());
-	}
-	if (pbounds_host && world == 1) { pbounds_host[0] = 0; pbounds_host[1] = n; }
+	PhaseScope ph(c, NBCO_PH_L2L);
+	for (int lc = 3; lc <= t.L; ++lc) NBCO_TRY(oct_launch_l2l(c, r.P, t, lc, (const int *)r.slab));
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// L2P + near field + rescale
+template <typename T>
+static int oct_l2p(nbco_ctx *c, const OctRun<T> &r, const float *param, float *a)
+{
+	PhaseScope ph(c, NBCO_PH_L2P);
+	NBCO_TRY(oct_launch_l2p(c, r, param, a));
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// positions and velocities in cell order (fmm_cart3_traceless.cuh:386-392, :530-535)
+template <typename T>
+static int oct_finish_order(nbco_ctx *c, const OctRun<T> &r, float *p)
+{
+	PhaseScope ph(c, NBCO_PH_FINISH);
+	const long long n = r.t.n;
+	hipLaunchKernelGGL(oct_unpack4_kernel, dim3(grid_blocks(n, kBlock, kGridCap)), dim3(kBlock), 0, c->stream, (const float4 *)r.pos, p, n);
+	NBCO_TRY(c->reserve(c->tmp3, sizeof(float) * 3 * (size_t)n));
+	NBCO_TRY(launch_gather3(c, c->tmp3.as<float>(), p + 3 * n, (const int *)r.idx, n, false));
+	NBCO_HIP(hipMemcpyAsync(p + 3 * n, c->tmp3.ptr, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// what nbco_oct_get_info and nbco_oct_copy report about this evaluation
+template <typename T>
+static void oct_commit(nbco_ctx *c, const OctRun<T> &r)
+{
+	const OctView<T> &t = r.t;
 	OctTreeDev &o = c->oct;
-	o.L = L; o.ntot = ntot; o.order = P; o.n = n; o.csz = t.csz; o.mpole = t.mpole; o.local = t.local; o.mult = t.mult; o.index = t.index;
-	o.keys = keys; o.perm = idx; o.m2l_entries = nm2l; o.p2p_groups = ngr; o.p2p_desc = h_tot[2]; o.p2p_chunks = nck; o.tpl = tpl;
+	o.L = t.L; o.ntot = t.ntot; o.order = r.P; o.n = t.n; o.csz = t.csz; o.mpole = t.mpole; o.local = t.local; o.mult = t.mult; o.index = t.index;
+	o.keys = r.keys; o.perm = r.idx; o.m2l_entries = r.nm2l; o.p2p_groups = r.ngr; o.p2p_desc = r.nds; o.p2p_chunks = r.nck; o.tpl = r.tpl;
 	o.real_bytes = (int)sizeof(T);
-	o.mpole_reals = offMP;
+	o.mpole_reals = r.offMP;
 	o.valid = true;
+}
+
+// T = float, or double with opts.far_fp64.  world > 1: this rank's slab of the cell order only; pbounds_host[world + 1] = the
+// particle boundaries of all slabs.  Everything that can refuse the call is asked before the first side effect.
+template <typename T>
+static int oct_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, bool sym, int world, int rank, long long *pbounds_host)
+{
+	OctRun<T> r;
+	r.P = c->o.fmm_order; r.sym = sym; r.world = world; r.rank = rank;
+	if (r.P < 1 || r.P > (sym ? 9 : 10)) return oct_no_order(c, sym);
+	r.radius = (int)c->o.tree_radius;   // fmm_cart3_traceless.cuh:439
+	if (r.radius < 1) return c->fail(NBCO_ERR_ARG, "nbco_fmm_traceless: tree_radius must be >= 1");
+	const int L = oct_levels(n, r.P, c->o.dens_inhom);
+	if (L > 8) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_traceless: more than 8 octree levels");
+	if (world > 64 || world < 1 || rank < 0 || rank >= world) return c->fail(NBCO_ERR_ARG, "nbco_fmm_oct_shard: 1 <= world <= 64, 0 <= rank < world");
+	r.offL = NBCO_OFFL(r.P);
+	r.offM = r.P * (r.P + 1) * (r.P + 2) / 6;
+	r.offMP = sym ? NBCO_OFFM(r.P + 1) : r.offL;
+
+	NBCO_TRY(oct_carve(c, r, n, L));
+	NBCO_TRY(oct_build(c, r, p));
+	NBCO_TRY(oct_upward(c, r));
+	NBCO_TRY(oct_lists(c, r, pbounds_host));
+	NBCO_TRY(oct_near(c, r));
+	NBCO_TRY(oct_far(c, r));
+	NBCO_TRY(oct_l2p(c, r, param, a));
+	NBCO_TRY(oct_finish_order(c, r, p));
+	if (pbounds_host && world == 1) { pbounds_host[0] = 0; pbounds_host[1] = n; }
+	oct_commit(c, r);
 	return NBCO_OK;
 }
 
@@ -694,27 +800,8 @@ int fmm_oct_traceless_eval(nbco_ctx *c, float *p, float *a, long long n, const f
 {
 	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_fmm_traceless: n must be positive");
 	if (n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_traceless: n too large for 32-bit indices");
-	const bool f64 = c->o.far_fp64 != 0;
-	if (symmetric)
-	{
-		// symmetric multipoles of orders 0..p come from the generated operators of order p + 1: p <= 9
-#define NBCO_OCT_CASE(PP) case PP: return f64 ? oct_eval<PP, double, true>(c, p, a, n, param, world, rank, pbounds_host) : oct_eval<PP, float, true>(c, p, a, n, param, world, rank, pbounds_host);
-		switch (c->o.fmm_order)
-		{
-		NBCO_OCT_CASE(1) NBCO_OCT_CASE(2) NBCO_OCT_CASE(3) NBCO_OCT_CASE(4) NBCO_OCT_CASE(5)
-		NBCO_OCT_CASE(6) NBCO_OCT_CASE(7) NBCO_OCT_CASE(8) NBCO_OCT_CASE(9)
-		default: return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_symmetric: orders 1..9");
-		}
-#undef NBCO_OCT_CASE
-	}
-#define NBCO_OCT_CASE(PP) case PP: return f64 ? oct_eval<PP, double, false>(c, p, a, n, param, world, rank, pbounds_host) : oct_eval<PP, float, false>(c, p, a, n, param, world, rank, pbounds_host);
-	switch (c->o.fmm_order)
-	{
-	NBCO_OCT_CASE(1) NBCO_OCT_CASE(2) NBCO_OCT_CASE(3) NBCO_OCT_CASE(4) NBCO_OCT_CASE(5)
-	NBCO_OCT_CASE(6) NBCO_OCT_CASE(7) NBCO_OCT_CASE(8) NBCO_OCT_CASE(9) NBCO_OCT_CASE(10)
-	default: return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_fmm_traceless: generated operators exist for orders 1..10");
-	}
-#undef NBCO_OCT_CASE
+	if (c->o.far_fp64) return oct_eval<double>(c, p, a, n, param, symmetric, world, rank, pbounds_host);
+	return oct_eval<float>(c, p, a, n, param, symmetric, world, rank, pbounds_host);
 }
 
 int oct_copy_out(nbco_ctx *c, int which, void *dst, long long bytes)

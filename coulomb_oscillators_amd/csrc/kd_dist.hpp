@@ -203,11 +203,7 @@ int kd_dist_partition(nbco_ctx *c, const float *state_all, long long n_global, i
 			uint32_t *own = reinterpret_cast<uint32_t *>(unsort + (size_t)rank * nl), *sorted = c->idx.as<uint32_t>();
 			int bits = 1;
 			while ((1LL << bits) < n) ++bits;
-			size_t bytes = 0;
-			NBCO_HIP(rocprim::radix_sort_keys(nullptr, bytes, own, sorted, (size_t)nl, 0u, (unsigned)bits, st));
-			NBCO_TRY(c->reserve(c->sort_tmp, bytes));
-			bytes = c->sort_tmp.bytes;
-			NBCO_HIP(rocprim::radix_sort_keys(c->sort_tmp.ptr, bytes, own, sorted, (size_t)nl, 0u, (unsigned)bits, st));
+			NBCO_TRY(sort_keys(c, c->sort_tmp, own, sorted, nl, 0u, (unsigned)bits));
 			NBCO_TRY(launch_gather3(c, state_local, state_all, reinterpret_cast<const int *>(sorted), nl, false));
 			NBCO_TRY(launch_gather3(c, state_local + 3 * nl, state_all + 3 * n, reinterpret_cast<const int *>(sorted), nl, false));
 		}

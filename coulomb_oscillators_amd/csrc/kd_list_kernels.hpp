@@ -440,12 +440,6 @@ __global__ __launch_bounds__(kBlock) void unpack4_kernel(const float4 *__restric
 	}
 }
 
-static int grid1d(long long n, int cap = 2048)
-{
-	long long b = (n + kBlock - 1) / kBlock;
-	if (b < 1) b = 1;
-	if (b > cap) b = cap;
-	return (int)b;
-}
+static int grid1d(long long n, int cap = 2048) { return std::max(1, grid_blocks(n, kBlock, cap)); }   // at least one block: n may be 0 here
 
 

@@ -160,6 +160,15 @@ def test_fmm_accelerations_match_restatement(engine, cfg):
             assert r < 1e-6 and g < 1e-6, (g, r)
 
 
+@pytest.mark.parametrize("p", range(1, 11))
+def test_every_order_reaches_its_own_kernels(engine, p):
+    """the order is chosen per kernel launch: every order at n = 2000, the smallest n of this file that has L >= 3 at every
+    order (L = 5 at p = 1, 3 at p = 10), with the comparison and the bars of test_fmm_accelerations_match_restatement"""
+    cfg = _cfg(p=p, n=2000)
+    assert F.levels(cfg["n"], p) >= 3
+    test_fmm_accelerations_match_restatement(engine, cfg)
+
+
 # every buffer shrinks and every stride changes between neighbours; the last call is the first again
 SEQUENCE = [_cfg(shape="gauss", n=30001, p=10), _cfg(shape="clusters", n=300, p=3, L=2), _cfg(shape="gauss", n=3000, p=2, L=13),
             _cfg(p=5), _cfg(shape="gauss", n=1, p=5), _cfg(shape="lattice", n=4096, p=7, L=6, coll=0, p1=0.37),

@@ -368,3 +368,52 @@ def test_baseline_config_2_by_name_properties(engine, oracle32):
     # stencil radius 1 at p = 6: truncation-bound, the level the reference's own -test table records (8.7e-3 at p = 6 on a
     # cube); the near field here covers almost everything
     assert err.max() < 2e-3, err.max()
+
+
+# ---- every accepted (evaluator, precision, order): the order is chosen per kernel launch, once per kernel ----------------------
+ORDER_SWEEP = [(ev, f64, p) for ev, top in (("traceless", 10), ("symmetric", 9)) for f64 in (0, 1) for p in range(1, top + 1)]
+
+
+@pytest.mark.parametrize("evaluator,far_fp64,p", ORDER_SWEEP)
+def test_every_order_reaches_its_own_kernels(engine, oracle32, oracle64, evaluator, far_fp64, p):
+    """A wrong case label in the order dispatch gives a plausible but less accurate force, or tuples of another order's size.
+    n = 3000 on the blob: L = 2..4 over the orders, so M2M, M2L, L2L and a near field of several cells all run.  The bars are
+    this file's: test_low_orders / test_orders_nine_and_ten (traceless), test_symmetric_evaluator_matches_oracle (symmetric)
+    and test_far_fp64_against_double_oracle (far_fp64, each evaluator against its own SCAL = double oracle)."""
+    import torch
+    n = 3000
+    sym = evaluator == "symmetric"
+    buf = state(oracle32, n, "blob")
+    par = oracle32.params(n)
+
+    def gpu(f64):
+        engine.set(fmm_order=p, far_fp64=f64)
+        d = dev(buf[:2])
+        a = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+        (engine.fmm_cart3 if sym else engine.fmm_cart3_traceless)(d, a, n, dev(par))
+        torch.cuda.synchronize()
+        return d.cpu().numpy(), a.cpu().numpy()
+
+    o = oracle64 if far_fp64 else oracle32
+    real = np.float64 if far_fp64 else np.float32
+    pv, want = (o.fmm_oct_symmetric if sym else o.fmm_oct_traceless)(buf[:2].astype(real), par.astype(real), p=p, threads=8)
+    tree = o.oct_tree(n)
+    got_pv, got = gpu(far_fp64)
+    info = engine.oct_info()
+    reals = (p + 1) * (p + 2) * (p + 3) // 6 if sym else (p + 1) ** 2
+    mp = engine.oct_array("mpole")
+    assert (info.order, info.L, info.ntot, info.real_bytes) == (p, tree["L"], tree["ntot"], 8 if far_fp64 else 4)
+    assert 2 <= info.L <= 4
+    assert info.mpole_reals == reals and mp.size == info.ntot * reals and mp.dtype == real
+    np.testing.assert_array_equal(engine.oct_array("keys").astype(np.int64), tree["keys"])
+    np.testing.assert_array_equal(got_pv, pv.astype(np.float32))
+    err = force_err(got, want)
+    print("oct %s far_fp64=%d p=%d L=%d err=%.3e" % (evaluator, far_fp64, p, info.L, err))
+    assert err < 1e-5
+    if far_fp64:
+        _, got32 = gpu(0)
+        assert engine.oct_info().real_bytes == 4
+        e32 = force_err(got32, want)
+        print("oct %s p=%d all-fp32 against the double oracle err=%.3e" % (evaluator, p, e32))
+        assert err < 1.5 * e32 + 2e-7          # never worse than the all-fp32 evaluation
+    engine.set(far_fp64=0)
