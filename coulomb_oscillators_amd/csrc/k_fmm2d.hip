@@ -16,6 +16,9 @@
 // Kernel plan per evaluation (L levels): minmax partials, scalars, keys, radix sort, gather, cell ranges, P2M, L-2 M2M, one M2L
 // launch for all levels, L-2 L2L, and the near field fused with L2P and the rescale.  No atomics anywhere: every sum has a fixed
 // order, so results are bit-reproducible.
+//
+// Energy diagnostics (f2d_energy_kernels.hpp): nbco_2d_energy sums the pair potential exactly; nbco_2d_energy_fmm builds the same
+// tree over a scratch copy of the positions and carries one real constant per cell next to the field's locals.
 #include "nbco_internal.hpp"
 #include "host_util.hpp"
 #include <algorithm>
@@ -502,6 +505,8 @@ __global__ __launch_bounds__(kNear) void f2d_near_kernel(Quad q, const double2 *
 	}
 }
 
+#include "f2d_energy_kernels.hpp"
+
 } // namespace
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -629,6 +634,125 @@ static int f2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double 
 	return f2d_fmm_run(c, p, a, n, param);
 }
 
+// ---- energy diagnostics ------------------------------------------------------------------------------------------------------
+static void f2d_launch_m2l0(nbco_ctx *c, int P, const Quad &q, double *c0, int L, int radius, double eps2)
+{
+	const long long nm2l = quad_beg(L + 1) - quad_beg(2);
+	with_order(P, [&](auto p) {
+		hipLaunchKernelGGL((f2d_m2l0_kernel<decltype(p)::value>), dim3((unsigned)((nm2l + kB - 1) / kB)), dim3(kB), 0, c->stream, q, c0, L, radius, eps2);
+	});
+}
+static void f2d_launch_l2l0(nbco_ctx *c, int P, const Quad &q, double *c0, int l)
+{
+	with_order(P, [&](auto p) { hipLaunchKernelGGL((f2d_l2l0_kernel<decltype(p)::value>), dim3(((1 << (2 * l)) + kB - 1) / kB), dim3(kB), 0, c->stream, q, c0, l); });
+}
+static void f2d_launch_near_pot(nbco_ctx *c, int P, int grid, const Quad &q, const double *c0, const double2 *x, const uint32_t *idx, int L, int radius,
+                                double eps2, const double *param, double *psi, double *part)
+{
+	with_order(P, [&](auto p) {
+		hipLaunchKernelGGL((f2d_near_pot_kernel<decltype(p)::value>), dim3(grid), dim3(kNear), 0, c->stream, q, c0, x, idx, L, radius, eps2, param, psi, part);
+	});
+}
+
+// f2d_part for an energy call: | minmax partials 4 kRedBlocks | scalars 8 (out3 at + 4) | kinetic / elastic slots 2 kRedBlocks | npot potential slots |
+static int f2d_energy_part(nbco_ctx *c, long long npot, double **scal, double **ke, double **pot)
+{
+	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (6 * (size_t)kRedBlocks + 8 + (size_t)npot)));
+	double *part = c->f2d_part.as<double>();
+	*scal = part + 4 * kRedBlocks;
+	*ke = *scal + 8;
+	*pot = *ke + 2 * kRedBlocks;
+	return NBCO_OK;
+}
+
+// kinetic and elastic slots, then the final block and the copy to the host
+static int f2d_energy_finish(nbco_ctx *c, const double *buf, long long n, const double *param, double *scal, double *ke, const double *pot, long long npot,
+                             double *out3_host)
+{
+	const int nke = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
+	hipLaunchKernelGGL(f2d_kin_ela_kernel, dim3(nke), dim3(kB), 0, c->stream, (const double2 *)buf, (const double2 *)buf + n, n, param + 2, ke);
+	hipLaunchKernelGGL(f2d_energy_final_kernel, dim3(1), dim3(kB), 0, c->stream, (const double *)ke, nke, pot, npot, param, scal + 4);
+	NBCO_HIP(hipGetLastError());
+	double h[3];
+	NBCO_HIP(hipMemcpyAsync(h, scal + 4, sizeof h, hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	out3_host[0] = h[0];
+	out3_host[1] = h[1];
+	out3_host[2] = h[2];
+	return NBCO_OK;
+}
+
+static int f2d_energy(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!buf || !param || !out3_host || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy: bad arguments");
+	const long long nb = (n + kB - 1) / kB;
+	if (nb > (1LL << 31) - 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy: n too large");
+	double *scal, *ke, *pot;
+	NBCO_TRY(f2d_energy_part(c, nb, &scal, &ke, &pot));
+	hipLaunchKernelGGL(f2d_pair_pot_kernel, dim3((unsigned)nb), dim3(kB), 0, c->stream, (const double2 *)buf, n, (double)c->o.eps2, param, phi_dev, pot);
+	return f2d_energy_finish(c, buf, n, param, scal, ke, pot, nb, out3_host);
+}
+
+// the tree of f2d_fmm_run over a scratch copy of the positions (same level formula, keys, stable sort, centroids and multipoles),
+// then the field's M2L / L2L with the constant's next to them, and the near-field potential.  buf is only read.
+static int f2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!buf || !param || !out3_host || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy_fmm: bad arguments");
+	NBCO_TRY(f2d_fmm_check(c, n));
+	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
+		return c->fail(NBCO_ERR_ARG, "nbco_2d_energy_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
+	const int P = c->o.fmm_order;
+	const int L = f2d_levels(c->o, n);
+	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy_fmm: tree_L must be 0 or 2..15");
+	const int radius = (int)c->o.tree_radius;
+	const double eps2 = (double)c->o.eps2;
+	const int side = 1 << L, m = side * side;
+	const long long ntot = quad_beg(L + 1);
+	hipStream_t st = c->stream;
+
+	// scratch as in f2d_fmm_run, with the constants between the locals and the integer arrays
+	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
+	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
+	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1) + P) + sizeof(double) * (size_t)ntot + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
+	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
+	const int near_grid = std::min(1 << (2 * L), 1 << 22);
+	double *scal, *ke, *pot;
+	NBCO_TRY(f2d_energy_part(c, near_grid, &scal, &ke, &pot));
+	double *part = c->f2d_part.as<double>();
+	Quad q;
+	q.center = c->f2d_tree.as<double2>();
+	q.mpole = q.center + ntot;
+	q.local = q.mpole + ntot * (P + 1);
+	double *c0 = reinterpret_cast<double *>(q.local + ntot * P);
+	q.mult = reinterpret_cast<int *>(c0 + ntot);
+	q.index = q.mult + ntot;
+
+	const double2 *x0 = (const double2 *)buf;
+	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
+	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, x0, n, part);
+	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, n, (const double *)scal, side, keys_in, idx_in);
+	// f2d_tmp is the sort's scratch and then holds the positions in cell order
+	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * L), sizeof(double2) * (size_t)n));
+	double2 *x = c->f2d_tmp.as<double2>();
+	hipLaunchKernelGGL(f2d_gather_pos_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, (const uint32_t *)idx, x, n);
+	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
+
+	f2d_launch_leaf(c, P, q, x, m, quad_beg(L));
+	for (int l = L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
+	f2d_launch_m2l(c, P, q, L, radius, eps2);
+	f2d_launch_m2l0(c, P, q, c0, L, radius, eps2);
+	for (int l = 3; l <= L; ++l)
+	{
+		f2d_launch_l2l(c, P, q, l);
+		f2d_launch_l2l0(c, P, q, c0, l);
+	}
+	f2d_launch_near_pot(c, P, near_grid, q, c0, x, idx, L, radius, eps2, param, phi_dev, pot);
+	return f2d_energy_finish(c, buf, n, param, scal, ke, pot, near_grid, out3_host);
+}
+
 static int f2d_step(nbco_ctx *c, double *b, const double *a, long double ds, long long n)
 {
 	hipLaunchKernelGGL(f2d_axpy_kernel, dim3(grid_blocks(2 * n, kB, kGridCap)), dim3(kB), 0, c->stream, b, a, (double)ds, 2 * n);
@@ -682,6 +806,15 @@ extern "C" {
 int nbco_2d_direct(nbco_ctx *c, const double *p, double *a, long long n, const double *param) { return f2d_direct(c, p, a, n, param, false); }
 int nbco_2d_direct3(nbco_ctx *c, const double *p, double *a, long long n, const double *param) { return f2d_direct(c, p, a, n, param, true); }
 int nbco_2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param) { return f2d_fmm(c, p, a, n, param); }
+
+int nbco_2d_energy(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev)
+{
+	return f2d_energy(c, buf, n, param, out3_host, phi_dev);
+}
+int nbco_2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev)
+{
+	return f2d_energy_fmm(c, buf, n, param, out3_host, phi_dev);
+}
 
 int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)
 {

@@ -168,6 +168,8 @@ def _load():
         "nbco_2d_integrate": [P, I, I, P, LL, P, D, D, I],
         "nbco_2d_integrate_steps": [P, I, I, P, LL, P, D, D, I, I],
         "nbco_2d_mean_relerr": [P, P, P, LL, C.POINTER(D)],
+        "nbco_2d_energy": [P, P, LL, P, C.POINTER(D), P],
+        "nbco_2d_energy_fmm": [P, P, LL, P, C.POINTER(D), P],
         "nbco_2d_init_kv": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
         "nbco_2d_init_gaussian": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
     }
@@ -335,6 +337,22 @@ class Engine:
         out = C.c_double()
         self._chk(self.lib.nbco_2d_mean_relerr(self.ctx, _ptr(x), _ptr(ref), n, C.byref(out)))
         return out.value
+
+    def _energy_2d(self, fn, buf, n, param, phi):
+        import numpy as np
+        out = (C.c_double * 3)()
+        self._chk(fn(self.ctx, _ptr(buf), n, _ptr(param), out, _ptr(phi)))
+        return np.array(out[:], dtype=np.float64)
+
+    def energy_2d(self, buf, n, param, phi=None):
+        """{kinetic, elastic, coulomb} of buf = [pos n | vel n | ..] with the exact O(N^2) pair potential (nbco_2d_energy); phi: None
+        or a float64 device tensor of n elements that receives psi_i in buf's particle order.  buf is not modified."""
+        return self._energy_2d(self.lib.nbco_2d_energy, buf, n, param, phi)
+
+    def energy_fmm_2d(self, buf, n, param, phi=None):
+        """the same with the Coulomb part from an O(N) quadtree FMM potential pass of its own (nbco_2d_energy_fmm): no preceding
+        evaluation is needed, buf is neither modified nor reordered"""
+        return self._energy_2d(self.lib.nbco_2d_energy_fmm, buf, n, param, phi)
 
     # ---- reductions -----------------------------------------------------------------------------
     def minmax(self, p, n):

@@ -2,6 +2,7 @@
 // the C ABI of libnbco_hip.so.  Flags, defaults, exit codes, error strings, the initial state, args.txt and the snapshot files
 // follow main.cu:257-903; the evaluator is nbco_2d_fmm (fmm_cart) plus the elastic term, integrated by nbco_2d_integrate.
 //
+// Addition: -energy writes the energies of every snapshot to energy.txt (nbco_2d_energy_fmm); without it nothing changes.
 // Deviations: -cpu / -cpu-threads are refused (main.cu -cpu runs a host FMM, which this product does not have); -gpu, -gridsize
 // and -cacheline are validated as main.cu does and then have no effect; -p above 10 is refused by the library (NBCO_ERR_ARG).
 #include <hip/hip_runtime.h>
@@ -45,6 +46,9 @@ const char *kHelp =
     "  -ncoll            skip the near field (a is scaled by 0 there instead)\n"
     "  -test             time one evaluation, then print the mean relative error against the\n"
     "                    compensated direct sum for p = 1..10; no snapshots\n"
+    "  -energy           at every snapshot append `iter kinetic elastic coulomb total` to <dir>/energy.txt:\n"
+    "                    the O(N) FMM potential energy of the snapshot's state (nbco_2d_energy_fmm, order -p);\n"
+    "                    no effect with -test\n"
     "  -ga               Gaussian initial state instead of KV\n"
     "  -xi <v>           perveance\n"
     "  -omega0 <x> <y>   trap phase advances\n"
@@ -73,7 +77,7 @@ int main(const int argc, const char **argv)
 	int fmm_order = 5, tree_radius = 1;
 	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1;
 	std::string strout("out"), strin;
-	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true;
+	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false;
 
 	// KV parameters matched to the emittances (main.cu:271-313)
 	const double twopi = 6.283185307179586476925286766559;
@@ -173,6 +177,7 @@ int main(const int argc, const char **argv)
 		else if (is(a, "cacheline") || is(a, "gpu") || is(a, "gridsize")) rc = int_arg(dummy);
 		else if (is(a, "test")) test = true;
 		else if (is(a, "ga")) ga = true;
+		else if (is(a, "energy")) energy = true;
 		else if (is(a, "xi"))
 		{
 			if (need(i, 1, a)) return missing();
@@ -289,23 +294,40 @@ int main(const int argc, const char **argv)
 	}
 
 	// main.cu:853-893: one evaluation, then per iteration a step and every nSteps iterations a snapshot
-	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return done(-1);
+	FILE *fen = nullptr;
+	if (energy && !(fen = std::fopen((strout + "/energy.txt").c_str(), "w")))
+	{
+		std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+		return done(-1);
+	}
+	auto finish = [&](int code) {
+		if (fen) std::fclose(fen);
+		return done(code);
+	};
+	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return finish(-1);
 	for (int iter = 0; iter < nIters; ++iter)
 	{
-		if (!lib_ok(nbco_2d_integrate(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1))) return done(-1);
+		if (!lib_ok(nbco_2d_integrate(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1))) return finish(-1);
 		if (iter % nSteps == 0)
 		{
 			std::cout << iter << ' ' << std::flush;
-			if (!hip_ok(hipMemcpy(buf.data(), d_buf, cpy, hipMemcpyDeviceToHost))) return done(-1);
+			if (!hip_ok(hipMemcpy(buf.data(), d_buf, cpy, hipMemcpyDeviceToHost))) return finish(-1);
 			std::ofstream fout(strout + "/out" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)
 			{
 				std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
-				return done(-1);
+				return finish(-1);
 			}
 			fout.write(reinterpret_cast<const char *>(buf.data()), (std::streamsize)cpy);
+			if (fen)
+			{
+				double e3[3];
+				if (!lib_ok(nbco_2d_energy_fmm(ctx, d_buf, n, d_par, e3, nullptr))) return finish(-1);
+				std::fprintf(fen, "%d %.17g %.17g %.17g %.17g\n", iter, e3[0], e3[1], e3[2], e3[0] + e3[1] + e3[2]);
+				std::fflush(fen);
+			}
 		}
 	}
 	std::cout << std::endl;
-	return done(0);
+	return finish(0);
 }

@@ -445,6 +445,25 @@ int nbco_2d_integrate_steps(nbco_ctx *c, int scheme, int kind, double *buf, long
 /* reductions.cuh:99 relerrReduce2: mean over particles of sqrt(|x_i - ref_i|^2 / (|ref_i|^2 + 1e-18)) (rel_diff1, :37-42;
  * main.cu:172 test_accuracy); syncs */
 int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host);
+/* ---- 2-D energy diagnostics (no reference driver computes an energy).  The pair law above is minus the gradient of a logarithmic
+ * potential:
+ *   phi_i   = sum_{j != i} 1/2 log(|x_i - x_j|^2 + EPS2)   (j != i by INDEX, not by distance: two coincident particles contribute
+ *                                                           1/2 log EPS2 each)
+ *   psi_i   = -param[0] phi_i                              (a_i = -grad psi_i, the evaluators' Coulomb term)
+ *   kinetic = 1/2 sum |v_i|^2,  elastic = 1/2 sum (kx x_i^2 + ky y_i^2) with k = param + 2,  coulomb = 1/2 sum_i psi_i
+ * With the elastic term on, kinetic + elastic + coulomb is the Hamiltonian of the flow nbco_2d_integrate integrates.
+ * out3_host = {kinetic, elastic, coulomb} of buf = [pos n | vel n | ..]: only the first 4n doubles are read, buf is neither modified
+ * nor reordered.  phi_dev: NULL, or n doubles in DEVICE memory that receive psi_i in the caller's particle order.  Both calls
+ * synchronise, use only the 2-D scratch of the context (a valid nbco_energy_fmm stays valid), sum in a fixed order without atomics
+ * (a second call returns the same bits) and refuse bad arguments with NBCO_ERR_ARG before any launch.
+ * nbco_2d_energy: the Coulomb part from the exact all-pairs sum, O(N^2): the yardstick, and the tool for small N. */
+int nbco_2d_energy(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev);
+/* the Coulomb part from a quadtree FMM potential pass of its own, O(N): it builds the tree nbco_2d_fmm would build for these
+ * positions (level formula, keys, stable sort, centroids, multipoles) over a scratch copy, so it needs no preceding evaluation and
+ * is right after integrators that end a step on a drift.  Reads fmm_order (1..10), tree_radius, eps2, dens_inhom, tree_L and
+ * stream, refuses exactly what nbco_2d_fmm refuses, and ignores coll: the near field is always summed.  The truncation error is
+ * that of the field evaluation at the same order. */
+int nbco_2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev);
 /* main.cu:120-145 initKV and :147-170 initGA over std::mt19937_64(seed) after discard(discard) (main.cu:779-784 uses
  * NBCO_REF_SEED / NBCO_REF_DISCARD); host_state = [pos n x 2 | vel n x 2] doubles in HOST memory, centred with exactly the
  * RMS A/2, omega A/2 (KV) or x, u (Gaussian) per axis.  initKV takes each angle's sine and cosine from one glibc sincos call,

@@ -4,12 +4,17 @@
 
 Per size: W warm-up steps, then R repeats of K timed steps (HIP events around the K calls); ms_per_step is the median repeat.
 near_pairs is the near-field pair count of the final state (sum over leaves of targets x sources in the (2r+1)^2 neighbour
-cells, the self pair included), from the cell keys of main.cu's formula."""
+cells, the self pair included), from the cell keys of main.cu's formula.
+
+The energy diagnostics at the same sizes and repeats: energy_fmm_ms is the median time of one nbco_2d_energy_fmm call (it
+synchronises; wall clock around the call) and fmm_eval_ms the median of one nbco_2d_fmm evaluation of the same state (HIP events),
+energy_over_eval their ratio; energy_exact_ms is one nbco_2d_energy call, at sizes up to --exact-max only (it is O(N^2))."""
 import argparse
 import json
 import math
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -50,13 +55,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sizes", default="30001,1048576,4194304")
-    a = ap.parse_args()
+    ap.add_argument("--exact-max", type=int, default=30001)
+    args = ap.parse_args()
     import torch
     from coulomb_oscillators_amd import Engine, EVAL2D_FMM, INTEG_LEAPFROG, init2d
     A, om, xi, om0 = kv_params()
     eps2 = float(np.float32(1e-18))
     out = {"metric": "ms per leapfrog step, 2-D fp64 quadtree FMM p = 5, KV beam, 1 GPU", "cases": []}
-    for n in [int(s) for s in a.sizes.split(",")]:
+    for n in [int(s) for s in args.sizes.split(",")]:
         p = 5
         L = min(max(int(math.floor(math.log2(n / (p * math.sqrt(p))) / 2 + 0.5)), 2), 15)
         eng = Engine(fmm_order=p, tree_radius=1.0, eps2=1e-18, coll=1, dens_inhom=1.0, tree_L=0)
@@ -64,22 +70,49 @@ def main():
         buf = torch.from_numpy(np.concatenate([st.reshape(-1), np.zeros(2 * n)])).cuda()
         prm = torch.from_numpy(np.array([xi / n, 0.0, om0[0] ** 2, om0[1] ** 2])).cuda()
         eng.compute_force_2d(EVAL2D_FMM, buf, n, prm)
-        for _ in range(a.warmup):
+        for _ in range(args.warmup):
             eng.integrate_2d(INTEG_LEAPFROG, EVAL2D_FMM, buf, n, prm, 5e-4)
         reps = []
-        for _ in range(a.repeats):
+        for _ in range(args.repeats):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            for _ in range(a.steps):
+            for _ in range(args.steps):
                 eng.integrate_2d(INTEG_LEAPFROG, EVAL2D_FMM, buf, n, prm, 5e-4)
             e1.record()
             e1.synchronize()
-            reps.append(e0.elapsed_time(e1) / a.steps)
+            reps.append(e0.elapsed_time(e1) / args.steps)
+        # the energy pass and one plain evaluation, on the state the timed steps left
+        a = buf[4 * n:]
+        eng.energy_fmm_2d(buf, n, prm)
+        en_ms = []
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            energies = eng.energy_fmm_2d(buf, n, prm)
+            en_ms.append((time.perf_counter() - t0) * 1e3)
+        ev_ms = []
+        for _ in range(args.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng.fmm_2d(buf, a, n, prm)
+            e1.record()
+            e1.synchronize()
+            ev_ms.append(e0.elapsed_time(e1))
+        exact_ms = None
+        if n <= args.exact_max:
+            eng.energy_2d(buf, n, prm)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            exact = eng.energy_2d(buf, n, prm)
+            exact_ms = (time.perf_counter() - t0) * 1e3
         x = buf[:2 * n].view(n, 2).cpu().numpy()
         pairs, occupied = near_pairs(x, L, eps2)
         ms = float(np.median(reps))
         out["cases"].append({"n": n, "L": L, "ms_per_step": ms, "repeats_ms": reps, "near_pairs": pairs, "occupied_leaves": occupied,
-                             "pairs_per_occupied_leaf_target": pairs / n, "finite": bool(torch.isfinite(buf).all().item())})
+                             "pairs_per_occupied_leaf_target": pairs / n, "finite": bool(torch.isfinite(buf).all().item()),
+                             "energy_fmm_ms": float(np.median(en_ms)), "fmm_eval_ms": float(np.median(ev_ms)),
+                             "energy_over_eval": float(np.median(en_ms) / np.median(ev_ms)), "energy_exact_ms": exact_ms,
+                             "energies": [float(v) for v in energies]})
         eng.close()
     print(json.dumps(out))
 
