@@ -47,9 +47,13 @@ def test_direct_config2_size_properties(engine, oracle32):
     n = 262144
     buf = o.init_reference(n)
     par = o.params(n)
+    dup = (0, 200001)                   # one point twice, in different target blocks and lanes: the pair's r^2 is the softening alone
+    buf[0][dup[1]] = buf[0][dup[0]]
     p, prm = dev(buf[0]), dev(par)
     a = torch.empty_like(p)
     engine.direct3(p, a, n, prm)
+    assert torch.isfinite(a).all()
+    assert torch.equal(a[dup[0]].view(torch.int32), a[dup[1]].view(torch.int32))      # the same sources in the same order: the same bits
     a_h = a.cpu().numpy().astype(np.float64)
     scale = np.linalg.norm(a_h, axis=1).mean()
     assert np.abs(a_h.sum(axis=0)).max() / (n * scale) < 1e-6
@@ -61,6 +65,11 @@ def test_direct_config2_size_properties(engine, oracle32):
     want = (d / r2[..., None] ** 1.5).sum(1) * float(par[0])
     got = a_h[rows]
     assert (np.linalg.norm(got - want, axis=1) / (np.linalg.norm(want, axis=1) + scale)).max() < 1e-5
+    # and the two copies themselves, to which the pair contributes exactly zero
+    d = pos64[list(dup), None, :] - pos64[None, :, :]
+    r2 = (d ** 2).sum(-1) + 1e-18
+    want = (d / r2[..., None] ** 1.5).sum(1) * float(par[0])
+    assert (np.linalg.norm(a_h[list(dup)] - want, axis=1) / (np.linalg.norm(want, axis=1) + scale)).max() < 1e-5
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 1001, 4096, 30001])
