@@ -30,6 +30,7 @@ template <int P, typename T> __device__ __forceinline__ void l2p_body(const T (&
 {
 	FmmOps<P, T>::l2p_body(Lp, dx, dy, dz, fx, fy, fz);
 }
+template <int P, typename T> __device__ __forceinline__ T lpot_body(const T (&Lp)[NBCO_OFFL(P)], T dx, T dy, T dz) { return FmmOps<P, T>::lpot_body(Lp, dx, dy, dz); }
 // octree flavour: traceless multipoles orders 0..P (tuple of (P+1)^2 entries, dipole identically 0)
 template <int P, typename T> __device__ __forceinline__ void p2m_tl_accum(T dx, T dy, T dz, T (&A)[NBCO_OFFL(P)]) { FmmOctOps<P, T>::p2m_tl_accum(dx, dy, dz, A); }
 template <int P, typename T> __device__ __forceinline__ void m2m_tl_accum(const T *__restrict__ Mc, T dx, T dy, T dz, T (&A)[NBCO_OFFL(P)])

@@ -14,6 +14,7 @@ every operator is a coefficient-free correlation / convolution, i.e. plain v_fma
     M2M   M~'[X]   = sum_{K <= X} D~[K] M~[X-K]                  (d = new centre - old centre)
     L2L   L~'_n[X] = sum_{m >= n} sum_{|K| = m-n} D~[K] L~_m[X+K] (d = child - parent)
     L2P   a_c      = - sum_{K} D~[K] L~_{|K|+1}[e_c + K]          (d = particle - leaf centre)
+    LPOT  phi - c0 = sum_{1 <= |K| <= p} D~[K] L~_{|K|}[K]        (the potential whose gradient L2P takes; c0: its value at the centre)
 
 Arrays in HBM keep the reference's normalisation; the scale factors are literals at load / store.
 Usage: gen_ops.py <out.inc> [PMAX]
@@ -313,6 +314,20 @@ def gen(P, out):
         w("\tconst T ez%d = %s;" % (q, ez))
         ex, ey, ez = "ex%d" % q, "ey%d" % q, "ez%d" % q
     w("\tfx = -%s; fy = -%s; fz = -%s;" % (ex, ey, ez))
+    w("}")
+    # ---------------------------------------------------------------- LPOT: the potential the locals stand for, less its value at the centre
+    w("static __device__ __forceinline__ T lpot_body(const T (&Lp)[%d], T dx, T dy, T dz)" % offL)
+    w("{")
+    emit_monomials(w, P)
+    emit_expand_local(w, P, "Lp")
+    ph = None
+    for n in range(1, P + 1):
+        for (kx, ky, kz) in comps(n):
+            i = full(kx, ky, kz)
+            ph = "D%d * F%d" % (i, i) if ph is None else "nb_fma(D%d, F%d, %s)" % (i, i, ph)
+        w("\tconst T ph%d = %s;" % (n, ph))
+        ph = "ph%d" % n
+    w("\treturn %s;" % ph)
     w("}")
     w("};")
     w("")

@@ -56,6 +56,14 @@ template <int P, typename T> int l2p(const T *Lp, const T *d, T *f)
 	l2p_body<P, T>(in, d[0], d[1], d[2], f[0], f[1], f[2]);
 	return 0;
 }
+template <int P, typename T> int lpot(const T *Lp, const T *d, T *out)
+{
+	constexpr int offL = (P + 1) * (P + 1);
+	T in[offL];
+	for (int q = 0; q < offL; ++q) in[q] = Lp[q];
+	*out = lpot_body<P, T>(in, d[0], d[1], d[2]);
+	return 0;
+}
 template <int P, typename T> int p2m_tl(const T *pts, int npts, const T *c, T *A)
 {
 	T acc[NBCO_OFFL(P)] = {};
@@ -87,6 +95,7 @@ template <typename T> static int d_m2m(int order, const T *Mc, const T *d, T *Mp
 template <typename T> static int d_m2l(int order, const T *M, const T *d, T eps2, T *L) { DISPATCH(m2l, M, d, eps2, L) }
 template <typename T> static int d_l2l(int order, const T *Lp, const T *d, T *O) { DISPATCH(l2l, Lp, d, O) }
 template <typename T> static int d_l2p(int order, const T *Lp, const T *d, T *f) { DISPATCH(l2p, Lp, d, f) }
+template <typename T> static int d_lpot(int order, const T *Lp, const T *d, T *out) { DISPATCH(lpot, Lp, d, out) }
 template <typename T> static int d_p2m_tl(int order, const T *pts, int npts, const T *c, T *A) { DISPATCH(p2m_tl, pts, npts, c, A) }
 template <typename T> static int d_m2m_tl(int order, const T *Mc, const T *d, T *A) { DISPATCH(m2m_tl, Mc, d, A) }
 
@@ -104,6 +113,9 @@ int nbco_genop_l2l_f32(int order, const float *Lp, const float *d, float *O) { r
 int nbco_genop_l2l_f64(int order, const double *Lp, const double *d, double *O) { return d_l2l<double>(order, Lp, d, O); }
 int nbco_genop_l2p_f32(int order, const float *Lp, const float *d, float *f) { return d_l2p<float>(order, Lp, d, f); }
 int nbco_genop_l2p_f64(int order, const double *Lp, const double *d, double *f) { return d_l2p<double>(order, Lp, d, f); }
+// lpot: the far potential at centre + d less its value at the centre; -grad of it is what l2p returns
+int nbco_genop_lpot_f32(int order, const float *Lp, const float *d, float *out) { return d_lpot<float>(order, Lp, d, out); }
+int nbco_genop_lpot_f64(int order, const double *Lp, const double *d, double *out) { return d_lpot<double>(order, Lp, d, out); }
 // octree flavour: traceless multipoles orders 0..p as ACCUMULATORS (the kernels of k_fmm_oct.hip scale / store them)
 int nbco_genop_p2m_tl_f32(int order, const float *pts, int npts, const float *c, float *A) { return d_p2m_tl<float>(order, pts, npts, c, A); }
 int nbco_genop_p2m_tl_f64(int order, const double *pts, int npts, const double *c, double *A) { return d_p2m_tl<double>(order, pts, npts, c, A); }

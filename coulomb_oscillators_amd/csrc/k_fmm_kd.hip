@@ -619,6 +619,7 @@ static int kd_fields(nbco_ctx *c, const TreeView &tv, const float4 *pos, long lo
 		le.L = L; le.ntot = ntot; le.order = P; le.shift = shift; le.real_bytes = c->o.far_fp64 ? 8 : 4;
 		le.pos = pos; le.n = n; le.own0 = own0; le.own_n = own_n;
 		le.have_p2p = c->o.coll != 0;
+		le.local = tv.local; le.unsort = unsort; le.scatter = c->o.unsort != 0; le.sharded = tv.center != c->kd.center;
 	}
 	if (mutual && 2LL * h[0] + nself > react_cap) out.react_overflow = 1;   // the pair list outgrew the reaction records: same evaluation again, sized from h[0]
 	return NBCO_OK;
@@ -651,6 +652,7 @@ static int kd_finish_order(nbco_ctx *c, float *p, long long n, KdStepLink *link)
 }
 
 #include "kd_energy_kernels.hpp"   // FMM potential energy: multipole-to-particle potential and the per-particle pass
+#include "kd_potential_kernels.hpp"   // O(N) potential pass over the locals: per-node c0, downward, per-leaf psi, slot sum
 } // namespace
 
 // sum over the own particles of phi_i / 2 (the caller multiplies by param[0] = xi / N)
@@ -683,6 +685,46 @@ int kd_energy_fmm(nbco_ctx *c, long long n_own, double *half_phi_sum)
 	double s = 0.0;
 	for (double v : h) s += v;
 	*half_phi_sum = 0.5 * s;
+	return NBCO_OK;
+}
+
+// nbco_kd_potential: the preconditions of nbco_energy_fmm, and no sharded evaluation (its tree is pruned to the domain)
+int kd_potential_check(nbco_ctx *c, long long n)
+{
+	const nbco_ctx::LastEval &le = c->last_eval;
+	if (!le.valid || !c->tree_valid) return c->fail(NBCO_ERR_ARG, "nbco_kd_potential: no kd-tree evaluation to take the lists from");
+	if (le.sharded) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_kd_potential: the last evaluation was sharded (nbco_energy_fmm serves a domain)");
+	if (le.own_n != n || le.n != n) return c->fail(NBCO_ERR_ARG, "nbco_kd_potential: particle count differs from the last evaluation's");
+	if (le.order < 1 || le.order > kMaxOrder) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_kd_potential: order");
+	return NBCO_OK;
+}
+
+// psi_i = param[0] phi_i into psi_dev (nullptr: not wanted), in the particle order of the evaluation's caller; 1/2 sum psi_i to the host
+int kd_potential(nbco_ctx *c, long long n, const float *param, double *psi_dev, double *half_psi_sum)
+{
+	NBCO_TRY(kd_potential_check(c, n));
+	const nbco_ctx::LastEval &le = c->last_eval;
+	const int nleaf = kd_cnt(le.L);
+	NBCO_TRY(c->reserve(c->pot_c0, sizeof(double) * (size_t)le.ntot));
+	NBCO_TRY(c->reserve(c->pot_slot, sizeof(double) * (size_t)nleaf));
+	double *c0 = c->pot_c0.as<double>(), *slot = c->pot_slot.as<double>(), *out = c->small.as<double>() + 8;
+	switch (le.order)
+	{
+	case 1: launch_kd_psi<1>(c, c0, slot, param, psi_dev); break;
+	case 2: launch_kd_psi<2>(c, c0, slot, param, psi_dev); break;
+	case 3: launch_kd_psi<3>(c, c0, slot, param, psi_dev); break;
+	case 4: launch_kd_psi<4>(c, c0, slot, param, psi_dev); break;
+	case 5: launch_kd_psi<5>(c, c0, slot, param, psi_dev); break;
+	case 6: launch_kd_psi<6>(c, c0, slot, param, psi_dev); break;
+	case 7: launch_kd_psi<7>(c, c0, slot, param, psi_dev); break;
+	case 8: launch_kd_psi<8>(c, c0, slot, param, psi_dev); break;
+	case 9: launch_kd_psi<9>(c, c0, slot, param, psi_dev); break;
+	default: launch_kd_psi<10>(c, c0, slot, param, psi_dev); break;
+	}
+	hipLaunchKernelGGL(kd_slot_sum_kernel, dim3(1), dim3(kBlock), 0, c->stream, (const double *)slot, nleaf, out);
+	NBCO_HIP(hipGetLastError());
+	NBCO_HIP(hipMemcpyAsync(half_psi_sum, out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
 	return NBCO_OK;
 }
 

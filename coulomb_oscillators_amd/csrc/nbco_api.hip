@@ -210,6 +210,7 @@ int nbco_destroy(nbco_ctx *c)
 		fprintf(stderr, "[nbco] nbco_integrate: %lld calls, %.1f us host time per call, of which %.1f us waiting for the traversal flags\n", c->host_calls,
 		        1e6 * c->host_call_s / c->host_calls, 1e6 * c->host_wait_s / c->host_calls);
 	if (!c) return NBCO_OK;
+	if (c->energy_child) { nbco_destroy(c->energy_child); c->energy_child = nullptr; }
 	hipStreamSynchronize(c->stream);
 	if (c->aux && !c->aux_is_main) { hipStreamSynchronize(c->aux); hipStreamDestroy(c->aux); }
 	if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -679,6 +680,53 @@ int nbco_energy_fmm(nbco_ctx *c, const float *buf, long long n, const float *par
 	float p0;
 	NBCO_HIP(hipMemcpy(&p0, param, sizeof(float), hipMemcpyDeviceToHost));
 	out3_host[0] = ke[0]; out3_host[1] = ke[1]; out3_host[2] = (double)p0 * half_phi;
+	return NBCO_OK;
+}
+
+// {kinetic, elastic} from buf, the Coulomb part from the potential pass over the last kd evaluation of `c`
+static int energy_from_potential(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev)
+{
+	double ke[2], half_psi = 0;
+	NBCO_TRY(launch_energy_kin_ela(c, buf, n, param, ke));
+	NBCO_TRY(kd_potential(c, n, param, phi_dev, &half_psi));
+	out3_host[0] = ke[0]; out3_host[1] = ke[1]; out3_host[2] = half_psi;
+	return NBCO_OK;
+}
+
+int nbco_kd_potential(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev)
+{
+	if (!c || !buf || !param || !out3_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_kd_potential: null pointer") : NBCO_ERR_ARG;
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_kd_potential: n must be positive");
+	NBCO_TRY(kd_potential_check(c, n));   // (before any launch)
+	return energy_from_potential(c, buf, n, param, out3_host, phi_dev);
+}
+
+int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev)
+{
+	if (!c || !buf || !param || !out3_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_energy_tree: null pointer") : NBCO_ERR_ARG;
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_energy_tree: n must be positive");
+	if (n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_energy_tree: n too large for 32-bit tree indices");
+	// Everything runs on a private context: this one's tree, lists, schedule and bookkeeping are not touched.  The child follows
+	// this context's expansion and tree options (re-read here) and always rebuilds, in the caller's particle order.
+	nbco_opts o = c->o;
+	o.unsort = 1; o.tree_steps = 1; o.track_order = 0; o.p2p_mutual = 0; o.coll = 1; o.sync = 0;
+	if (!c->energy_child)
+	{
+		const int rc = nbco_create(&c->energy_child, &o);
+		if (rc != NBCO_OK) return c->fail(rc, "nbco_energy_tree: could not create the private context");
+	}
+	nbco_ctx *k = c->energy_child;
+	auto pass = [&]() -> int {
+		NBCO_TRY(nbco_set_opts(k, &o));
+		// scratch copy of the positions + room for the accelerations the evaluation writes
+		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 6 * (size_t)n));
+		float *x = k->pot_xa.as<float>(), *a = x + 3 * n;
+		NBCO_HIP_M(k, hipMemcpyAsync(x, buf, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
+		NBCO_TRY(fmm_kdtree_eval(k, x, a, n, param));
+		return energy_from_potential(k, buf, n, param, out3_host, phi_dev);
+	};
+	const int rc = pass();
+	if (rc != NBCO_OK) return c->fail(rc, "nbco_energy_tree: " + k->err);
 	return NBCO_OK;
 }
 

@@ -285,7 +285,15 @@ struct nbco_ctx
 		const int *mult = nullptr, *index = nullptr;
 		int L = 0, ntot = 0, order = 0, shift = 0, real_bytes = 4;   // real_bytes: element size of mpole (8 after an evaluation with opts.far_fp64)
 		long long n = 0, own0 = 0, own_n = 0;
+		// for nbco_kd_potential: the final locals (element size real_bytes), the map back to the caller's order (used when scatter),
+		// and whether the tree is the assembled global tree of a sharded evaluation
+		const void *local = nullptr;
+		const int *unsort = nullptr;
+		bool scatter = false, sharded = false;
 	} last_eval;
+	DevBuf pot_c0, pot_slot;           // nbco_kd_potential: the far potential at the node centres, the per-leaf sums
+	DevBuf pot_xa;                     // nbco_energy_tree (on the private context): scratch copy of the positions + the accelerations of its evaluation
+	nbco_ctx *energy_child = nullptr;   // nbco_energy_tree: a private context for the tree it builds (created on first use, freed by nbco_destroy)
 	// bookkeeping of the last evaluation
 	nbco_kd_info info{};
 	long long eval_counter = 0;
@@ -352,6 +360,8 @@ int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *p
 int kd_copy_out(nbco_ctx *c, int which, void *host_dst, long long host_bytes);
 int kd_count_pairs(nbco_ctx *c, long long *out);
 int kd_energy_fmm(nbco_ctx *c, long long n_own, double *half_phi_sum);
+int kd_potential_check(nbco_ctx *c, long long n);
+int kd_potential(nbco_ctx *c, long long n, const float *param, double *psi_dev, double *half_psi_sum);
 int launch_energy_kin_ela(nbco_ctx *c, const float *buf, long long n, const float *param, double *out2_host);
 // k_fmm_oct.hip
 int fmm_oct_traceless_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, bool symmetric = false, int world = 1, int rank = 0,

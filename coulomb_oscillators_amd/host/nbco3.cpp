@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <cstdio>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -59,9 +60,26 @@ const char *kHelp =
     "  -xi <v>, -omega0 <wx> <wy>, -x <sx> <sy> <sz>, -u <ux> <uy> <uz>   physical parameters.\n"
     "  -snapshot-order <tree|input>   order of the particles in the snapshots: tree (default, as the reference: the order the\n"
     "                    last tree rebuild left them in) or input (every particle keeps the row it had in the initial state).\n"
+    "  -energy           At every snapshot append 'iter kinetic elastic coulomb total' to <output>/energy.txt: the Coulomb part from an\n"
+    "                    O(N) kd-tree potential pass of its own at the run's -p, -r and -eps (with -cpu: the exact fp64 pair sum).\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -cpu              Run the simulation on the host: compensated direct sum O(N^2) over C++20 threads (small N; the test and\n"
     "                    tuning modes need the GPU).  -cpu-threads <n> sets the number of threads (default 8); -cacheline <n> is\n"
     "                    accepted and ignored.\n";
+
+// <folder>/energy.txt of -energy: emptied when the run starts, one line per snapshot
+struct EnergyLog
+{
+	std::ofstream out;
+	EnergyLog(bool on, const std::string &folder) { if (on) out.open(folder + "/energy.txt", std::ios::out | std::ios::trunc); }
+	void line(int iter, const double (&e)[3])
+	{
+		if (!out.is_open()) return;
+		char buf[160];
+		std::snprintf(buf, sizeof buf, "%d %.17g %.17g %.17g %.17g\n", iter, e[0], e[1], e[2], e[0] + e[1] + e[2]);
+		out << buf << std::flush;
+	}
+};
 
 // device allocation that frees itself
 template <class T> struct DeviceArray
@@ -188,8 +206,10 @@ struct Session
 
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
-	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order)
+	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
+	             bool energy)
 	{
+		EnergyLog elog(energy, folder);
 		change([&](nbco_opts &c) { c.unsort = 0; c.sync = 0; c.track_order = input_order ? 1 : 0; });
 		std::vector<int> order(input_order ? (size_t)n : 0);
 		std::vector<float> rows(input_order ? host.size() : 0);
@@ -236,6 +256,13 @@ struct Session
 				fout.write(reinterpret_cast<const char *>(rows.data()), (std::streamsize)state_bytes);
 			}
 			else fout.write(reinterpret_cast<const char *>(host.data()), (std::streamsize)state_bytes);
+			if (energy)
+			{
+				// a tree of its own on a private context: the run's tree, rebuild schedule and state are not touched
+				double e3[3];
+				check(nbco_energy_tree(ctx(), state.ptr, n, par.ptr, e3, nullptr), "energy_tree");
+				elog.line(snap, e3);
+			}
 			if (snap == 0) { loop_t0 = std::chrono::steady_clock::now(); loop_first = 1; }   // the timer below starts behind the first snapshot
 		}
 		check(nbco_sync(ctx()), "sync");
@@ -261,7 +288,7 @@ int main(int argc, const char **argv)
 	SCAL dt = (SCAL)5.e-4;
 	int nIters = 30001, nSteps = 200;
 	std::string strout("out"), strin;
-	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false;
+	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
 	SCAL xi = (SCAL)2.e-6;
@@ -370,6 +397,7 @@ int main(int argc, const char **argv)
 			++i;
 		}
 		else if (a == "-cpu") cpu = true;
+		else if (a == "-energy") energy = true;
 		else if (a == "-cpu-threads")
 		{
 			if (!need(i, 1, "-cpu-threads")) return -1;
@@ -467,6 +495,7 @@ int main(int argc, const char **argv)
 		const nbco_cpu::Scheme sch = scheme == NBCO_INTEG_EULER ? nbco_cpu::Euler : scheme == NBCO_INTEG_FORESTRUTH ? nbco_cpu::ForestRuth
 		                             : scheme == NBCO_INTEG_PEFRL ? nbco_cpu::Pefrl : nbco_cpu::Leapfrog;
 		nbco_cpu::force(st.data(), nBodies, par, o.eps2);
+		EnergyLog elog(energy, strout);
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt);
@@ -479,6 +508,12 @@ int main(int argc, const char **argv)
 				return -1;
 			}
 			fout.write(reinterpret_cast<const char *>(st.data()), (std::streamsize)state_bytes);
+			if (energy)
+			{
+				double e3[3];
+				nbco_cpu::energy(st.data(), nBodies, par, o.eps2, e3);
+				elog.line(iter, e3);
+			}
 		}
 		std::cout << std::endl;
 		return 0;
@@ -491,7 +526,7 @@ int main(int argc, const char **argv)
 	{
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
-		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order);
+		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy);
 	}
 	return rc;
 }

@@ -77,6 +77,36 @@ inline void force(V3 *buf, int n, const float *par, float eps2)
 	add_elastic(buf, buf + 2 * (size_t)n, n, par + 3);
 }
 
+// {kinetic, elastic, coulomb} of buf = [pos | vel | ..] in fp64 over the fp32 state (`nbco3 -cpu -energy`): the exact pair sum
+// sum_{i < j} (|x_i - x_j|^2 + eps2)^(-1/2) par[0] -- the self pair is excluded by index, eps2 is widened from float -- with one
+// partial sum per worker, added in worker order
+inline void energy(const V3 *buf, int n, const float *par, float eps2, double (&out3)[3])
+{
+	const V3 *x = buf, *v = buf + n;
+	double ke = 0, pe = 0;
+	for (int i = 0; i < n; ++i)
+	{
+		ke += 0.5 * ((double)v[i].x * v[i].x + (double)v[i].y * v[i].y + (double)v[i].z * v[i].z);
+		pe += 0.5 * ((double)par[3] * x[i].x * x[i].x + (double)par[4] * x[i].y * x[i].y + (double)par[5] * x[i].z * x[i].z);
+	}
+	const int workers = std::max(1, std::min(threads(), n)), per = (n - 1) / workers + 1;
+	std::vector<double> part((size_t)workers, 0.0);
+	double *pp = part.data();
+	for_ranges(n, [=](int lo, int hi) {
+		double s = 0;
+		for (int i = lo; i < hi; ++i)
+			for (int j = i + 1; j < n; ++j)
+			{
+				const double dx = (double)x[i].x - x[j].x, dy = (double)x[i].y - x[j].y, dz = (double)x[i].z - x[j].z;
+				s += 1.0 / std::sqrt(dx * dx + dy * dy + dz * dz + (double)eps2);
+			}
+		pp[lo / per] = s;
+	});
+	double ce = 0;
+	for (double s : part) ce += s;
+	out3[0] = ke; out3[1] = pe; out3[2] = ce * (double)par[0];
+}
+
 // one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call)
 enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
 inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt)

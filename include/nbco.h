@@ -170,6 +170,26 @@ int nbco_energy(nbco_ctx *c, const float *buf, long long n, const float *param, 
  * (nbco_fmm_traceless, nbco_fmm_symmetric, nbco_fmm_oct_shard) reuse its position and list scratch, and after any of them this
  * call is refused with NBCO_ERR_ARG until nbco_fmm_kdtree has run again. */
 int nbco_energy_fmm(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host);
+/* The Coulomb part from the LOCAL expansions instead: psi_i = param[0] (near_i + c0[leaf] + sum_{1 <= |K| <= p} d^K / K! F[K]), with F
+ * the leaf's final locals, d = x_i - c_leaf, c0 the far potential at the leaf centre (the node's M2L sources evaluated at its centre,
+ * carried down the tree through the parents' locals) and near_i the fp64 pair sum over the leaf's P2P list (j != i by index;
+ * skipped after an evaluation with coll = 0).  Inside a leaf -grad of it is the far-field force the evaluation applied, to
+ * rounding.  One pass per node plus one per leaf, O(N); fp64, no atomics, fixed summation order (a second call returns the same
+ * bits).  out3_host = {kinetic, elastic, coulomb}, coulomb = 1/2 sum psi_i.  phi_dev: NULL, or n doubles in DEVICE memory that
+ * receive psi_i in the particle order of buf (through the kd unsort map after an unsort = 1 evaluation; after unsort = 0 buf is
+ * in tree order).  Both calls synchronise and refuse bad arguments with NBCO_ERR_ARG before any launch.
+ * nbco_kd_potential: on the lists, multipoles and locals of the LAST nbco_fmm_kdtree evaluation, under the preconditions of
+ * nbco_energy_fmm (that evaluation was the context's last evaluator call, at the positions in buf, with this n; far_fp64,
+ * m2l_first, p2p_mutual and a reused tree are all fine).  After a sharded (nbco_dist_*) evaluation: NBCO_ERR_UNSUPPORTED --
+ * nbco_energy_fmm stays the tool there. */
+int nbco_kd_potential(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev);
+/* Self-contained: valid in any state of the context (after direct or octree evaluators, 2-D calls, or a drift -- Forest-Ruth and
+ * PEFRL end a step on one), buf is neither modified nor reordered.  A private child context (created on first use, freed by
+ * nbco_destroy) gets a scratch copy of the positions and one rebuild evaluation (unsort = 1, tree_steps = 1, track_order = 0,
+ * p2p_mutual = 0, coll = 1, on this context's stream) at this context's fmm_order, tree_radius, eps2, dens_inhom, tree_L, far_fp64,
+ * m2l_first, list_factor and list_grow (re-read on every call), then the potential pass.  This context's tree, rebuild schedule,
+ * warm-select history, order tracking, nbco_kd_get_info and a valid nbco_energy_fmm are left exactly as they were. */
+int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev);
 
 /* ---- introspection of the last kd-tree evaluation (parity tests, benchmarks) ----------------- */
 typedef struct nbco_kd_info {
