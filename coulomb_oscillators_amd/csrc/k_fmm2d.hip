@@ -19,6 +19,9 @@
 //
 // Energy diagnostics (f2d_energy_kernels.hpp): nbco_2d_energy sums the pair potential exactly; nbco_2d_energy_fmm builds the same
 // tree over a scratch copy of the positions and carries one real constant per cell next to the field's locals.
+//
+// Probes (f2d_probe_kernels.hpp): nbco_2d_probe sums field and potential of the sources at arbitrary points exactly;
+// nbco_2d_probe_fmm builds that tree up to the multipoles and evaluates them at the probes, leaf by leaf in the probes' key order.
 #include "nbco_internal.hpp"
 #include "host_util.hpp"
 #include <algorithm>
@@ -506,6 +509,7 @@ __global__ __launch_bounds__(kNear) void f2d_near_kernel(Quad q, const double2 *
 }
 
 #include "f2d_energy_kernels.hpp"
+#include "f2d_probe_kernels.hpp"
 
 } // namespace
 
@@ -753,6 +757,104 @@ static int f2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const dou
 	return f2d_energy_finish(c, buf, n, param, scal, ke, pot, near_grid, out3_host);
 }
 
+// ---- probes ------------------------------------------------------------------------------------------------------------------
+static int f2d_probe_args(nbco_ctx *c, const char *who, const double *p, long long n, const double *t, long long m, const double *param,
+                          const double *a, const double *psi)
+{
+	if (!p || !t || !param || n <= 0 || m <= 0 || (!a && !psi)) return c->fail(NBCO_ERR_ARG, std::string(who) + ": bad arguments");
+	if (n >= (1LL << 31) || m >= (1LL << 31)) return c->fail(NBCO_ERR_ARG, std::string(who) + ": n and m must be below 2^31");
+	return NBCO_OK;
+}
+
+// f(std::bool_constant<WANT_A>, std::bool_constant<WANT_PSI>) for the outputs that are given: an output that is NULL costs nothing
+template <class F>
+static void with_outputs(const double *a, const double *psi, F &&f)
+{
+	if (a && psi) f(std::true_type{}, std::true_type{});
+	else if (a) f(std::true_type{}, std::false_type{});
+	else f(std::false_type{}, std::true_type{});
+}
+
+static int f2d_probe(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a, double *psi)
+{
+	if (!c) return NBCO_ERR_ARG;
+	NBCO_TRY(f2d_probe_args(c, "nbco_2d_probe", p, n, t, m, param, a, psi));
+	const unsigned nb = (unsigned)((m + kB - 1) / kB);
+	with_outputs(a, psi, [&](auto wa, auto wp) {
+		hipLaunchKernelGGL((f2d_probe_direct_kernel<decltype(wa)::value, decltype(wp)::value>), dim3(nb), dim3(kB), 0, c->stream, (const double2 *)p, n,
+		                   (const double2 *)t, m, (double)c->o.eps2, param, (double2 *)a, psi);
+	});
+	return f2d_done(c);
+}
+
+static void f2d_launch_probe(nbco_ctx *c, int P, const Quad &q, const int *pindex, const uint32_t *pidx, const double2 *x, const double2 *t, int L,
+                             int radius, double eps2, const double *param, double *a, double *psi)
+{
+	const int grid = std::min(1 << (2 * L), 1 << 22);
+	with_order(P, [&](auto p) {
+		with_outputs(a, psi, [&](auto wa, auto wp) {
+			hipLaunchKernelGGL((f2d_probe_kernel<decltype(p)::value, decltype(wa)::value, decltype(wp)::value>), dim3(grid), dim3(kNear), 0, c->stream,
+			                   (const double2 *)q.center, (const double2 *)q.mpole, (const int *)q.mult, (const int *)q.index, pindex, pidx, x, t, L,
+			                   radius, eps2, param, (double2 *)a, psi);
+		});
+	});
+}
+
+// the tree of f2d_energy_fmm over a scratch copy of p, up to the M2M chain; then the probes keyed with the sources' scalars, sorted,
+// indexed by leaf, and summed leaf by leaf.  p and t are only read.
+static int f2d_probe_fmm(nbco_ctx *c, const double *p, long long n, const double *t, long long mp, const double *param, double *a, double *psi)
+{
+	if (!c) return NBCO_ERR_ARG;
+	NBCO_TRY(f2d_probe_args(c, "nbco_2d_probe_fmm", p, n, t, mp, param, a, psi));
+	NBCO_TRY(f2d_fmm_check(c, n));
+	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
+		return c->fail(NBCO_ERR_ARG, "nbco_2d_probe_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
+	const int P = c->o.fmm_order;
+	const int L = f2d_levels(c->o, n);
+	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_probe_fmm: tree_L must be 0 or 2..15");
+	const int radius = (int)c->o.tree_radius;
+	const double eps2 = (double)c->o.eps2;
+	const int side = 1 << L, m = side * side;
+	const long long ntot = quad_beg(L + 1);
+	hipStream_t st = c->stream;
+
+	// scratch: the sources' as in f2d_energy_fmm, without locals; the probes' keys in / out, indices in / out and leaf index
+	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
+	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
+	NBCO_TRY(c->reserve(c->f2d_pkeys, sizeof(uint32_t) * 4 * (size_t)mp + sizeof(int) * ((size_t)m + 1)));
+	uint32_t *pkeys_in = c->f2d_pkeys.as<uint32_t>(), *pkeys = pkeys_in + mp, *pidx_in = pkeys + mp, *pidx = pidx_in + mp;
+	int *pindex = reinterpret_cast<int *>(pidx + mp);
+	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1)) + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
+	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
+	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
+	Quad q;
+	q.center = c->f2d_tree.as<double2>();
+	q.mpole = q.center + ntot;
+	q.local = nullptr;
+	q.mult = reinterpret_cast<int *>(q.mpole + ntot * (P + 1));
+	q.index = q.mult + ntot;
+	double *part = c->f2d_part.as<double>(), *scal = part + 4 * kRedBlocks;
+
+	const double2 *x0 = (const double2 *)p, *t0 = (const double2 *)t;
+	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
+	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, x0, n, part);
+	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, n, (const double *)scal, side, keys_in, idx_in);
+	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * L), sizeof(double2) * (size_t)n));
+	double2 *x = c->f2d_tmp.as<double2>();
+	hipLaunchKernelGGL(f2d_gather_pos_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, (const uint32_t *)idx, x, n);
+	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
+	f2d_launch_leaf(c, P, q, x, m, quad_beg(L));
+	for (int l = L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
+
+	// the clamp of f2d_keys_kernel projects a probe outside the sources' square onto it
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(mp, kB, kGridCap)), dim3(kB), 0, st, t0, mp, (const double *)scal, side, pkeys_in, pidx_in);
+	NBCO_TRY(sort_pairs(c, c->f2d_ptmp, pkeys_in, pkeys, pidx_in, pidx, mp, 0u, (unsigned)(2 * L)));
+	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)pkeys, mp, m, pindex);
+	f2d_launch_probe(c, P, q, pindex, pidx, x, t0, L, radius, eps2, param, a, psi);
+	return f2d_done(c);
+}
+
 static int f2d_step(nbco_ctx *c, double *b, const double *a, long double ds, long long n)
 {
 	hipLaunchKernelGGL(f2d_axpy_kernel, dim3(grid_blocks(2 * n, kB, kGridCap)), dim3(kB), 0, c->stream, b, a, (double)ds, 2 * n);
@@ -814,6 +916,15 @@ int nbco_2d_energy(nbco_ctx *c, const double *buf, long long n, const double *pa
 int nbco_2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev)
 {
 	return f2d_energy_fmm(c, buf, n, param, out3_host, phi_dev);
+}
+
+int nbco_2d_probe(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a_dev, double *psi_dev)
+{
+	return f2d_probe(c, p, n, t, m, param, a_dev, psi_dev);
+}
+int nbco_2d_probe_fmm(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a_dev, double *psi_dev)
+{
+	return f2d_probe_fmm(c, p, n, t, m, param, a_dev, psi_dev);
 }
 
 int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)

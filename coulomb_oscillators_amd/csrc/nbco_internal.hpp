@@ -199,6 +199,8 @@ struct nbco_ctx
 	DevBuf oct_tree, oct_groups;
 	// 2-D fp64 evaluators (k_fmm2d.hip): quadtree arrays, keys / permutation, gather scratch, reduction partials
 	DevBuf f2d_tree, f2d_keys, f2d_tmp, f2d_part;
+	// probe calls: the probes' keys / permutation / leaf index, and their sort's scratch (f2d_tmp holds the sources meanwhile)
+	DevBuf f2d_pkeys, f2d_ptmp;
 	OctTreeDev oct;
 	struct DistState
 	{

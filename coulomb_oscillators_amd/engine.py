@@ -172,6 +172,8 @@ def _load():
         "nbco_2d_mean_relerr": [P, P, P, LL, C.POINTER(D)],
         "nbco_2d_energy": [P, P, LL, P, C.POINTER(D), P],
         "nbco_2d_energy_fmm": [P, P, LL, P, C.POINTER(D), P],
+        "nbco_2d_probe": [P, P, LL, P, LL, P, P, P],
+        "nbco_2d_probe_fmm": [P, P, LL, P, LL, P, P, P],
         "nbco_2d_init_kv": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
         "nbco_2d_init_gaussian": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
     }
@@ -375,6 +377,16 @@ class Engine:
         """the same with the Coulomb part from an O(N) quadtree FMM potential pass of its own (nbco_2d_energy_fmm): no preceding
         evaluation is needed, buf is neither modified nor reordered"""
         return self._energy_2d(self.lib.nbco_2d_energy_fmm, buf, n, param, phi)
+
+    def probe_2d(self, p, n, t, m, param, a=None, psi=None):
+        """field and potential of the n sources p at the m probes t, exact O(n m) sums (nbco_2d_probe): a receives m xy pairs, psi m
+        values, float64 device tensors in the probes' order; either may be None, not both.  Every source counts (no self exclusion),
+        t may be p, and neither is modified."""
+        self._chk(self.lib.nbco_2d_probe(self.ctx, _ptr(p), n, _ptr(t), m, _ptr(param), _ptr(a), _ptr(psi)))
+
+    def probe_fmm_2d(self, p, n, t, m, param, a=None, psi=None):
+        """the same from the quadtree nbco_2d_fmm would build for p, the multipoles evaluated at the probes (nbco_2d_probe_fmm)"""
+        self._chk(self.lib.nbco_2d_probe_fmm(self.ctx, _ptr(p), n, _ptr(t), m, _ptr(param), _ptr(a), _ptr(psi)))
 
     # ---- reductions -----------------------------------------------------------------------------
     def minmax(self, p, n):

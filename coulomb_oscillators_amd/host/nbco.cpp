@@ -2,7 +2,8 @@
 // the C ABI of libnbco_hip.so.  Flags, defaults, exit codes, error strings, the initial state, args.txt and the snapshot files
 // follow main.cu:257-903; the evaluator is nbco_2d_fmm (fmm_cart) plus the elastic term, integrated by nbco_2d_integrate.
 //
-// Addition: -energy writes the energies of every snapshot to energy.txt (nbco_2d_energy_fmm); without it nothing changes.
+// Additions: -energy writes the energies of every snapshot to energy.txt (nbco_2d_energy_fmm); -probes <file> writes the field and
+// the potential at the file's points for every snapshot (nbco_2d_probe_fmm); without them nothing changes.
 // Deviations: -cpu / -cpu-threads are refused (main.cu -cpu runs a host FMM, which this product does not have); -gpu, -gridsize
 // and -cacheline are validated as main.cu does and then have no effect; -p above 10 is refused by the library (NBCO_ERR_ARG).
 #include <hip/hip_runtime.h>
@@ -49,6 +50,10 @@ const char *kHelp =
     "  -energy           at every snapshot append `iter kinetic elastic coulomb total` to <dir>/energy.txt:\n"
     "                    the O(N) FMM potential energy of the snapshot's state (nbco_2d_energy_fmm, order -p);\n"
     "                    no effect with -test\n"
+    "  -probes <file>    binary file of probe points as pairs of doubles (M = file size / 16).  At every snapshot\n"
+    "                    write <dir>/probes<iter>_<ds>.bin: the M accelerations (pairs) and then the M potentials\n"
+    "                    of the snapshot's particles at these points (nbco_2d_probe_fmm, order -p; the points feel\n"
+    "                    the beam and do not act on it); no effect with -test\n"
     "  -ga               Gaussian initial state instead of KV\n"
     "  -xi <v>           perveance\n"
     "  -omega0 <x> <y>   trap phase advances\n"
@@ -76,7 +81,7 @@ int main(const int argc, const char **argv)
 	int nBodies = 30001, nIters = 30001, nSteps = 200, integ = NBCO_INTEG_LEAPFROG;
 	int fmm_order = 5, tree_radius = 1;
 	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1;
-	std::string strout("out"), strin;
+	std::string strout("out"), strin, strprobes;
 	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false;
 
 	// KV parameters matched to the emittances (main.cu:271-313)
@@ -178,6 +183,7 @@ int main(const int argc, const char **argv)
 		else if (is(a, "test")) test = true;
 		else if (is(a, "ga")) ga = true;
 		else if (is(a, "energy")) energy = true;
+		else if (is(a, "probes")) { if (need(i, 1, a)) return missing(); strprobes = argv[++i]; }
 		else if (is(a, "xi"))
 		{
 			if (need(i, 1, a)) return missing();
@@ -197,6 +203,22 @@ int main(const int argc, const char **argv)
 	if (fmm_order > 10) return fail("Error: invalid argument to '-p': " + std::to_string(fmm_order) + " (orders above 10 are not provided)\n");
 	if (calc_omega) omega = V2{u.x / x.x, u.y / x.y};
 	else if (calc_u) u = V2{omega.x * x.x, omega.y * x.y};
+
+	std::vector<double> probes;
+	if (!strprobes.empty())
+	{
+		std::ifstream fpr(strprobes, std::ios::in | std::ios::binary);
+		if (!fpr) return fail("Error: cannot read the probes file.\n");
+		fpr.ignore(std::numeric_limits<std::streamsize>::max());
+		const long long bytes = (long long)fpr.gcount();
+		if (bytes <= 0 || bytes % 16 != 0) return fail("Error: the probes file must hold pairs of doubles (a multiple of 16 bytes, at least one pair).\n");
+		probes.assign((size_t)(bytes / 8), 0.0);
+		fpr.clear();
+		fpr.seekg(0, std::ios::beg);
+		fpr.read(reinterpret_cast<char *>(probes.data()), bytes);
+		if (fpr.gcount() != bytes) return fail("Error: cannot read the probes file.\n");
+	}
+	const long long nprobes = (long long)(probes.size() / 2);
 
 	std::vector<double> buf;
 	if (in)
@@ -246,7 +268,7 @@ int main(const int argc, const char **argv)
 	nbco_ctx *ctx = nullptr;
 	int rc = nbco_create(&ctx, &o);
 	if (rc != NBCO_OK) return fail("Error: no usable GPU context (status " + std::to_string(rc) + ")\n");
-	double *d_buf = nullptr, *d_par = nullptr;
+	double *d_buf = nullptr, *d_par = nullptr, *d_probes = nullptr, *d_pout = nullptr;   // d_pout: nprobes pairs, then nprobes potentials
 	auto hip_ok = [&](hipError_t e) {
 		if (e != hipSuccess) std::cerr << "Error: " << hipGetErrorString(e) << '\n';
 		return e == hipSuccess;
@@ -254,6 +276,8 @@ int main(const int argc, const char **argv)
 	auto done = [&](int code) {
 		if (d_buf) (void)hipFree(d_buf);
 		if (d_par) (void)hipFree(d_par);
+		if (d_probes) (void)hipFree(d_probes);
+		if (d_pout) (void)hipFree(d_pout);
 		nbco_destroy(ctx);
 		return code;
 	};
@@ -300,6 +324,17 @@ int main(const int argc, const char **argv)
 		std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
 		return done(-1);
 	}
+	std::vector<double> pout;
+	if (nprobes > 0)
+	{
+		pout.assign(3 * (size_t)nprobes, 0.0);
+		if (!hip_ok(hipMalloc(&d_probes, sizeof(double) * 2 * (size_t)nprobes)) || !hip_ok(hipMalloc(&d_pout, sizeof(double) * 3 * (size_t)nprobes)) ||
+		    !hip_ok(hipMemcpy(d_probes, probes.data(), sizeof(double) * 2 * (size_t)nprobes, hipMemcpyHostToDevice)))
+		{
+			if (fen) std::fclose(fen);
+			return done(-1);
+		}
+	}
 	auto finish = [&](int code) {
 		if (fen) std::fclose(fen);
 		return done(code);
@@ -325,6 +360,19 @@ int main(const int argc, const char **argv)
 				if (!lib_ok(nbco_2d_energy_fmm(ctx, d_buf, n, d_par, e3, nullptr))) return finish(-1);
 				std::fprintf(fen, "%d %.17g %.17g %.17g %.17g\n", iter, e3[0], e3[1], e3[2], e3[0] + e3[1] + e3[2]);
 				std::fflush(fen);
+			}
+			if (nprobes > 0)
+			{
+				if (!lib_ok(nbco_2d_probe_fmm(ctx, d_buf, n, d_probes, nprobes, d_par, d_pout, d_pout + 2 * nprobes)) ||
+				    !hip_ok(hipMemcpy(pout.data(), d_pout, sizeof(double) * pout.size(), hipMemcpyDeviceToHost)))
+					return finish(-1);
+				std::ofstream fpo(strout + "/probes" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+				if (!fpo)
+				{
+					std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+					return finish(-1);
+				}
+				fpo.write(reinterpret_cast<const char *>(pout.data()), (std::streamsize)(sizeof(double) * pout.size()));
 			}
 		}
 	}

@@ -484,6 +484,29 @@ int nbco_2d_energy(nbco_ctx *c, const double *buf, long long n, const double *pa
  * stream, refuses exactly what nbco_2d_fmm refuses, and ignores coll: the near field is always summed.  The truncation error is
  * that of the field evaluation at the same order. */
 int nbco_2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev);
+/* ---- 2-D probes: field and potential of the sources at arbitrary points (no reference driver evaluates away from the particles).
+ * All pointers except the context are DEVICE pointers.  p: n source positions as xy pairs (only the first 2n doubles are read);
+ * t: m probe positions in the same format; t == p is allowed, and neither array is modified or reordered.  a_dev receives m xy
+ * pairs and psi_dev m doubles, both in the caller's probe order; either may be NULL (not both), and an output that is NULL costs
+ * nothing.  Every source counts at every probe -- there is no self exclusion, because a probe is not a particle:
+ *   a_i   =  param[0] sum_j d / (|d|^2 + EPS2),  d = t_i - x_j
+ *   psi_i = -param[0] sum_j 1/2 log(|d|^2 + EPS2)                  (a_i = -grad psi_i; no elastic term is added)
+ * A probe on top of a source gets nothing from it in a and -param[0] 1/2 log EPS2 in psi.  So for t = p: a equals nbco_2d_direct's,
+ * and psi equals the psi_i of nbco_2d_energy minus param[0] 1/2 log EPS2.
+ * Both calls use only the 2-D scratch of the context (a valid nbco_energy_fmm stays valid), sum in a fixed order without atomics
+ * (a second call returns the same bits), return as the evaluators do (opts.sync) and refuse with NBCO_ERR_ARG before any launch,
+ * leaving the outputs as they were: a NULL p, t or param, n <= 0, m <= 0, n or m >= 2^31, both outputs NULL.
+ * nbco_2d_probe: the exact sums, O(n m): the yardstick, and the tool for small sizes. */
+int nbco_2d_probe(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a_dev,
+                  double *psi_dev);
+/* O(n + m log n): the quadtree nbco_2d_fmm would build for p (over a scratch copy, up to the multipoles; the level count comes
+ * from n, not from m), then per probe the near field of its leaf and, at every level, the multipoles of its ancestor's M2L stencil
+ * evaluated at the probe itself.  A probe outside the sources' bounding square is served through the border leaf nearest to it.
+ * Reads fmm_order (1..10), tree_radius, eps2, dens_inhom, tree_L and stream, refuses exactly what nbco_2d_fmm refuses, and
+ * ignores coll: the near field is always summed.  The truncation error is below the field evaluation's at the same order
+ * (DESIGN 7a). */
+int nbco_2d_probe_fmm(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a_dev,
+                      double *psi_dev);
 /* main.cu:120-145 initKV and :147-170 initGA over std::mt19937_64(seed) after discard(discard) (main.cu:779-784 uses
  * NBCO_REF_SEED / NBCO_REF_DISCARD); host_state = [pos n x 2 | vel n x 2] doubles in HOST memory, centred with exactly the
  * RMS A/2, omega A/2 (KV) or x, u (Gaussian) per axis.  initKV takes each angle's sine and cosine from one glibc sincos call,
