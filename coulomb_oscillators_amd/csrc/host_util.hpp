@@ -28,6 +28,16 @@ static bool with_order(int P, F &&f)
 #undef NBCO_ORDER_CASE
 }
 
+// f(std::bool_constant<WANT_A>, std::bool_constant<WANT_PSI>) for the outputs of a probe call that are given (not both are NULL): an
+// output that is NULL costs nothing, because the kernels are compiled per output set
+template <class F>
+static void with_outputs(const double *a, const double *psi, F &&f)
+{
+	if (a && psi) f(std::true_type{}, std::true_type{});
+	else if (a) f(std::true_type{}, std::false_type{});
+	else f(std::false_type{}, std::true_type{});
+}
+
 // blocks of `block` threads that cover n items, at most cap.  No lower bound: 0 for n <= 0.
 static inline int grid_blocks(long long n, int block, long long cap) { return (int)std::min<long long>((n + block - 1) / block, cap); }
 

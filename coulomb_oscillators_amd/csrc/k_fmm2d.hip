@@ -766,15 +766,6 @@ static int f2d_probe_args(nbco_ctx *c, const char *who, const double *p, long lo
 	return NBCO_OK;
 }
 
-// f(std::bool_constant<WANT_A>, std::bool_constant<WANT_PSI>) for the outputs that are given: an output that is NULL costs nothing
-template <class F>
-static void with_outputs(const double *a, const double *psi, F &&f)
-{
-	if (a && psi) f(std::true_type{}, std::true_type{});
-	else if (a) f(std::true_type{}, std::false_type{});
-	else f(std::false_type{}, std::true_type{});
-}
-
 static int f2d_probe(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a, double *psi)
 {
 	if (!c) return NBCO_ERR_ARG;

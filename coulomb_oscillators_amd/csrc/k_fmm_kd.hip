@@ -406,6 +406,22 @@ static int kd_list_room(nbco_ctx *c, int ntot, long long &capR, long long &cap)
 	return NBCO_OK;
 }
 
+// the acceptance test's table for a tree of L levels over n particles at expansion order p: a node of level l holds lo or lo + 1 particles
+static AdmTab kd_adm_table(long long n, int L, int order)
+{
+	AdmTab tab;
+	for (int l = 0; l < 32; ++l)
+	{
+		long long lo = l <= L ? (n >> l) : 0;
+		long long hi = l <= L ? ((n + (1LL << l) - 1) >> l) : 0;
+		tab.lo[l] = (int)lo;
+		const float e = 1.f / (float)(3 * order + 6);
+		tab.Mlo[l] = lo > 0 ? std::pow((float)lo / (float)n, e) : 0.f;   // fmm_cart3_kdtree.cuh:410
+		tab.Mhi[l] = hi > 0 ? std::pow((float)hi / (float)n, e) : 0.f;
+	}
+	return tab;
+}
+
 // dual tree traversal, up to and including the event behind which its counts and flags are in pinned host memory
 static int kd_traverse(nbco_ctx *c, const TreeView &tv, long long n, const Dom dm)
 {
@@ -415,16 +431,7 @@ static int kd_traverse(nbco_ctx *c, const TreeView &tv, long long n, const Dom d
 	long long capR, cap;
 	NBCO_TRY(kd_list_room(c, ntot, capR, cap));
 	PhaseScope ph(c, NBCO_PH_TRAVERSE);
-	AdmTab tab;
-	for (int l = 0; l < 32; ++l)
-	{
-		long long lo = l <= L ? (n >> l) : 0;
-		long long hi = l <= L ? ((n + (1LL << l) - 1) >> l) : 0;
-		tab.lo[l] = (int)lo;
-		const float e = 1.f / (float)(3 * c->o.fmm_order + 6);
-		tab.Mlo[l] = lo > 0 ? std::pow((float)lo / (float)n, e) : 0.f;   // fmm_cart3_kdtree.cuh:410
-		tab.Mhi[l] = hi > 0 ? std::pow((float)hi / (float)n, e) : 0.f;
-	}
+	const AdmTab tab = kd_adm_table(n, L, c->o.fmm_order);
 	int *ctr = c->counters.as<int>();
 	int2 *fa = c->frontier_a.as<int2>(), *fb = c->frontier_b.as<int2>();
 	// per-target entry counters / fill cursors of the two directed lists: [cnt_p2p | fill_p2p | cnt_m2l | fill_m2l]
@@ -615,6 +622,7 @@ static int kd_fields(nbco_ctx *c, const TreeView &tv, const float4 *pos, long lo
 	{
 		nbco_ctx::LastEval &le = c->last_eval;
 		le.valid = true;
+		c->drifted = false;
 		le.center = tv.center; le.csz = tv.csz; le.mpole = tv.mpole; le.mult = tv.mult; le.index = tv.index;
 		le.L = L; le.ntot = ntot; le.order = P; le.shift = shift; le.real_bytes = c->o.far_fp64 ? 8 : 4;
 		le.pos = pos; le.n = n; le.own0 = own0; le.own_n = own_n;
@@ -653,6 +661,7 @@ static int kd_finish_order(nbco_ctx *c, float *p, long long n, KdStepLink *link)
 
 #include "kd_energy_kernels.hpp"   // FMM potential energy: multipole-to-particle potential and the per-particle pass
 #include "kd_potential_kernels.hpp"   // O(N) potential pass over the locals: per-node c0, downward, per-leaf psi, slot sum
+#include "kd_probe_kernels.hpp"   // probes: acceptance of a node by a point, multipole to point (field + potential), exact sums, keys, the walk
 } // namespace
 
 // sum over the own particles of phi_i / 2 (the caller multiplies by param[0] = xi / N)
@@ -726,6 +735,96 @@ int kd_potential(nbco_ctx *c, long long n, const float *param, double *psi_dev, 
 	NBCO_HIP(hipMemcpyAsync(half_psi_sum, out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	NBCO_HIP(hipStreamSynchronize(c->stream));
 	return NBCO_OK;
+}
+
+// ---- probes ---------------------------------------------------------------------------------------------------------------
+int launch_probe_direct(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a, double *psi)
+{
+	const dim3 grid((unsigned)((m + kBlock - 1) / kBlock)), block(kBlock);
+	with_outputs(a, psi, [&](auto wa, auto wp) {
+		hipLaunchKernelGGL((kd_probe_direct_kernel<decltype(wa)::value, decltype(wp)::value>), grid, block, 0, c->stream, p, n, t, m, c->o.eps2, param, a, psi);
+	});
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// keys, sort and walk of m probes over the tree `s`; all scratch is the probes' own (probe_keys, probe_tmp)
+static int kd_probe_walk(nbco_ctx *c, const ProbeSrc &s, const float *t, long long m, const float *param, double *a, double *psi)
+{
+	if (s.order < 1 || s.order > kMaxOrder) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_kd_probe: order");
+	const size_t mm = ((size_t)m + 3) & ~(size_t)3;   // (four arrays of m words, each 16-byte aligned)
+	NBCO_TRY(c->reserve(c->probe_keys, sizeof(uint32_t) * 4 * mm));
+	uint32_t *keys = c->probe_keys.as<uint32_t>(), *keys_alt = keys + mm, *idx = keys + 2 * mm, *perm = keys + 3 * mm;
+	hipLaunchKernelGGL(kd_probe_keys_kernel, dim3(grid1d(m)), dim3(kBlock), 0, c->stream, t, m, s.lbound, s.rbound, keys, idx);
+	NBCO_HIP(hipGetLastError());
+	NBCO_TRY(sort_pairs(c, c->probe_tmp, keys, keys_alt, idx, perm, m, 0u, 30u));
+	// (the table belongs to the tree: its order and particle count, not the options of this moment)
+	const AdmTab tab = kd_adm_table(s.n, s.L, s.order);
+	const bool f64 = s.real_bytes == 8;
+	with_order(s.order, [&](auto pc) {
+		constexpr int P = decltype(pc)::value;
+		if (f64) launch_probe_walk_t<P, double>(c, s, tab, perm, t, m, param, a, psi);
+		else launch_probe_walk_t<P, float>(c, s, tab, perm, t, m, param, a, psi);
+	});
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// nbco_kd_probe: the preconditions of nbco_kd_potential, less the particle count (the probes bring their own)
+int kd_probe_check(nbco_ctx *c)
+{
+	const nbco_ctx::LastEval &le = c->last_eval;
+	if (!le.valid || !c->tree_valid) return c->fail(NBCO_ERR_ARG, "nbco_kd_probe: no kd-tree evaluation to take the tree from");
+	if (c->drifted) return c->fail(NBCO_ERR_ARG, "nbco_kd_probe: nbco_integrate has moved the particles since the last kd-tree evaluation");
+	if (le.sharded) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_kd_probe: the last evaluation was sharded (its tree is pruned to the domain)");
+	if (le.order < 1 || le.order > kMaxOrder) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_kd_probe: order");
+	return NBCO_OK;
+}
+
+// the walk over the tree, multipoles and tree-ordered positions of the last evaluation (the caller has run kd_probe_check); nothing of
+// that evaluation is written
+int kd_probe_last(nbco_ctx *c, const float *t, long long m, const float *param, double *a, double *psi)
+{
+	const nbco_ctx::LastEval &le = c->last_eval;
+	ProbeSrc s;
+	s.csz = le.csz; s.pos = le.pos; s.mpole = le.mpole; s.mult = le.mult; s.index = le.index;
+	s.lbound = c->kd.lbound; s.rbound = c->kd.rbound;   // (not sharded: the tree is the context's own)
+	s.L = le.L; s.ntot = le.ntot; s.order = le.order; s.real_bytes = le.real_bytes; s.n = le.n;
+	return kd_probe_walk(c, s, t, m, param, a, psi);
+}
+
+// nbco_probe_tree, on the private context: tree and multipoles over x[0..n) and the walk.  The probes need kd_build + kd_upward only,
+// and a flagged build (pivot ties, a missed warm window) is settled right behind the build, the way a kd-domain's local build settles
+// it before its exchange (kd_dist_local_build): the flag is read back, and demote_build decides how the build is repeated.
+int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long m, const float *param, double *a, double *psi)
+{
+	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
+	c->last_eval.valid = false;   // the lists of an earlier evaluation belong to another tree
+	bool rebuild = false;
+	for (;;)
+	{
+		NBCO_TRY(kd_build(c, x, n, L, KdRoot{}, rebuild, nullptr));
+		int flag = 0;
+		NBCO_HIP(hipMemcpyAsync(&flag, c->counters.as<int>() + 110, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+		NBCO_HIP(hipStreamSynchronize(c->stream));
+		if (!flag)
+		{
+			if (rebuild && c->sel_warm_used) c->note_warm_ok();
+			break;
+		}
+		if (!c->demote_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
+	}
+	NBCO_TRY(kd_upward(c));
+	NBCO_TRY(c->join_aux());
+	c->tree_valid = true;   // (the boxes in the tree arrays are this build's: the next build of the same shape may select around them)
+	c->tree_n = n;
+	c->tree_order = c->kd.order;
+	const KdTreeDev &k = c->kd;
+	ProbeSrc s;
+	s.csz = k.csz; s.pos = c->pos4.as<float4>(); s.mpole = k.mpole; s.mult = k.mult; s.index = k.index;
+	s.lbound = k.lbound; s.rbound = k.rbound;
+	s.L = k.L; s.ntot = k.ntot; s.order = k.order; s.real_bytes = k.real_bytes; s.n = n;
+	return kd_probe_walk(c, s, t, m, param, a, psi);
 }
 
 // kd_fields has returned `rc`: twice the room for the lists (the caller's arrays are untouched), or reaction records sized from the

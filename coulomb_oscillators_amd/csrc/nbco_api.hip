@@ -541,7 +541,7 @@ int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, c
 	const long long n3 = 3 * n;
 	const long double dt = dt_, scale = scale_;
 	auto K = [&](long double s) { PhaseScope ph(c, NBCO_PH_AXPY); return launch_step(c, v, a, (float)s, n3); };
-	auto D = [&](long double s) { PhaseScope ph(c, NBCO_PH_AXPY); return launch_step(c, x, v, (float)s, n3); };
+	auto D = [&](long double s) { PhaseScope ph(c, NBCO_PH_AXPY); c->drifted = true; return launch_step(c, x, v, (float)s, n3); };
 	auto F = [&]() {
 		NBCO_TRY(eval_kind(c, kind, x, a, n, param));
 		if (elastic)
@@ -728,6 +728,60 @@ int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *pa
 	const int rc = pass();
 	if (rc != NBCO_OK) return c->fail(rc, "nbco_energy_tree: " + k->err);
 	return NBCO_OK;
+}
+
+// ---- 3-D probes --------------------------------------------------------------------------------
+// what all three calls refuse before any launch (p == nullptr with need_p = false: the sources are the last evaluation's)
+static int probe_args(nbco_ctx *c, const char *who, bool need_p, const float *p, long long n, const float *t, long long m, const float *param,
+                      const double *a_dev, const double *psi_dev)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if ((need_p && !p) || !t || !param) return c->fail(NBCO_ERR_ARG, std::string(who) + ": null pointer");
+	if ((need_p && n <= 0) || m <= 0) return c->fail(NBCO_ERR_ARG, std::string(who) + ": n and m must be positive");
+	if (!a_dev && !psi_dev) return c->fail(NBCO_ERR_ARG, std::string(who) + ": both outputs are NULL");
+	if (m >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, std::string(who) + ": m too large for 32-bit probe indices");
+	if (need_p && n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, std::string(who) + ": n too large for 32-bit tree indices");
+	return NBCO_OK;
+}
+
+int nbco_probe(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a_dev, double *psi_dev)
+{
+	NBCO_TRY(probe_args(c, "nbco_probe", true, p, n, t, m, param, a_dev, psi_dev));
+	NBCO_TRY(launch_probe_direct(c, p, n, t, m, param, a_dev, psi_dev));
+	return maybe_sync(c);
+}
+
+int nbco_kd_probe(nbco_ctx *c, const float *t, long long m, const float *param, double *a_dev, double *psi_dev)
+{
+	NBCO_TRY(probe_args(c, "nbco_kd_probe", false, nullptr, 0, t, m, param, a_dev, psi_dev));
+	NBCO_TRY(kd_probe_check(c));   // (before any launch)
+	NBCO_TRY(kd_probe_last(c, t, m, param, a_dev, psi_dev));
+	return maybe_sync(c);
+}
+
+int nbco_probe_tree(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a_dev, double *psi_dev)
+{
+	NBCO_TRY(probe_args(c, "nbco_probe_tree", true, p, n, t, m, param, a_dev, psi_dev));
+	// nbco_energy_tree's private context (this one's tree, lists, schedule and bookkeeping are not touched), under this context's
+	// expansion and tree options, re-read here; it always rebuilds, in the caller's particle order
+	nbco_opts o = c->o;
+	o.unsort = 1; o.tree_steps = 1; o.track_order = 0; o.p2p_mutual = 0; o.coll = 1; o.sync = 0;
+	if (!c->energy_child)
+	{
+		const int rc = nbco_create(&c->energy_child, &o);
+		if (rc != NBCO_OK) return c->fail(rc, "nbco_probe_tree: could not create the private context");
+	}
+	nbco_ctx *k = c->energy_child;
+	auto pass = [&]() -> int {
+		NBCO_TRY(nbco_set_opts(k, &o));
+		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
+		float *x = k->pot_xa.as<float>();
+		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
+		return kd_probe_tree(k, x, n, t, m, param, a_dev, psi_dev);
+	};
+	const int rc = pass();
+	if (rc != NBCO_OK) return c->fail(rc, "nbco_probe_tree: " + k->err);
+	return maybe_sync(c);
 }
 
 // ---- introspection -----------------------------------------------------------------------------

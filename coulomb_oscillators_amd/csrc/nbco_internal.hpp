@@ -295,7 +295,9 @@ struct nbco_ctx
 	} last_eval;
 	DevBuf pot_c0, pot_slot;           // nbco_kd_potential: the far potential at the node centres, the per-leaf sums
 	DevBuf pot_xa;                     // nbco_energy_tree (on the private context): scratch copy of the positions + the accelerations of its evaluation
-	nbco_ctx *energy_child = nullptr;   // nbco_energy_tree: a private context for the tree it builds (created on first use, freed by nbco_destroy)
+	nbco_ctx *energy_child = nullptr;   // nbco_energy_tree, nbco_probe_tree: a private context for the tree they build (created on first use, freed by nbco_destroy)
+	bool drifted = false;               // nbco_integrate has moved the particles since the last kd-tree evaluation (a scheme that ends on a drift): nbco_kd_probe refuses
+	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
 	// bookkeeping of the last evaluation
 	nbco_kd_info info{};
 	long long eval_counter = 0;
@@ -365,6 +367,10 @@ int kd_energy_fmm(nbco_ctx *c, long long n_own, double *half_phi_sum);
 int kd_potential_check(nbco_ctx *c, long long n);
 int kd_potential(nbco_ctx *c, long long n, const float *param, double *psi_dev, double *half_psi_sum);
 int launch_energy_kin_ela(nbco_ctx *c, const float *buf, long long n, const float *param, double *out2_host);
+int launch_probe_direct(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a, double *psi);
+int kd_probe_check(nbco_ctx *c);
+int kd_probe_last(nbco_ctx *c, const float *t, long long m, const float *param, double *a, double *psi);
+int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long m, const float *param, double *a, double *psi);
 // k_fmm_oct.hip
 int fmm_oct_traceless_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, bool symmetric = false, int world = 1, int rank = 0,
                            long long *pbounds_host = nullptr);

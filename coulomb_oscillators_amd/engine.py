@@ -131,6 +131,9 @@ def _load():
         "nbco_energy_fmm": [P, P, LL, P, C.POINTER(D)],
         "nbco_kd_potential": [P, P, LL, P, C.POINTER(D), P],
         "nbco_energy_tree": [P, P, LL, P, C.POINTER(D), P],
+        "nbco_probe": [P, P, LL, P, LL, P, P, P],
+        "nbco_probe_tree": [P, P, LL, P, LL, P, P, P],
+        "nbco_kd_probe": [P, P, LL, P, P, P],
         "nbco_kd_get_info": [P, C.POINTER(KdInfo)],
         "nbco_kd_copy": [P, I, P, LL],
         "nbco_oct_get_info": [P, C.POINTER(OctInfo)],
@@ -424,6 +427,22 @@ class Engine:
         """the same from a kd-tree evaluation of its own on a private context (nbco_energy_tree): valid in any state of this engine,
         which it leaves untouched; buf is neither modified nor reordered"""
         return self._energy_2d(self.lib.nbco_energy_tree, buf, n, param, phi)
+
+    def probe(self, p, n, t, m, param, a=None, psi=None):
+        """field and potential of the n sources p at the m probes t, exact O(n m) sums (nbco_probe): p and t are float32 device tensors
+        of xyz triplets, a receives m xyz triplets, psi m values, float64 device tensors in the probes' order; either may be None, not
+        both.  Every source counts (no self exclusion), t may be p, and neither is modified."""
+        self._chk(self.lib.nbco_probe(self.ctx, _ptr(p), n, _ptr(t), m, _ptr(param), _ptr(a), _ptr(psi)))
+
+    def probe_kd(self, t, m, param, a=None, psi=None):
+        """the same from a walk over the tree and multipoles of the last kd-tree evaluation (nbco_kd_probe; the preconditions of
+        energy_fmm): accepted inner nodes by their expansions at the probe, leaves always pair by pair"""
+        self._chk(self.lib.nbco_kd_probe(self.ctx, _ptr(t), m, _ptr(param), _ptr(a), _ptr(psi)))
+
+    def probe_tree(self, p, n, t, m, param, a=None, psi=None):
+        """the same from a kd-tree of its own on a private context (nbco_probe_tree): valid in any state of this engine, which it
+        leaves untouched; p is neither modified nor reordered"""
+        self._chk(self.lib.nbco_probe_tree(self.ctx, _ptr(p), n, _ptr(t), m, _ptr(param), _ptr(a), _ptr(psi)))
 
     # ---- multi-GPU kd-domain sharding (see dist.py for the orchestration) ---------------------------
     def dist_layout(self, n_global, world, rank):

@@ -63,6 +63,10 @@ const char *kHelp =
     "  -energy           At every snapshot append 'iter kinetic elastic coulomb total' to <output>/energy.txt: the Coulomb part from an\n"
     "                    O(N) kd-tree potential pass of its own at the run's -p, -r and -eps (with -cpu: the exact fp64 pair sum).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -probes <file>    <file> holds probe points (fp32 xyz triplets, no header).  At every snapshot write the field and the potential of\n"
+    "                    the charges at these points to <output>/probes<iter>_<ds>.bin: m x 3 doubles of field, then m doubles of\n"
+    "                    potential, from a kd-tree walk of its own at the run's -p, -r and -eps (with -cpu: the exact fp64 sums).\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -cpu              Run the simulation on the host: compensated direct sum O(N^2) over C++20 threads (small N; the test and\n"
     "                    tuning modes need the GPU).  -cpu-threads <n> sets the number of threads (default 8); -cacheline <n> is\n"
     "                    accepted and ignored.\n";
@@ -80,6 +84,53 @@ struct EnergyLog
 		out << buf << std::flush;
 	}
 };
+
+// -probes: the points of <file>; false (with a message) for a file that cannot be read, is empty or holds no whole triplets
+bool read_probes(const std::string &path, std::vector<float> &pts)
+{
+	std::ifstream fin(path, std::ios::in | std::ios::binary | std::ios::ate);
+	if (!fin) { std::cerr << "Error: cannot read the probe file '" << path << "'" << std::endl; return false; }
+	const std::streamoff len = fin.tellg();
+	if (len <= 0) { std::cerr << "Error: the probe file '" << path << "' is empty" << std::endl; return false; }
+	if (len % 12 != 0) { std::cerr << "Error: the size of the probe file '" << path << "' (" << len << " bytes) is not a multiple of 12 (fp32 xyz triplets)" << std::endl; return false; }
+	pts.resize((size_t)len / sizeof(float));
+	fin.seekg(0, std::ios::beg);
+	fin.read(reinterpret_cast<char *>(pts.data()), (std::streamsize)len);
+	if (!fin) { std::cerr << "Error: cannot read the probe file '" << path << "'" << std::endl; return false; }
+	return true;
+}
+
+// <folder>/probes<iter>_<dt>.bin: out = [field m x 3 | potential m] doubles
+bool write_probes(const std::string &folder, int iter, SCAL dt, const std::vector<double> &out)
+{
+	std::ofstream f(folder + "/probes" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+	if (f) f.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)(out.size() * sizeof(double)));
+	if (!f) std::cerr << "Error: cannot write the probe file of iteration " << iter << " into \"" << folder << "\"" << std::endl;
+	return (bool)f;
+}
+
+// `nbco3 -cpu -probes`: the exact sums in fp64 over the fp32 positions, every source at every probe (no self exclusion), eps2 widened
+// from float; out = [field m x 3 | potential m]
+void cpu_probes(const nbco_cpu::V3 *x, int n, const std::vector<float> &pts, const float *par, float eps2, std::vector<double> &out)
+{
+	const int m = (int)(pts.size() / 3);
+	const float *t = pts.data();
+	double *a = out.data(), *psi = out.data() + 3 * (size_t)m;
+	const double k = (double)par[0], e = (double)eps2;
+	nbco_cpu::for_ranges(m, [=](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			double ax = 0, ay = 0, az = 0, ps = 0;
+			for (int j = 0; j < n; ++j)
+			{
+				const double dx = (double)t[3 * i] - x[j].x, dy = (double)t[3 * i + 1] - x[j].y, dz = (double)t[3 * i + 2] - x[j].z;
+				const double inv = 1.0 / std::sqrt(dx * dx + dy * dy + dz * dz + e), inv3 = inv * inv * inv;
+				ps += inv; ax += dx * inv3; ay += dy * inv3; az += dz * inv3;
+			}
+			a[3 * i] = k * ax; a[3 * i + 1] = k * ay; a[3 * i + 2] = k * az; psi[i] = k * ps;
+		}
+	});
+}
 
 // device allocation that frees itself
 template <class T> struct DeviceArray
@@ -207,9 +258,15 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy)
+	             bool energy, const std::vector<float> &probes)
 	{
 		EnergyLog elog(energy, folder);
+		// -probes: the points and their results [field m x 3 | potential m] on the device, and the host copy that goes into the files
+		const size_t m = probes.size() / 3;
+		DeviceArray<float> probes_dev(probes.size());   // (nothing is allocated without the flag)
+		DeviceArray<double> probes_out(4 * m);
+		std::vector<double> probes_host(4 * m);
+		if (m) HIPCHK(hipMemcpy(probes_dev.ptr, probes.data(), probes.size() * sizeof(float), hipMemcpyHostToDevice));
 		change([&](nbco_opts &c) { c.unsort = 0; c.sync = 0; c.track_order = input_order ? 1 : 0; });
 		std::vector<int> order(input_order ? (size_t)n : 0);
 		std::vector<float> rows(input_order ? host.size() : 0);
@@ -263,6 +320,14 @@ struct Session
 				check(nbco_energy_tree(ctx(), state.ptr, n, par.ptr, e3, nullptr), "energy_tree");
 				elog.line(snap, e3);
 			}
+			if (m)
+			{
+				// the same private context: a tree over a scratch copy of the positions, walked by the probes
+				check(nbco_probe_tree(ctx(), state.ptr, n, probes_dev.ptr, (long long)m, par.ptr, probes_out.ptr, probes_out.ptr + 3 * m), "probe_tree");
+				check(nbco_sync(ctx()), "sync");
+				HIPCHK(hipMemcpy(probes_host.data(), probes_out.ptr, probes_host.size() * sizeof(double), hipMemcpyDeviceToHost));
+				if (!write_probes(folder, snap, dt, probes_host)) return -1;
+			}
 			if (snap == 0) { loop_t0 = std::chrono::steady_clock::now(); loop_first = 1; }   // the timer below starts behind the first snapshot
 		}
 		check(nbco_sync(ctx()), "sync");
@@ -287,7 +352,8 @@ int main(int argc, const char **argv)
 	int nBodies = 30001;
 	SCAL dt = (SCAL)5.e-4;
 	int nIters = 30001, nSteps = 200;
-	std::string strout("out"), strin;
+	std::string strout("out"), strin, strprobes;
+	std::vector<float> probes;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
@@ -398,6 +464,12 @@ int main(int argc, const char **argv)
 		}
 		else if (a == "-cpu") cpu = true;
 		else if (a == "-energy") energy = true;
+		else if (a == "-probes")
+		{
+			if (!need(i, 1, "-probes")) return -1;
+			strprobes = argv[++i];
+			if (!read_probes(strprobes, probes)) return -1;
+		}
 		else if (a == "-cpu-threads")
 		{
 			if (!need(i, 1, "-cpu-threads")) return -1;
@@ -496,6 +568,7 @@ int main(int argc, const char **argv)
 		                             : scheme == NBCO_INTEG_PEFRL ? nbco_cpu::Pefrl : nbco_cpu::Leapfrog;
 		nbco_cpu::force(st.data(), nBodies, par, o.eps2);
 		EnergyLog elog(energy, strout);
+		std::vector<double> probes_out(4 * (probes.size() / 3));
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt);
@@ -514,6 +587,11 @@ int main(int argc, const char **argv)
 				nbco_cpu::energy(st.data(), nBodies, par, o.eps2, e3);
 				elog.line(iter, e3);
 			}
+			if (!probes.empty())
+			{
+				cpu_probes(st.data(), nBodies, probes, par, o.eps2, probes_out);
+				if (!write_probes(strout, iter, dt, probes_out)) return -1;
+			}
 		}
 		std::cout << std::endl;
 		return 0;
@@ -526,7 +604,7 @@ int main(int argc, const char **argv)
 	{
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
-		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy);
+		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, b_accuracy ? std::vector<float>{} : probes);
 	}
 	return rc;
 }

@@ -469,6 +469,7 @@ int main(int argc, char **argv)
 			             "  per GPU, RCCL all-gathers in between; G a power of two, N a multiple of G with at least 4096 particles per GPU.\n";
 			return 0;
 		}
+		else if (f == "-probes") { std::cerr << "Error: '-probes' is not available with kd-domain sharding (nbco_probe_tree takes one context's particles as the system): nbco3 serves it\n"; return -1; }
 		else { std::cerr << "Error: unrecognised option '" << argv[i] << "'\n"; return -1; }
 	}
 	if (const char *e = getenv("NBCO3_DIST_HANG")) a.hang_rank = atoi(e);

@@ -191,6 +191,43 @@ int nbco_kd_potential(nbco_ctx *c, const float *buf, long long n, const float *p
  * warm-select history, order tracking, nbco_kd_get_info and a valid nbco_energy_fmm are left exactly as they were. */
 int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev);
 
+/* ---- 3-D probes: field and potential of the charges at arbitrary points (no reference driver evaluates away from the particles).
+ * All pointers except the context are DEVICE pointers.  p: n source positions as fp32 xyz triplets with a 12-byte stride (the head
+ * of a state buffer works as it is); t: m probe positions in the same format; t == p is allowed, and neither array is modified or
+ * reordered.  a_dev receives m xyz triplets of DOUBLE and psi_dev m doubles, both in the caller's probe order; either may be NULL
+ * (not both), and an output that is NULL costs nothing.  Every source counts at every probe -- there is no self exclusion, because
+ * a probe is not a particle:
+ *   a_i   = param[0] sum_j d (|d|^2 + EPS2)^(-3/2),  d = t_i - x_j
+ *   psi_i = param[0] sum_j   (|d|^2 + EPS2)^(-1/2)                 (a_i = -grad psi_i; no elastic term is added)
+ * A probe on top of a source gets nothing from it in a and param[0] / sqrt(EPS2) in psi: with the default EPS2 = 1e-18 that self
+ * term is 1e9 param[0], so callers who want the potential AT THE PARTICLES take nbco_energy_tree's phi_dev (j != i by index).
+ * All arithmetic is fp64 over the widened floats; every sum has a fixed order and there are no atomics (a second call returns the
+ * same bits).  The calls return as the evaluators do (opts.sync, opts.stream) and refuse before any launch, leaving the outputs as
+ * they were: with NBCO_ERR_ARG a NULL p, t or param, n <= 0, m <= 0, both outputs NULL; with NBCO_ERR_UNSUPPORTED m >= 2^31 and an
+ * n beyond what nbco_energy_tree takes.
+ * nbco_probe: the exact sums, O(n m): the yardstick, and the tool for small sizes.  It reads p and t as they are and has no
+ * scratch, so a valid nbco_energy_fmm / nbco_kd_potential stays valid. */
+int nbco_probe(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a_dev, double *psi_dev);
+/* Self-contained tree call, valid in any state of the context: nbco_energy_tree's private child context gets a scratch copy of p,
+ * builds the kd-tree and runs the upward pass (kd_build + kd_upward only: no traversal, no lists, no fields; a flagged build is
+ * settled behind the build with the evaluator's retry policy) at this context's fmm_order, tree_radius, eps2, dens_inhom, tree_L
+ * and far_fp64 (re-read on every call), with unsort = 1, tree_steps = 1, on this context's stream; then the probes walk that tree
+ * (below).  Reading the build's flag is one host round trip per call (a stream synchronisation behind the build), also with
+ * opts.sync = 0; the walk itself is enqueued like any other call.  This context's tree, rebuild schedule, warm-select history, order tracking, nbco_kd_get_info and a valid
+ * nbco_energy_fmm are left exactly as they were.  O(n log n + m log n). */
+int nbco_probe_tree(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a_dev, double *psi_dev);
+/* The walk alone, on the tree, the multipoles and the tree-ordered positions of the LAST nbco_fmm_kdtree evaluation, under the
+ * preconditions of nbco_energy_fmm (that evaluation was the context's last evaluator call, and nbco_integrate has not ended a step on
+ * a drift since: NBCO_ERR_ARG otherwise); far_fp64,
+ * m2l_first, p2p_mutual, unsort 0 or 1 and a reused tree with stale boxes are all fine; after a sharded (nbco_dist_*) evaluation:
+ * NBCO_ERR_UNSUPPORTED.  Every probe walks the tree depth first, left child first: a node that passes the evaluator's acceptance
+ * test against the probe (as a node of size 0 and multiplicity 1; opts.tree_radius and opts.eps2 are read at call time, coll and
+ * m2l_first are ignored) contributes its multipole expansion evaluated at the probe, a leaf is never expanded and always contributes
+ * its particles pair by pair, any other node is opened.  A probe's result depends on the tree and its own position alone: the same bits in any probe set,
+ * in any order.  last_eval, the lists and the rebuild schedule are untouched: a following nbco_energy_fmm or nbco_kd_potential
+ * returns the bits it would have returned.  The truncation error is the evaluator's at the same order or below. */
+int nbco_kd_probe(nbco_ctx *c, const float *t, long long m, const float *param, double *a_dev, double *psi_dev);
+
 /* ---- introspection of the last kd-tree evaluation (parity tests, benchmarks) ----------------- */
 typedef struct nbco_kd_info {
 	int L, ntot, order, mlt_max;
