@@ -173,6 +173,8 @@ static int grid_for(long long n)
 	return (int)b;
 }
 
+#include "beam_diag_kernels.hpp"   // beam diagnostics: the two moment passes and the histogram kernel
+
 } // namespace
 
 int launch_minmax(nbco_ctx *c, const float *p3, long long n, float *out6_dev)
@@ -265,5 +267,92 @@ int launch_energy(nbco_ctx *c, const float *buf, long long n, const float *param
 	out3_host[0] = h1[0];
 	out3_host[1] = h1[1];
 	out3_host[2] = h2[2] * (double)p0;
+	return NBCO_OK;
+}
+
+// ---- beam diagnostics (beam_diag_kernels.hpp) --------------------------------------------------
+// results in c->small, in doubles from kBeamOut on: mean[6], min[6], max[6], then the central sums
+constexpr int kBeamOut = 128;
+
+template <class T, int D> static int beam_moments(nbco_ctx *c, const T *buf, long long n, nbco_moments *out_host)
+{
+	constexpr int Q = 2 * D, K = beam_central_count(D);
+	const int g = grid_for(n);
+	NBCO_TRY(c->reserve(c->part, sizeof(double) * beam_central_count(3) * kMaxBlocks));   // (3 Q <= K)
+	double *part = c->part.as<double>(), *out = c->small.as<double>() + kBeamOut;
+	// two passes, no host round trip in between: the second reads the means the first left on the device
+	hipLaunchKernelGGL((beam_sums_stage1<T, D>), dim3(g), dim3(kBlock), 0, c->stream, buf, n, part);
+	hipLaunchKernelGGL(beam_sums_stage2<Q>, dim3(1), dim3(kBlock), 0, c->stream, part, g, n, out);
+	hipLaunchKernelGGL((beam_central_stage1<T, D>), dim3(g), dim3(kBlock), 0, c->stream, buf, n, out, part);
+	hipLaunchKernelGGL(beam_central_stage2, dim3(1), dim3(kBlock), 0, c->stream, part, g, K, out + 18);
+	NBCO_HIP(hipGetLastError());
+	double h[18 + K];
+	NBCO_HIP(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	nbco_moments m;
+	memset(&m, 0, sizeof m);
+	m.n = n;
+	m.dim = D;
+	for (int a = 0; a < Q; ++a) { m.mean[a] = h[a]; m.min[a] = h[6 + a]; m.max[a] = h[12 + a]; }
+	const double *s = h + 18;
+	for (int a = 0; a < Q; ++a)
+		for (int b = a; b < Q; ++b) m.cov[a][b] = m.cov[b][a] = *s++ / (double)n;
+	for (int p = 0; p < D; ++p)
+		for (int j = 0; j < 5; ++j) m.m4[p][j] = *s++ / (double)n;
+	nbco_moments_derive(&m);
+	*out_host = m;
+	return NBCO_OK;
+}
+
+int launch_beam_moments(nbco_ctx *c, const void *buf, int dim, long long n, nbco_moments *out_host)
+{
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, "beam_moments: n must be positive");
+	return dim == 3 ? beam_moments<float, 3>(c, (const float *)buf, n, out_host) : beam_moments<double, 2>(c, (const double *)buf, n, out_host);
+}
+
+template <class T, int D> static void hist_run(nbco_ctx *c, const T *buf, long long n, const HistAxes &ax, int B, unsigned long long *counts)
+{
+	if (B <= kHistLdsBins)
+	{
+		long long g = (n + kHistPerBlock - 1) / kHistPerBlock;
+		if (g > kMaxBlocks) g = kMaxBlocks;
+		hipLaunchKernelGGL((hist_kernel<T, D, true>), dim3((int)g), dim3(kBlock), sizeof(unsigned) * (size_t)B, c->stream, buf, n, ax, counts);
+	}
+	else hipLaunchKernelGGL((hist_kernel<T, D, false>), dim3(grid_for(n)), dim3(kBlock), 0, c->stream, buf, n, ax, counts);
+}
+
+int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axes, int naxes, unsigned long long *counts)
+{
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, "hist: n must be positive");
+	if (naxes != 1 && naxes != 2) return c->fail(NBCO_ERR_ARG, "hist: one or two axes");
+	long long B = 1;
+	for (int a = 0; a < naxes; ++a)
+	{
+		const nbco_hist_axis &x = axes[a];
+		const bool have = dim == 3 ? x.coord >= NBCO_Q_X && x.coord <= NBCO_Q_VZ
+		                           : x.coord == NBCO_Q_X || x.coord == NBCO_Q_Y || x.coord == NBCO_Q_VX || x.coord == NBCO_Q_VY;
+		if (!have) return c->fail(NBCO_ERR_ARG, "hist: the state has no such coordinate");
+		if (x.bins < 1 || x.bins > 65536) return c->fail(NBCO_ERR_ARG, "hist: bins must be 1..65536");
+		if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !std::isfinite(x.hi - x.lo)) return c->fail(NBCO_ERR_ARG, "hist: lo and hi must be finite");
+		if (!(x.lo < x.hi)) return c->fail(NBCO_ERR_ARG, "hist: lo must be below hi");
+		B *= x.bins;
+	}
+	if (B > (1LL << 24)) return c->fail(NBCO_ERR_ARG, "hist: more than 2^24 bins");
+	// element offset of a coordinate in buf = [pos n | vel n | ..]
+	auto off = [&](int coord) { return coord < 3 ? (long long)coord : (long long)dim * n + (coord - 3); };
+	HistAxes ax{};
+	ax.off0 = off(axes[0].coord);
+	ax.bins0 = axes[0].bins; ax.lo0 = axes[0].lo; ax.hi0 = axes[0].hi; ax.scale0 = (double)axes[0].bins / (axes[0].hi - axes[0].lo);
+	ax.bins1 = 1;
+	if (naxes == 2)
+	{
+		ax.two = 1;
+		ax.off1 = off(axes[1].coord);
+		ax.bins1 = axes[1].bins; ax.lo1 = axes[1].lo; ax.hi1 = axes[1].hi; ax.scale1 = (double)axes[1].bins / (axes[1].hi - axes[1].lo);
+	}
+	NBCO_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * (size_t)(B + 1), c->stream));
+	if (dim == 3) hist_run<float, 3>(c, (const float *)buf, n, ax, (int)B, counts);
+	else hist_run<double, 2>(c, (const double *)buf, n, ax, (int)B, counts);
+	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }

@@ -671,6 +671,50 @@ int nbco_energy(nbco_ctx *c, const float *buf, long long n, const float *param, 
 	return launch_energy(c, buf, n, param, out3_host);
 }
 
+// ---- beam diagnostics (k_reduce.hip) -------------------------------------------------------------
+int nbco_beam_moments(nbco_ctx *c, const float *buf, long long n, nbco_moments *out_host)
+{
+	if (!c || !buf || !out_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_beam_moments: null pointer") : NBCO_ERR_ARG;
+	return launch_beam_moments(c, buf, 3, n, out_host);
+}
+int nbco_2d_beam_moments(nbco_ctx *c, const double *buf, long long n, nbco_moments *out_host)
+{
+	if (!c || !buf || !out_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_2d_beam_moments: null pointer") : NBCO_ERR_ARG;
+	return launch_beam_moments(c, buf, 2, n, out_host);
+}
+// emit, halo_q, halo from cov and m4 (host only).  Zero conventions: halo_q = 0 where <d^2> = 0; emit = halo = 0 where I2 <= 0
+int nbco_moments_derive(nbco_moments *m)
+{
+	if (!m || (m->dim != 2 && m->dim != 3)) return NBCO_ERR_ARG;
+	const int D = m->dim;
+	for (int k = 0; k < 3; ++k) m->emit[k] = m->halo_q[k] = m->halo[k] = 0.0;
+	for (int k = 0; k < D; ++k)
+	{
+		const double x2 = m->cov[k][k], e2 = m->cov[D + k][D + k], xe = m->cov[k][D + k], *f = m->m4[k];
+		const double i2 = x2 * e2 - xe * xe;
+		const double i4 = f[0] * f[4] + 3.0 * f[2] * f[2] - 4.0 * f[3] * f[1];
+		if (x2 > 0.0) m->halo_q[k] = f[0] / (x2 * x2) - 2.0;
+		if (i2 > 0.0)
+		{
+			m->emit[k] = std::sqrt(i2);
+			m->halo[k] = std::sqrt(3.0 * std::fmax(i4, 0.0)) / (2.0 * i2) - 2.0;
+		}
+	}
+	return NBCO_OK;
+}
+int nbco_hist(nbco_ctx *c, const float *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev)
+{
+	if (!c || !buf || !axes_host || !counts_dev) return c ? c->fail(NBCO_ERR_ARG, "nbco_hist: null pointer") : NBCO_ERR_ARG;
+	NBCO_TRY(launch_hist(c, buf, 3, n, axes_host, naxes, counts_dev));
+	return maybe_sync(c);
+}
+int nbco_2d_hist(nbco_ctx *c, const double *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev)
+{
+	if (!c || !buf || !axes_host || !counts_dev) return c ? c->fail(NBCO_ERR_ARG, "nbco_2d_hist: null pointer") : NBCO_ERR_ARG;
+	NBCO_TRY(launch_hist(c, buf, 2, n, axes_host, naxes, counts_dev));
+	return maybe_sync(c);
+}
+
 int nbco_energy_fmm(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host)
 {
 	if (!c || !buf || !param || !out3_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_energy_fmm: null pointer") : NBCO_ERR_ARG;

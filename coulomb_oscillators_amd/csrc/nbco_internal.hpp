@@ -359,6 +359,9 @@ int launch_minmax4(nbco_ctx *c, const float4 *p4, long long n, float *out6_dev);
 int launch_mean_relerr(nbco_ctx *c, const float *x, const float *ref, long long n, float *out_host);
 int launch_pow_sum(nbco_ctx *c, const float *x, int expo, long long n, double *out3_host);
 int launch_energy(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host);
+// beam diagnostics; dim 3: buf holds fp32 xyz triplets, dim 2: fp64 xy pairs
+int launch_beam_moments(nbco_ctx *c, const void *buf, int dim, long long n, nbco_moments *out_host);
+int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
 // k_fmm_kd.hip
 int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);
 int kd_copy_out(nbco_ctx *c, int which, void *host_dst, long long host_bytes);

@@ -72,6 +72,20 @@ class DistStep(C.Structure):
                 ("rows_send", C.c_longlong * 64), ("rows_recv", C.c_longlong * 64)]
 
 
+class Moments(C.Structure):
+    """nbco_moments: phase-space moments of a state (include/nbco.h); q = (x, y, z, vx, vy, vz), in 2-D (x, y, vx, vy)"""
+    _fields_ = [("n", C.c_longlong), ("dim", C.c_int), ("mean", C.c_double * 6), ("min", C.c_double * 6), ("max", C.c_double * 6),
+                ("cov", (C.c_double * 6) * 6), ("m4", (C.c_double * 5) * 3), ("emit", C.c_double * 3), ("halo_q", C.c_double * 3),
+                ("halo", C.c_double * 3)]
+
+
+class HistAxis(C.Structure):
+    """nbco_hist_axis"""
+    _fields_ = [("coord", C.c_int), ("bins", C.c_int), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+Q_X, Q_Y, Q_Z, Q_VX, Q_VY, Q_VZ = range(6)   # NBCO_Q_*: the coordinate of a histogram axis
+
 COLL_DONE, COLL_ALLREDUCE_MIN_I32, COLL_ALLREDUCE_SUM_I32, COLL_ALLGATHER, COLL_ALLTOALL = range(5)
 
 
@@ -177,6 +191,11 @@ def _load():
         "nbco_2d_energy_fmm": [P, P, LL, P, C.POINTER(D), P],
         "nbco_2d_probe": [P, P, LL, P, LL, P, P, P],
         "nbco_2d_probe_fmm": [P, P, LL, P, LL, P, P, P],
+        "nbco_beam_moments": [P, P, LL, C.POINTER(Moments)],
+        "nbco_2d_beam_moments": [P, P, LL, C.POINTER(Moments)],
+        "nbco_moments_derive": [C.POINTER(Moments)],
+        "nbco_hist": [P, P, LL, C.POINTER(HistAxis), I, P],
+        "nbco_2d_hist": [P, P, LL, C.POINTER(HistAxis), I, P],
         "nbco_2d_init_kv": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
         "nbco_2d_init_gaussian": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
     }
@@ -443,6 +462,47 @@ class Engine:
         """the same from a kd-tree of its own on a private context (nbco_probe_tree): valid in any state of this engine, which it
         leaves untouched; p is neither modified nor reordered"""
         self._chk(self.lib.nbco_probe_tree(self.ctx, _ptr(p), n, _ptr(t), m, _ptr(param), _ptr(a), _ptr(psi)))
+
+    # ---- beam diagnostics ------------------------------------------------------------------------
+    def _moments(self, fn, buf, n):
+        out = Moments()
+        self._chk(fn(self.ctx, _ptr(buf), n, C.byref(out)))
+        return out
+
+    def beam_moments(self, buf, n):
+        """phase-space moments of buf = [pos n | vel n | ..] (float32 xyz triplets): a Moments structure with the means, the exact
+        extrema, the central second moments, the central fourth moments of every plane (q, p), and from them the rms emittances
+        and the halo parameters (nbco_beam_moments).  Two passes over the state, fp64, fixed order; buf is not modified."""
+        return self._moments(self.lib.nbco_beam_moments, buf, n)
+
+    def beam_moments_2d(self, buf, n):
+        """the same of the 2-D fp64 state [pos n | vel n | ..] of xy pairs (nbco_2d_beam_moments)"""
+        return self._moments(self.lib.nbco_2d_beam_moments, buf, n)
+
+    def _hist(self, fn, buf, n, axes, counts):
+        if len(axes) == 4 and not hasattr(axes[0], "__len__"):
+            axes = [axes]   # one (coord, bins, lo, hi) tuple
+        arr = (HistAxis * max(len(axes), 1))(*[HistAxis(int(a[0]), int(a[1]), float(a[2]), float(a[3])) for a in axes])
+        if counts is None:
+            total = 1
+            for a in axes:
+                total *= max(int(a[1]), 0)
+            if not 1 <= total <= 1 << 24:
+                total = 0   # (the library refuses the call; nothing that large is allocated for it)
+            counts = self.torch.empty(total + 1, dtype=self.torch.int64, device=buf.device)
+        self._chk(fn(self.ctx, _ptr(buf), n, arr, len(axes), _ptr(counts)))
+        return counts
+
+    def hist(self, buf, n, axes, counts=None):
+        """counts of the particles of buf = [pos n | vel n | ..] over one or two phase-space coordinates (nbco_hist): axes is one
+        (coord, bins, lo, hi) tuple or a list of one or two, coord one of Q_X .. Q_VZ.  Returns an int64 device tensor of B + 1
+        counts, B = bins0 * bins1 with axis 0 the slow index and the particles outside the window last; `counts` (allocated if
+        None) is overwritten.  inside: lo <= q < hi on every axis; bin (int)((q - lo) * (bins / (hi - lo))), clamped to bins - 1."""
+        return self._hist(self.lib.nbco_hist, buf, n, axes, counts)
+
+    def hist_2d(self, buf, n, axes, counts=None):
+        """the same of the 2-D fp64 state (nbco_2d_hist); the coordinates are Q_X, Q_Y, Q_VX, Q_VY"""
+        return self._hist(self.lib.nbco_2d_hist, buf, n, axes, counts)
 
     # ---- multi-GPU kd-domain sharding (see dist.py for the orchestration) ---------------------------
     def dist_layout(self, n_global, world, rank):

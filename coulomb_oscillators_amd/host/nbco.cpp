@@ -3,7 +3,8 @@
 // follow main.cu:257-903; the evaluator is nbco_2d_fmm (fmm_cart) plus the elastic term, integrated by nbco_2d_integrate.
 //
 // Additions: -energy writes the energies of every snapshot to energy.txt (nbco_2d_energy_fmm); -probes <file> writes the field and
-// the potential at the file's points for every snapshot (nbco_2d_probe_fmm); without them nothing changes.
+// the potential at the file's points for every snapshot (nbco_2d_probe_fmm); -moments writes the beam's phase-space moments of every
+// snapshot to moments.txt (nbco_2d_beam_moments); without them nothing changes.
 // Deviations: -cpu / -cpu-threads are refused (main.cu -cpu runs a host FMM, which this product does not have); -gpu, -gridsize
 // and -cacheline are validated as main.cu does and then have no effect; -p above 10 is refused by the library (NBCO_ERR_ARG).
 #include <hip/hip_runtime.h>
@@ -50,6 +51,10 @@ const char *kHelp =
     "  -energy           at every snapshot append `iter kinetic elastic coulomb total` to <dir>/energy.txt:\n"
     "                    the O(N) FMM potential energy of the snapshot's state (nbco_2d_energy_fmm, order -p);\n"
     "                    no effect with -test\n"
+    "  -moments          at every snapshot append the beam's phase-space moments to <dir>/moments.txt\n"
+    "                    (nbco_2d_beam_moments): `iter`, the means of (x, y, vx, vy), then per plane (x, vx), (y, vy)\n"
+    "                    `sig_q sig_p cov_qp emit halo_q halo`; the file starts with a `#` line naming the columns;\n"
+    "                    no effect with -test\n"
     "  -probes <file>    binary file of probe points as pairs of doubles (M = file size / 16).  At every snapshot\n"
     "                    write <dir>/probes<iter>_<ds>.bin: the M accelerations (pairs) and then the M potentials\n"
     "                    of the snapshot's particles at these points (nbco_2d_probe_fmm, order -p; the points feel\n"
@@ -82,7 +87,7 @@ int main(const int argc, const char **argv)
 	int fmm_order = 5, tree_radius = 1;
 	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1;
 	std::string strout("out"), strin, strprobes;
-	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false;
+	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false, moments = false;
 
 	// KV parameters matched to the emittances (main.cu:271-313)
 	const double twopi = 6.283185307179586476925286766559;
@@ -183,6 +188,7 @@ int main(const int argc, const char **argv)
 		else if (is(a, "test")) test = true;
 		else if (is(a, "ga")) ga = true;
 		else if (is(a, "energy")) energy = true;
+		else if (is(a, "moments")) moments = true;
 		else if (is(a, "probes")) { if (need(i, 1, a)) return missing(); strprobes = argv[++i]; }
 		else if (is(a, "xi"))
 		{
@@ -324,6 +330,20 @@ int main(const int argc, const char **argv)
 		std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
 		return done(-1);
 	}
+	FILE *fmo = nullptr;
+	if (moments)
+	{
+		if (!(fmo = std::fopen((strout + "/moments.txt").c_str(), "w")))
+		{
+			std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+			if (fen) std::fclose(fen);
+			return done(-1);
+		}
+		std::fprintf(fmo, "# iter mean_x mean_y mean_vx mean_vy");
+		for (const char *k : {"x", "y"}) std::fprintf(fmo, " sig_%s sig_v%s cov_%s_v%s emit_%s halo_q_%s halo_%s", k, k, k, k, k, k, k);
+		std::fprintf(fmo, "\n");
+		std::fflush(fmo);
+	}
 	std::vector<double> pout;
 	if (nprobes > 0)
 	{
@@ -332,11 +352,13 @@ int main(const int argc, const char **argv)
 		    !hip_ok(hipMemcpy(d_probes, probes.data(), sizeof(double) * 2 * (size_t)nprobes, hipMemcpyHostToDevice)))
 		{
 			if (fen) std::fclose(fen);
+			if (fmo) std::fclose(fmo);
 			return done(-1);
 		}
 	}
 	auto finish = [&](int code) {
 		if (fen) std::fclose(fen);
+		if (fmo) std::fclose(fmo);
 		return done(code);
 	};
 	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return finish(-1);
@@ -360,6 +382,18 @@ int main(const int argc, const char **argv)
 				if (!lib_ok(nbco_2d_energy_fmm(ctx, d_buf, n, d_par, e3, nullptr))) return finish(-1);
 				std::fprintf(fen, "%d %.17g %.17g %.17g %.17g\n", iter, e3[0], e3[1], e3[2], e3[0] + e3[1] + e3[2]);
 				std::fflush(fen);
+			}
+			if (fmo)
+			{
+				nbco_moments mom;
+				if (!lib_ok(nbco_2d_beam_moments(ctx, d_buf, n, &mom))) return finish(-1);
+				std::fprintf(fmo, "%d", iter);
+				for (int a = 0; a < 4; ++a) std::fprintf(fmo, " %.17g", mom.mean[a]);
+				for (int k = 0; k < 2; ++k)
+					std::fprintf(fmo, " %.17g %.17g %.17g %.17g %.17g %.17g", std::sqrt(mom.cov[k][k]), std::sqrt(mom.cov[2 + k][2 + k]), mom.cov[k][2 + k],
+					             mom.emit[k], mom.halo_q[k], mom.halo[k]);
+				std::fprintf(fmo, "\n");
+				std::fflush(fmo);
 			}
 			if (nprobes > 0)
 			{

@@ -63,6 +63,10 @@ const char *kHelp =
     "  -energy           At every snapshot append 'iter kinetic elastic coulomb total' to <output>/energy.txt: the Coulomb part from an\n"
     "                    O(N) kd-tree potential pass of its own at the run's -p, -r and -eps (with -cpu: the exact fp64 pair sum).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -moments          At every snapshot append the beam's phase-space moments to <output>/moments.txt (nbco_beam_moments; with -cpu the\n"
+    "                    same two-pass fp64 sums on the host): 'iter', the 6 means of (x, y, z, vx, vy, vz), then per plane (x, vx),\n"
+    "                    (y, vy), (z, vz) 'sig_q sig_p cov_qp emit halo_q halo'.  The file starts with a '#' line naming the columns.\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -probes <file>    <file> holds probe points (fp32 xyz triplets, no header).  At every snapshot write the field and the potential of\n"
     "                    the charges at these points to <output>/probes<iter>_<ds>.bin: m x 3 doubles of field, then m doubles of\n"
     "                    potential, from a kd-tree walk of its own at the run's -p, -r and -eps (with -cpu: the exact fp64 sums).\n"
@@ -82,6 +86,35 @@ struct EnergyLog
 		char buf[160];
 		std::snprintf(buf, sizeof buf, "%d %.17g %.17g %.17g %.17g\n", iter, e[0], e[1], e[2], e[0] + e[1] + e[2]);
 		out << buf << std::flush;
+	}
+};
+
+// <folder>/moments.txt of -moments: emptied when the run starts, a '#' line naming the columns, one line per snapshot
+struct MomentsLog
+{
+	std::ofstream out;
+	MomentsLog(bool on, const std::string &folder)
+	{
+		if (!on) return;
+		out.open(folder + "/moments.txt", std::ios::out | std::ios::trunc);
+		out << "# iter mean_x mean_y mean_z mean_vx mean_vy mean_vz";
+		for (const char *k : {"x", "y", "z"})
+			out << " sig_" << k << " sig_v" << k << " cov_" << k << "_v" << k << " emit_" << k << " halo_q_" << k << " halo_" << k;
+		out << std::endl;
+	}
+	void line(int iter, const nbco_moments &m)
+	{
+		if (!out.is_open()) return;
+		char buf[64];
+		auto put = [&](double v) { std::snprintf(buf, sizeof buf, " %.17g", v); out << buf; };
+		out << iter;
+		for (int a = 0; a < 6; ++a) put(m.mean[a]);
+		for (int k = 0; k < 3; ++k)
+		{
+			put(std::sqrt(m.cov[k][k])); put(std::sqrt(m.cov[3 + k][3 + k])); put(m.cov[k][3 + k]);
+			put(m.emit[k]); put(m.halo_q[k]); put(m.halo[k]);
+		}
+		out << '\n' << std::flush;
 	}
 };
 
@@ -258,9 +291,10 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, const std::vector<float> &probes)
+	             bool energy, bool moments, const std::vector<float> &probes)
 	{
 		EnergyLog elog(energy, folder);
+		MomentsLog mlog(moments, folder);
 		// -probes: the points and their results [field m x 3 | potential m] on the device, and the host copy that goes into the files
 		const size_t m = probes.size() / 3;
 		DeviceArray<float> probes_dev(probes.size());   // (nothing is allocated without the flag)
@@ -320,6 +354,13 @@ struct Session
 				check(nbco_energy_tree(ctx(), state.ptr, n, par.ptr, e3, nullptr), "energy_tree");
 				elog.line(snap, e3);
 			}
+			if (moments)
+			{
+				// two reduction passes over the state as it is; they use only the transient reduction scratch of the context
+				nbco_moments mom;
+				check(nbco_beam_moments(ctx(), state.ptr, n, &mom), "beam_moments");
+				mlog.line(snap, mom);
+			}
 			if (m)
 			{
 				// the same private context: a tree over a scratch copy of the positions, walked by the probes
@@ -354,7 +395,7 @@ int main(int argc, const char **argv)
 	int nIters = 30001, nSteps = 200;
 	std::string strout("out"), strin, strprobes;
 	std::vector<float> probes;
-	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false;
+	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
 	SCAL xi = (SCAL)2.e-6;
@@ -464,6 +505,7 @@ int main(int argc, const char **argv)
 		}
 		else if (a == "-cpu") cpu = true;
 		else if (a == "-energy") energy = true;
+		else if (a == "-moments") moments = true;
 		else if (a == "-probes")
 		{
 			if (!need(i, 1, "-probes")) return -1;
@@ -568,6 +610,7 @@ int main(int argc, const char **argv)
 		                             : scheme == NBCO_INTEG_PEFRL ? nbco_cpu::Pefrl : nbco_cpu::Leapfrog;
 		nbco_cpu::force(st.data(), nBodies, par, o.eps2);
 		EnergyLog elog(energy, strout);
+		MomentsLog mlog(moments, strout);
 		std::vector<double> probes_out(4 * (probes.size() / 3));
 		for (int iter = 0; iter < nIters; ++iter)
 		{
@@ -587,6 +630,15 @@ int main(int argc, const char **argv)
 				nbco_cpu::energy(st.data(), nBodies, par, o.eps2, e3);
 				elog.line(iter, e3);
 			}
+			if (moments)
+			{
+				nbco_moments mom{};
+				mom.n = nBodies;
+				mom.dim = 3;
+				nbco_cpu::moment_sums(st.data(), nBodies, mom.mean, mom.min, mom.max, mom.cov, mom.m4);
+				nbco_moments_derive(&mom);
+				mlog.line(iter, mom);
+			}
 			if (!probes.empty())
 			{
 				cpu_probes(st.data(), nBodies, probes, par, o.eps2, probes_out);
@@ -604,7 +656,7 @@ int main(int argc, const char **argv)
 	{
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
-		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, b_accuracy ? std::vector<float>{} : probes);
+		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes);
 	}
 	return rc;
 }

@@ -107,6 +107,40 @@ inline void energy(const V3 *buf, int n, const float *par, float eps2, double (&
 	out3[0] = ke; out3[1] = pe; out3[2] = ce * (double)par[0];
 }
 
+// Phase-space sums of buf = [pos | vel | ..] for `nbco3 -cpu -moments`, the two passes of nbco_beam_moments in fp64 over the fp32
+// state: first the means (sum / n; the value itself for a coordinate that is the same in every particle) and the exact extrema of
+// q = (x, y, z, vx, vy, vz), then the central sums with d = q - mean: cov[a][b] = <d_a d_b> (both triangles) and per plane
+// k = (q_k, q_(3 + k)) m4[k] = <x^4>, <x^3 e>, <x^2 e^2>, <x e^3>, <e^4>.  nbco_moments_derive (include/nbco.h) makes the
+// emittances and halo parameters of them, as it does for the device's sums.
+inline void moment_sums(const V3 *buf, int n, double (&mean)[6], double (&mn)[6], double (&mx)[6], double (&cov)[6][6], double (&m4)[3][5])
+{
+	auto coord = [=](int i, int a) { const V3 &r = buf[a < 3 ? i : n + i]; return (double)(a % 3 == 0 ? r.x : a % 3 == 1 ? r.y : r.z); };
+	for (int a = 0; a < 6; ++a)
+	{
+		double s = 0;
+		mn[a] = mx[a] = coord(0, a);
+		for (int i = 0; i < n; ++i) { const double q = coord(i, a); s += q; mn[a] = std::min(mn[a], q); mx[a] = std::max(mx[a], q); }
+		mean[a] = mn[a] == mx[a] ? mn[a] : s / (double)n;
+	}
+	for (auto &row : cov) for (double &v : row) v = 0;
+	for (auto &row : m4) for (double &v : row) v = 0;
+	for (int i = 0; i < n; ++i)
+	{
+		double d[6];
+		for (int a = 0; a < 6; ++a) d[a] = coord(i, a) - mean[a];
+		for (int a = 0; a < 6; ++a)
+			for (int b = a; b < 6; ++b) cov[a][b] += d[a] * d[b];
+		for (int k = 0; k < 3; ++k)
+		{
+			const double x2 = d[k] * d[k], e2 = d[3 + k] * d[3 + k], xe = d[k] * d[3 + k];
+			m4[k][0] += x2 * x2; m4[k][1] += x2 * xe; m4[k][2] += x2 * e2; m4[k][3] += xe * e2; m4[k][4] += e2 * e2;
+		}
+	}
+	for (int a = 0; a < 6; ++a)
+		for (int b = a; b < 6; ++b) cov[b][a] = cov[a][b] = cov[a][b] / (double)n;
+	for (auto &row : m4) for (double &v : row) v /= (double)n;
+}
+
 // one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call)
 enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
 inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt)

@@ -544,6 +544,51 @@ int nbco_2d_probe(nbco_ctx *c, const double *p, long long n, const double *t, lo
  * (DESIGN 7a). */
 int nbco_2d_probe_fmm(nbco_ctx *c, const double *p, long long n, const double *t, long long m, const double *param, double *a_dev,
                       double *psi_dev);
+/* ---- beam diagnostics: phase-space moments and density maps of a state (the reference prints `emittances: x * u` once, at
+ * initialisation, main.cu:774; nothing there bins particles).  buf = [pos n | vel n | ..] is a DEVICE pointer: fp32 xyz triplets
+ * for the nbco_ calls, fp64 xy pairs for the nbco_2d_ calls.  Only positions and velocities are read; buf is neither modified nor
+ * reordered.  Both passes are O(n), use only the transient reduction scratch of the context (a valid nbco_energy_fmm /
+ * nbco_kd_potential / nbco_kd_probe stays valid and returns the bits it would have returned) and give the same bytes when called again.
+ * Sharded runs: the calls describe the particles they are given.  Central moments of domains do not simply add (the centres
+ * differ), so a sharded run gathers its state, or combines {n, mean, cov, m4} of the domains on the host with the usual shift formulas.
+ *
+ * nbco_beam_moments / nbco_2d_beam_moments: two passes.  The first takes the sums and the extrema of the 6 (4) coordinates and
+ * leaves mean = sum / n on the device -- the coordinate's value itself where min == max, so that a constant axis has deviations of
+ * exactly 0.  The second accumulates the products of d = (double) q - mean in fp64: the central form keeps the fourth moments of a
+ * beam that sits off the origin, which raw power sums lose to cancellation.  Four launches and one synchronisation; every sum has a
+ * fixed order and there are no float atomics.  The call synchronises and fills *out_host.  A NULL buf or out_host or n <= 0:
+ * NBCO_ERR_ARG before any launch, *out_host left as it was.
+ * Zero conventions: halo_q[k] = 0 where <d^2> = 0; emit[k] = halo[k] = 0 where I2 <= 0.  So n = 1, coincident particles and a
+ * flat axis give zeros, never NaN. */
+typedef struct nbco_moments {
+	long long n; int dim;      /* 3 or 2 */
+	double mean[6];            /* q = (x, y, z, vx, vy, vz); 2-D: (x, y, vx, vy), unused entries 0 */
+	double min[6], max[6];     /* exact */
+	double cov[6][6];          /* central: 1/n sum (q_a - mean_a)(q_b - mean_b), symmetric, both triangles filled */
+	double m4[3][5];           /* per plane k = (x,vx), (y,vy), (z,vz), central, with d = q - mean_q, e = p - mean_p:
+	                              <d^4>, <d^3 e>, <d^2 e^2>, <d e^3>, <e^4> */
+	double emit[3];            /* sqrt(max(I2, 0)), I2 = <d^2><e^2> - <d e>^2 */
+	double halo_q[3];          /* <d^4> / <d^2>^2 - 2          (0 for KV, 1 for a Gaussian) */
+	double halo[3];            /* sqrt(3 I4) / (2 I2) - 2, I4 = <d^4><e^4> + 3 <d^2 e^2>^2 - 4 <d e^3><d^3 e>   (same values) */
+} nbco_moments;
+int nbco_beam_moments(nbco_ctx *c, const float *buf, long long n, nbco_moments *out_host);
+int nbco_2d_beam_moments(nbco_ctx *c, const double *buf, long long n, nbco_moments *out_host);
+/* Host only, no GPU needed: emit, halo_q and halo of *m from its cov and m4 (and dim), with the zero conventions above.  The two
+ * calls above end with it; a caller that has formed the sums elsewhere (`nbco3 -cpu -moments`) gets the same derivation. */
+int nbco_moments_derive(nbco_moments *m_host);
+/* nbco_hist / nbco_2d_hist: counts of the particles over one (naxes = 1: a profile) or two (a map) phase-space coordinates.
+ * axes_host[a] = {coord, bins, lo, hi} in HOST memory; counts_dev receives B + 1 values in DEVICE memory, B = bins0 * bins1
+ * (bins1 = 1 for naxes = 1), axis 0 the slow index; counts[B] is the number of particles outside the window.  The buffer is
+ * overwritten, not accumulated.  The bin rule, in fp64 over the widened coordinate: scale = bins / (hi - lo) (computed once on
+ * the host); a particle is inside iff q >= lo && q < hi on every axis (a NaN is outside); b = (int) ((q - lo) * scale), clamped
+ * to bins - 1.  Integer atomics only: the counts are exact and do not depend on the order of arrival.  The calls return as the
+ * evaluators do (opts.sync, opts.stream) and refuse with NBCO_ERR_ARG before any launch, counts_dev untouched: NULL pointers,
+ * n <= 0, naxes not 1 or 2, a coordinate the state does not have (Z and VZ in 2-D), bins < 1 or > 65536, B > 2^24, lo or hi not
+ * finite, lo >= hi.  Radial coordinates and weights are not offered: a user folds the x-y map on the host. */
+enum { NBCO_Q_X = 0, NBCO_Q_Y = 1, NBCO_Q_Z = 2, NBCO_Q_VX = 3, NBCO_Q_VY = 4, NBCO_Q_VZ = 5 };
+typedef struct nbco_hist_axis { int coord; int bins; double lo, hi; } nbco_hist_axis;
+int nbco_hist(nbco_ctx *c, const float *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
+int nbco_2d_hist(nbco_ctx *c, const double *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
 /* main.cu:120-145 initKV and :147-170 initGA over std::mt19937_64(seed) after discard(discard) (main.cu:779-784 uses
  * NBCO_REF_SEED / NBCO_REF_DISCARD); host_state = [pos n x 2 | vel n x 2] doubles in HOST memory, centred with exactly the
  * RMS A/2, omega A/2 (KV) or x, u (Gaussian) per axis.  initKV takes each angle's sine and cosine from one glibc sincos call,
