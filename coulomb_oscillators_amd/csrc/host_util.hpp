@@ -1,42 +1,13 @@
 // host_util.hpp -- host idioms of the translation units that call rocPRIM (the tree evaluators and the re-partition): the size
-// query / scratch growth / call triple, written once; the grid size of a 1-D launch; the switch that turns a run-time expansion
-// order into a template argument.  The rocPRIM helpers enqueue on c->stream and grow the scratch buffer they are GIVEN: which
-// buffer that is stays the caller's choice, because two streams must never share a scratch (sort_tmp on the main stream,
-// scan_tmp_aux on the auxiliary one, f2d_tmp in the 2-D path).
+// query / scratch growth / call triple, written once; the grid size of a 1-D launch; and, through dispatch.hpp, the switches
+// that turn a run-time choice into a template argument.  The rocPRIM helpers enqueue on c->stream and grow the scratch buffer
+// they are GIVEN: which buffer that is stays the caller's choice, because two streams must never share a scratch (sort_tmp on
+// the main stream, scan_tmp_aux on the auxiliary one, f2d_tmp in the 2-D path).
 #pragma once
 #include "nbco_internal.hpp"
+#include "dispatch.hpp"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
-#include <type_traits>
-
-// f(std::integral_constant<int, P>) for a run-time order 1 <= P <= PMAX; false (and no call) for any other order.  A launch
-// function calls this once, around its hipLaunchKernelGGL: the only place where the order of that kernel is chosen.
-template <int PMAX = kMaxOrder, class F>
-static bool with_order(int P, F &&f)
-{
-	static_assert(PMAX <= 10 && kMaxOrder == 10, "the case list below ends at order 10");
-#define NBCO_ORDER_CASE(PP) \
-	case PP: \
-		if constexpr (PP <= PMAX) { f(std::integral_constant<int, PP>{}); return true; } \
-		return false;
-	switch (P)
-	{
-	NBCO_ORDER_CASE(1) NBCO_ORDER_CASE(2) NBCO_ORDER_CASE(3) NBCO_ORDER_CASE(4) NBCO_ORDER_CASE(5)
-	NBCO_ORDER_CASE(6) NBCO_ORDER_CASE(7) NBCO_ORDER_CASE(8) NBCO_ORDER_CASE(9) NBCO_ORDER_CASE(10)
-	default: return false;
-	}
-#undef NBCO_ORDER_CASE
-}
-
-// f(std::bool_constant<WANT_A>, std::bool_constant<WANT_PSI>) for the outputs of a probe call that are given (not both are NULL): an
-// output that is NULL costs nothing, because the kernels are compiled per output set
-template <class F>
-static void with_outputs(const double *a, const double *psi, F &&f)
-{
-	if (a && psi) f(std::true_type{}, std::true_type{});
-	else if (a) f(std::true_type{}, std::false_type{});
-	else f(std::false_type{}, std::true_type{});
-}
 
 // blocks of `block` threads that cover n items, at most cap.  No lower bound: 0 for n <= 0.
 static inline int grid_blocks(long long n, int block, long long cap) { return (int)std::min<long long>((n + block - 1) / block, cap); }

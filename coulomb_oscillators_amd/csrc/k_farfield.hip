@@ -8,6 +8,7 @@
 // levels with at most kTopNodes nodes are processed by ONE workgroup that walks the levels with
 // __syncthreads(); data it wrote at the previous level is re-read past the L1 (agent-scope loads).
 #include "nbco_internal.hpp"
+#include "dispatch.hpp"
 
 namespace {
 
@@ -512,14 +513,16 @@ static int run_l2p(nbco_ctx *c, const float4 *pos, const float *center, const T 
 
 } // namespace
 
-#define NBCO_DISPATCH_P(P, CALL)                                                       \
-	switch (P)                                                                         \
-	{                                                                                  \
-	case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); \
-	case 5: return CALL(5); case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); \
-	case 9: return CALL(9); case 10: return CALL(10);                                                \
-	default: return c->fail(NBCO_ERR_UNSUPPORTED, "generated far-field operators exist for orders 1..10"); \
-	}
+// run(order, T{}) -> status, with the order and the tuples' element type as template arguments (dispatch.hpp)
+template <class Run>
+static int far_dispatch(nbco_ctx *c, int P, int f64, Run &&run)
+{
+	int rc = NBCO_OK;
+	bool ok = false;
+	with_real(f64 != 0, [&](auto r) { ok = with_order(P, [&](auto p) { rc = run(p, r); }); });
+	if (!ok) return c->fail(NBCO_ERR_UNSUPPORTED, "generated far-field operators exist for orders 1..10");
+	return rc;
+}
 
 // centres + multiplicities of all internal nodes from the leaves' (2 launches up to 16 levels)
 int launch_kd_centres(nbco_ctx *c, float *center, int *mult, int L, const float *lbound, const float *rbound, float4 *csz)
@@ -549,15 +552,9 @@ int launch_kd_centres(nbco_ctx *c, float *center, int *mult, int L, const float 
 // downward shifts' fused kernels beyond what fits their LDS: the launchers size themselves from sizeof(T))
 int launch_upward_gen(nbco_ctx *c, int P, const float4 *pos, float *center, void *mpole, int *mult, const int *index, int L, int write_geom, int f64)
 {
-	if (f64)
-	{
-#define CALL(PP) run_upward<PP, double>(c, pos, center, (double *)mpole, mult, index, L, write_geom)
-		NBCO_DISPATCH_P(P, CALL)
-#undef CALL
-	}
-#define CALL(PP) run_upward<PP, float>(c, pos, center, (float *)mpole, mult, index, L, write_geom)
-	NBCO_DISPATCH_P(P, CALL)
-#undef CALL
+	return far_dispatch(c, P, f64, [&](auto p, auto r) {
+		return run_upward<decltype(p)::value, decltype(r)>(c, pos, center, (decltype(r) *)mpole, mult, index, L, write_geom);
+	});
 }
 
 // centres, multiplicities and traversal records of levels ltop .. 0 from level ltop + 1 (the levels above the kd-domains; the
@@ -572,43 +569,26 @@ int launch_kd_centres_top(nbco_ctx *c, float *center, int *mult, int ltop, const
 
 int launch_m2m_top_gen(nbco_ctx *c, int P, float *center, void *mpole, int *mult, int ltop, int L, int write_geom, int f64)
 {
-	if (f64)
-	{
-#define CALL(PP) run_m2m_top<PP, double>(c, center, (double *)mpole, mult, ltop, L, write_geom)
-		NBCO_DISPATCH_P(P, CALL)
-#undef CALL
-	}
-#define CALL(PP) run_m2m_top<PP, float>(c, center, (float *)mpole, mult, ltop, L, write_geom)
-	NBCO_DISPATCH_P(P, CALL)
-#undef CALL
+	return far_dispatch(c, P, f64, [&](auto p, auto r) {
+		return run_m2m_top<decltype(p)::value, decltype(r)>(c, center, (decltype(r) *)mpole, mult, ltop, L, write_geom);
+	});
 }
 
 int launch_downward_gen(nbco_ctx *c, int P, const float *center, void *local, int L, int dom_d, int dom_g, int f64)
 {
-	if (f64)
-	{
-#define CALL(PP) run_downward<PP, double>(c, center, (double *)local, L, dom_d, dom_g)
-		NBCO_DISPATCH_P(P, CALL)
-#undef CALL
-	}
-#define CALL(PP) run_downward<PP, float>(c, center, (float *)local, L, dom_d, dom_g)
-	NBCO_DISPATCH_P(P, CALL)
-#undef CALL
+	return far_dispatch(c, P, f64, [&](auto p, auto r) {
+		return run_downward<decltype(p)::value, decltype(r)>(c, center, (decltype(r) *)local, L, dom_d, dom_g);
+	});
 }
 
 int launch_l2p_gen(nbco_ctx *c, int P, const float4 *pos, const float *center, const void *local, const float4 *near, const int *chunk_off,
                    const int *index, int mlt_max, const int *unsort, int scatter, const float *param, float *a, int have_near, long long n, int L,
                    long long own0, long long own_n, const int2 *sec_range, const float4 *react, long long react_cap, int react_stride, int f64)
 {
-	if (f64)
-	{
-#define CALL(PP) run_l2p<PP, double>(c, pos, center, (const double *)local, near, chunk_off, index, mlt_max, unsort, scatter, param, a, have_near, n, L, own0, own_n, sec_range, react, react_cap, react_stride)
-		NBCO_DISPATCH_P(P, CALL)
-#undef CALL
-	}
-#define CALL(PP) run_l2p<PP, float>(c, pos, center, (const float *)local, near, chunk_off, index, mlt_max, unsort, scatter, param, a, have_near, n, L, own0, own_n, sec_range, react, react_cap, react_stride)
-	NBCO_DISPATCH_P(P, CALL)
-#undef CALL
+	return far_dispatch(c, P, f64, [&](auto p, auto r) {
+		return run_l2p<decltype(p)::value, decltype(r)>(c, pos, center, (const decltype(r) *)local, near, chunk_off, index, mlt_max, unsort, scatter, param, a,
+		                                                have_near, n, L, own0, own_n, sec_range, react, react_cap, react_stride);
+	});
 }
 
 NBCO_CHECKED_COLLECT(nbco_checked_collect_far)

@@ -24,6 +24,7 @@
 // nbco_2d_probe_fmm builds that tree up to the multipoles and evaluates them at the probes, leaf by leaf in the probes' key order.
 #include "nbco_internal.hpp"
 #include "host_util.hpp"
+#include "integ_compose.hpp"
 #include <algorithm>
 #include <cmath>
 #include <random>
@@ -573,52 +574,6 @@ static void f2d_launch_near(nbco_ctx *c, int P, bool coll, const Quad &q, const 
 	});
 }
 
-// one evaluation; f2d_fmm has checked the arguments and the order
-static int f2d_fmm_run(nbco_ctx *c, double *p, double *a, long long n, const double *param)
-{
-	const int P = c->o.fmm_order;
-	const int L = f2d_levels(c->o, n);
-	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: tree_L must be 0 or 2..15");
-	const int radius = (int)c->o.tree_radius;
-	const double eps2 = (double)c->o.eps2;
-	const int side = 1 << L, m = side * side;
-	const long long ntot = quad_beg(L + 1);
-	hipStream_t st = c->stream;
-
-	// scratch: keys in / out, indices in / out | tree | reduction partials + scalars (the gather and sort temp grows at the sort)
-	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
-	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
-	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1) + P) + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
-	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
-	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
-	Quad q;
-	q.center = c->f2d_tree.as<double2>();
-	q.mpole = q.center + ntot;
-	q.local = q.mpole + ntot * (P + 1);
-	q.mult = reinterpret_cast<int *>(q.local + ntot * P);
-	q.index = q.mult + ntot;
-	double *part = c->f2d_part.as<double>(), *scal = part + 4 * kRedBlocks;
-
-	double2 *x = (double2 *)p, *v = x + n;
-	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
-	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, (const double2 *)x, n, part);
-	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
-	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, (const double2 *)x, n, (const double *)scal, side, keys_in, idx_in);
-	// f2d_tmp is the sort's scratch and then the gather's destination: sized for the larger of the two
-	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * L), sizeof(double) * 4 * (size_t)n));
-	double2 *tmp = c->f2d_tmp.as<double2>();
-	hipLaunchKernelGGL(f2d_gather_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, (const double2 *)x, (const double2 *)v, (const uint32_t *)idx, tmp, n);
-	NBCO_HIP(hipMemcpyAsync(p, tmp, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
-	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
-
-	f2d_launch_leaf(c, P, q, x, m, quad_beg(L));
-	for (int l = L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
-	f2d_launch_m2l(c, P, q, L, radius, eps2);
-	for (int l = 3; l <= L; ++l) f2d_launch_l2l(c, P, q, l);
-	f2d_launch_near(c, P, c->o.coll != 0, q, x, (double2 *)a, L, radius, eps2, param);
-	return f2d_done(c);
-}
-
 // what nbco_2d_fmm asks of n and the options; the integrators ask it before their first launch, so that a refused step moves nothing
 static int f2d_fmm_check(nbco_ctx *c, long long n)
 {
@@ -628,14 +583,101 @@ static int f2d_fmm_check(nbco_ctx *c, long long n)
 	return NBCO_OK;
 }
 
+// ---- the tree stage that the evaluator, the FMM energy and the FMM probes share ------------------------------------------------------
+// what a tree call (`who`, for the refusals) takes from the options and n: side = 2^L, m = 4^L leaves, ntot nodes on levels 0..L
+struct F2dPlan
+{
+	int P, L, radius, side, m;
+	double eps2;
+	long long ntot;
+};
+static int f2d_plan(nbco_ctx *c, const char *who, long long n, F2dPlan &pl)
+{
+	NBCO_TRY(f2d_fmm_check(c, n));
+	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
+		return c->fail(NBCO_ERR_ARG, std::string(who) + ": fmm_order must be 1..10 (orders above 10 are not provided)");
+	pl.P = c->o.fmm_order;
+	pl.L = f2d_levels(c->o, n);
+	if (pl.L < 2 || pl.L > kMaxL2) return c->fail(NBCO_ERR_ARG, std::string(who) + ": tree_L must be 0 or 2..15");
+	pl.radius = (int)c->o.tree_radius;
+	pl.eps2 = (double)c->o.eps2;
+	pl.side = 1 << pl.L;
+	pl.m = pl.side * pl.side;
+	pl.ntot = quad_beg(pl.L + 1);
+	return NBCO_OK;
+}
+
+// the tree, the constants of the potential's far field (with_c0), the sources in cell order, the sort permutation, the scalars of the keys
+struct F2dTree
+{
+	Quad q;
+	double *c0;
+	const double2 *x;
+	const uint32_t *idx;
+	const double *scal;
+};
+
+// Keys, stable sort and gather of the n sources at x0, leaf index, centroids and multipoles up to level 2.  Scratch: f2d_keys = keys
+// in / out, indices in / out; f2d_tree = centres | multipoles | locals (with_local) | c0 (with_c0) | multiplicities | leaf index;
+// f2d_part = reduction partials + scalars + part_more doubles of the caller's behind them; f2d_tmp = the sort's scratch, then the
+// gather's destination.  state: the caller's [x | v] with x0 = x, reordered in place; nullptr: x0 is only read, and the
+// sorted positions stay in f2d_tmp.
+static int f2d_tree_build(nbco_ctx *c, const F2dPlan &pl, const double2 *x0, long long n, bool with_local, bool with_c0, double *state, size_t part_more,
+                          F2dTree &t)
+{
+	const int P = pl.P, m = pl.m;
+	const long long ntot = pl.ntot;
+	hipStream_t st = c->stream;
+	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
+	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
+	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1) + (with_local ? P : 0)) + sizeof(double) * (with_c0 ? (size_t)ntot : 0) +
+	                          sizeof(int) * ((size_t)ntot + (size_t)m + 1);
+	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
+	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8 + part_more)));
+	Quad &q = t.q;
+	q.center = c->f2d_tree.as<double2>();
+	q.mpole = q.center + ntot;
+	double2 *after = q.mpole + ntot * (P + 1);
+	q.local = with_local ? after : nullptr;
+	if (with_local) after += ntot * P;
+	t.c0 = with_c0 ? reinterpret_cast<double *>(after) : nullptr;
+	q.mult = reinterpret_cast<int *>(reinterpret_cast<double *>(after) + (with_c0 ? ntot : 0));
+	q.index = q.mult + ntot;
+	double *part = c->f2d_part.as<double>(), *scal = part + 4 * kRedBlocks;
+
+	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
+	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, x0, n, part);
+	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, pl.side, pl.eps2, scal);
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, n, (const double *)scal, pl.side, keys_in, idx_in);
+	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * pl.L), sizeof(double2) * (state ? 2 : 1) * (size_t)n));
+	double2 *tmp = c->f2d_tmp.as<double2>();
+	if (state)
+	{
+		hipLaunchKernelGGL(f2d_gather_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, x0 + n, (const uint32_t *)idx, tmp, n);
+		NBCO_HIP(hipMemcpyAsync(state, tmp, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+	}
+	else hipLaunchKernelGGL(f2d_gather_pos_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, (const uint32_t *)idx, tmp, n);
+	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
+	t.x = state ? x0 : tmp;
+	t.idx = idx;
+	t.scal = scal;
+	f2d_launch_leaf(c, P, q, t.x, m, quad_beg(pl.L));
+	for (int l = pl.L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
+	return NBCO_OK;
+}
+
 static int f2d_fmm(nbco_ctx *c, double *p, double *a, long long n, const double *param)
 {
 	if (!c) return NBCO_ERR_ARG;
 	if (!p || !a || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: bad arguments");
-	NBCO_TRY(f2d_fmm_check(c, n));
-	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
-		return c->fail(NBCO_ERR_ARG, "nbco_2d_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
-	return f2d_fmm_run(c, p, a, n, param);
+	F2dPlan pl;
+	NBCO_TRY(f2d_plan(c, "nbco_2d_fmm", n, pl));
+	F2dTree t;
+	NBCO_TRY(f2d_tree_build(c, pl, (const double2 *)p, n, /*with_local*/ true, /*with_c0*/ false, /*state*/ p, /*part_more*/ 0, t));
+	f2d_launch_m2l(c, pl.P, t.q, pl.L, pl.radius, pl.eps2);
+	for (int l = 3; l <= pl.L; ++l) f2d_launch_l2l(c, pl.P, t.q, l);
+	f2d_launch_near(c, pl.P, c->o.coll != 0, t.q, t.x, (double2 *)a, pl.L, pl.radius, pl.eps2, param);
+	return f2d_done(c);
 }
 
 // ---- energy diagnostics ------------------------------------------------------------------------------------------------------
@@ -659,14 +701,13 @@ static void f2d_launch_near_pot(nbco_ctx *c, int P, int grid, const Quad &q, con
 }
 
 // f2d_part for an energy call: | minmax partials 4 kRedBlocks | scalars 8 (out3 at + 4) | kinetic / elastic slots 2 kRedBlocks | npot potential slots |
-static int f2d_energy_part(nbco_ctx *c, long long npot, double **scal, double **ke, double **pot)
+// f2d_energy_more: what lies behind the scalars; f2d_energy_slots: the slots of a part that is reserved
+static size_t f2d_energy_more(long long npot) { return 2 * (size_t)kRedBlocks + (size_t)npot; }
+static void f2d_energy_slots(nbco_ctx *c, double **scal, double **ke, double **pot)
 {
-	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (6 * (size_t)kRedBlocks + 8 + (size_t)npot)));
-	double *part = c->f2d_part.as<double>();
-	*scal = part + 4 * kRedBlocks;
+	*scal = c->f2d_part.as<double>() + 4 * kRedBlocks;
 	*ke = *scal + 8;
 	*pot = *ke + 2 * kRedBlocks;
-	return NBCO_OK;
 }
 
 // kinetic and elastic slots, then the final block and the copy to the host
@@ -692,68 +733,34 @@ static int f2d_energy(nbco_ctx *c, const double *buf, long long n, const double 
 	if (!buf || !param || !out3_host || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy: bad arguments");
 	const long long nb = (n + kB - 1) / kB;
 	if (nb > (1LL << 31) - 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy: n too large");
+	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8 + f2d_energy_more(nb))));
 	double *scal, *ke, *pot;
-	NBCO_TRY(f2d_energy_part(c, nb, &scal, &ke, &pot));
+	f2d_energy_slots(c, &scal, &ke, &pot);
 	hipLaunchKernelGGL(f2d_pair_pot_kernel, dim3((unsigned)nb), dim3(kB), 0, c->stream, (const double2 *)buf, n, (double)c->o.eps2, param, phi_dev, pot);
 	return f2d_energy_finish(c, buf, n, param, scal, ke, pot, nb, out3_host);
 }
 
-// the tree of f2d_fmm_run over a scratch copy of the positions (same level formula, keys, stable sort, centroids and multipoles),
-// then the field's M2L / L2L with the constant's next to them, and the near-field potential.  buf is only read.
+// the evaluator's tree over a scratch copy of the positions, then the field's M2L / L2L with the constant's next to them, and the
+// near-field potential.  buf is only read.
 static int f2d_energy_fmm(nbco_ctx *c, const double *buf, long long n, const double *param, double *out3_host, double *phi_dev)
 {
 	if (!c) return NBCO_ERR_ARG;
 	if (!buf || !param || !out3_host || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy_fmm: bad arguments");
-	NBCO_TRY(f2d_fmm_check(c, n));
-	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
-		return c->fail(NBCO_ERR_ARG, "nbco_2d_energy_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
-	const int P = c->o.fmm_order;
-	const int L = f2d_levels(c->o, n);
-	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_energy_fmm: tree_L must be 0 or 2..15");
-	const int radius = (int)c->o.tree_radius;
-	const double eps2 = (double)c->o.eps2;
-	const int side = 1 << L, m = side * side;
-	const long long ntot = quad_beg(L + 1);
-	hipStream_t st = c->stream;
-
-	// scratch as in f2d_fmm_run, with the constants between the locals and the integer arrays
-	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
-	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
-	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1) + P) + sizeof(double) * (size_t)ntot + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
-	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
-	const int near_grid = std::min(1 << (2 * L), 1 << 22);
+	F2dPlan pl;
+	NBCO_TRY(f2d_plan(c, "nbco_2d_energy_fmm", n, pl));
+	const int P = pl.P, L = pl.L, near_grid = std::min(1 << (2 * L), 1 << 22);
+	F2dTree t;
+	NBCO_TRY(f2d_tree_build(c, pl, (const double2 *)buf, n, /*with_local*/ true, /*with_c0*/ true, /*state*/ nullptr, f2d_energy_more(near_grid), t));
 	double *scal, *ke, *pot;
-	NBCO_TRY(f2d_energy_part(c, near_grid, &scal, &ke, &pot));
-	double *part = c->f2d_part.as<double>();
-	Quad q;
-	q.center = c->f2d_tree.as<double2>();
-	q.mpole = q.center + ntot;
-	q.local = q.mpole + ntot * (P + 1);
-	double *c0 = reinterpret_cast<double *>(q.local + ntot * P);
-	q.mult = reinterpret_cast<int *>(c0 + ntot);
-	q.index = q.mult + ntot;
-
-	const double2 *x0 = (const double2 *)buf;
-	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
-	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, x0, n, part);
-	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
-	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, n, (const double *)scal, side, keys_in, idx_in);
-	// f2d_tmp is the sort's scratch and then holds the positions in cell order
-	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * L), sizeof(double2) * (size_t)n));
-	double2 *x = c->f2d_tmp.as<double2>();
-	hipLaunchKernelGGL(f2d_gather_pos_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, (const uint32_t *)idx, x, n);
-	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
-
-	f2d_launch_leaf(c, P, q, x, m, quad_beg(L));
-	for (int l = L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
-	f2d_launch_m2l(c, P, q, L, radius, eps2);
-	f2d_launch_m2l0(c, P, q, c0, L, radius, eps2);
+	f2d_energy_slots(c, &scal, &ke, &pot);
+	f2d_launch_m2l(c, P, t.q, L, pl.radius, pl.eps2);
+	f2d_launch_m2l0(c, P, t.q, t.c0, L, pl.radius, pl.eps2);
 	for (int l = 3; l <= L; ++l)
 	{
-		f2d_launch_l2l(c, P, q, l);
-		f2d_launch_l2l0(c, P, q, c0, l);
+		f2d_launch_l2l(c, P, t.q, l);
+		f2d_launch_l2l0(c, P, t.q, t.c0, l);
 	}
-	f2d_launch_near_pot(c, P, near_grid, q, c0, x, idx, L, radius, eps2, param, phi_dev, pot);
+	f2d_launch_near_pot(c, P, near_grid, t.q, t.c0, t.x, t.idx, L, pl.radius, pl.eps2, param, phi_dev, pot);
 	return f2d_energy_finish(c, buf, n, param, scal, ke, pot, near_grid, out3_host);
 }
 
@@ -791,58 +798,28 @@ static void f2d_launch_probe(nbco_ctx *c, int P, const Quad &q, const int *pinde
 	});
 }
 
-// the tree of f2d_energy_fmm over a scratch copy of p, up to the M2M chain; then the probes keyed with the sources' scalars, sorted,
-// indexed by leaf, and summed leaf by leaf.  p and t are only read.
+// the tree over a scratch copy of p, without locals; then the probes keyed with the sources' scalars, sorted, indexed by leaf (f2d_pkeys:
+// keys in / out, indices in / out, leaf index), and summed leaf by leaf.  p and t are only read.
 static int f2d_probe_fmm(nbco_ctx *c, const double *p, long long n, const double *t, long long mp, const double *param, double *a, double *psi)
 {
 	if (!c) return NBCO_ERR_ARG;
 	NBCO_TRY(f2d_probe_args(c, "nbco_2d_probe_fmm", p, n, t, mp, param, a, psi));
-	NBCO_TRY(f2d_fmm_check(c, n));
-	if (c->o.fmm_order < 1 || c->o.fmm_order > kMaxOrder)
-		return c->fail(NBCO_ERR_ARG, "nbco_2d_probe_fmm: fmm_order must be 1..10 (orders above 10 are not provided)");
-	const int P = c->o.fmm_order;
-	const int L = f2d_levels(c->o, n);
-	if (L < 2 || L > kMaxL2) return c->fail(NBCO_ERR_ARG, "nbco_2d_probe_fmm: tree_L must be 0 or 2..15");
-	const int radius = (int)c->o.tree_radius;
-	const double eps2 = (double)c->o.eps2;
-	const int side = 1 << L, m = side * side;
-	const long long ntot = quad_beg(L + 1);
+	F2dPlan pl;
+	NBCO_TRY(f2d_plan(c, "nbco_2d_probe_fmm", n, pl));
+	const int m = pl.m;
 	hipStream_t st = c->stream;
-
-	// scratch: the sources' as in f2d_energy_fmm, without locals; the probes' keys in / out, indices in / out and leaf index
-	NBCO_TRY(c->reserve(c->f2d_keys, sizeof(uint32_t) * 4 * (size_t)n));
-	uint32_t *keys_in = c->f2d_keys.as<uint32_t>(), *keys = keys_in + n, *idx_in = keys + n, *idx = idx_in + n;
 	NBCO_TRY(c->reserve(c->f2d_pkeys, sizeof(uint32_t) * 4 * (size_t)mp + sizeof(int) * ((size_t)m + 1)));
 	uint32_t *pkeys_in = c->f2d_pkeys.as<uint32_t>(), *pkeys = pkeys_in + mp, *pidx_in = pkeys + mp, *pidx = pidx_in + mp;
 	int *pindex = reinterpret_cast<int *>(pidx + mp);
-	const size_t tree_bytes = sizeof(double2) * (size_t)ntot * (1 + (P + 1)) + sizeof(int) * ((size_t)ntot + (size_t)m + 1);
-	NBCO_TRY(c->reserve(c->f2d_tree, tree_bytes));
-	NBCO_TRY(c->reserve(c->f2d_part, sizeof(double) * (4 * kRedBlocks + 8)));
-	Quad q;
-	q.center = c->f2d_tree.as<double2>();
-	q.mpole = q.center + ntot;
-	q.local = nullptr;
-	q.mult = reinterpret_cast<int *>(q.mpole + ntot * (P + 1));
-	q.index = q.mult + ntot;
-	double *part = c->f2d_part.as<double>(), *scal = part + 4 * kRedBlocks;
-
-	const double2 *x0 = (const double2 *)p, *t0 = (const double2 *)t;
-	const int nbr = std::min(kRedBlocks, grid_blocks(n, kB, kGridCap));
-	hipLaunchKernelGGL(f2d_minmax_kernel, dim3(nbr), dim3(kB), 0, st, x0, n, part);
-	hipLaunchKernelGGL(f2d_scalars_kernel, dim3(1), dim3(64), 0, st, (const double *)part, nbr, side, eps2, scal);
-	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, n, (const double *)scal, side, keys_in, idx_in);
-	NBCO_TRY(sort_pairs(c, c->f2d_tmp, keys_in, keys, idx_in, idx, n, 0u, (unsigned)(2 * L), sizeof(double2) * (size_t)n));
-	double2 *x = c->f2d_tmp.as<double2>();
-	hipLaunchKernelGGL(f2d_gather_pos_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, st, x0, (const uint32_t *)idx, x, n);
-	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)keys, n, m, q.index);
-	f2d_launch_leaf(c, P, q, x, m, quad_beg(L));
-	for (int l = L - 1; l >= 2; --l) f2d_launch_m2m(c, P, q, l);
+	F2dTree tr;
+	NBCO_TRY(f2d_tree_build(c, pl, (const double2 *)p, n, /*with_local*/ false, /*with_c0*/ false, /*state*/ nullptr, /*part_more*/ 0, tr));
 
 	// the clamp of f2d_keys_kernel projects a probe outside the sources' square onto it
-	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(mp, kB, kGridCap)), dim3(kB), 0, st, t0, mp, (const double *)scal, side, pkeys_in, pidx_in);
-	NBCO_TRY(sort_pairs(c, c->f2d_ptmp, pkeys_in, pkeys, pidx_in, pidx, mp, 0u, (unsigned)(2 * L)));
+	const double2 *t0 = (const double2 *)t;
+	hipLaunchKernelGGL(f2d_keys_kernel, dim3(grid_blocks(mp, kB, kGridCap)), dim3(kB), 0, st, t0, mp, tr.scal, pl.side, pkeys_in, pidx_in);
+	NBCO_TRY(sort_pairs(c, c->f2d_ptmp, pkeys_in, pkeys, pidx_in, pidx, mp, 0u, (unsigned)(2 * pl.L)));
 	hipLaunchKernelGGL(f2d_index_kernel, dim3((m + kB) / kB), dim3(kB), 0, st, (const uint32_t *)pkeys, mp, m, pindex);
-	f2d_launch_probe(c, P, q, pindex, pidx, x, t0, L, radius, eps2, param, a, psi);
+	f2d_launch_probe(c, pl.P, tr.q, pindex, pidx, tr.x, t0, pl.L, pl.radius, pl.eps2, param, a, psi);
 	return f2d_done(c);
 }
 
@@ -938,44 +915,7 @@ int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long 
 	auto K = [&](long double s) { return f2d_step(c, v, a, s, n); };
 	auto D = [&](long double s) { return f2d_step(c, x, v, s, n); };
 	auto F = [&]() { return f2d_eval(c, kind, buf, n, param, elastic); };
-	const long double th = 1.3512071919596576340476878089715L;   // integrator.cuh:98
-	const long double xi = +0.1786178958448091E+00L, la = -0.2123418310626054E+00L, ch = -0.6626458266981849E-01L;  // :130-132
-	switch (scheme)
-	{
-	case NBCO_INTEG_EULER:        // integrator.cuh:32
-		NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt)); NBCO_TRY(F());
-		break;
-	case NBCO_INTEG_PRE_EULER:    // :50
-		NBCO_TRY(F()); NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt));
-		break;
-	case NBCO_INTEG_LEAPFROG:     // :68
-	{
-		const long double ds = dt * scale * 0.5L;
-		NBCO_TRY(K(ds)); NBCO_TRY(D(dt)); NBCO_TRY(F()); NBCO_TRY(K(ds));
-		break;
-	}
-	case NBCO_INTEG_FORESTRUTH:   // :100
-	{
-		const long double ds = dt * scale;
-		NBCO_TRY(D(dt * th / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * th))); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * th / 2));
-		break;
-	}
-	case NBCO_INTEG_PEFRL:        // :134
-	{
-		const long double ds = dt * scale;
-		NBCO_TRY(D(dt * xi)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * (1 - 2 * (ch + xi)))); NBCO_TRY(F());
-		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * xi));
-		break;
-	}
-	default:
-		return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown scheme");
-	}
+	NBCO_TRY(integ_compose(scheme, dt, scale, K, D, F));
 	return f2d_done(c);
 }
 

@@ -343,6 +343,29 @@ static int kd_build(nbco_ctx *c, const float *p, long long n, int L, const KdRoo
 	return NBCO_OK;
 }
 
+// build() is a kd_build into `rebuild`.  A flagged build (pivot ties, a missed warm window) is settled right behind it, before anybody
+// consumes the tree: the flag (counter 110) is read back, and demote_build decides how the build is repeated.  A build that cannot
+// be demoted -- a reused tree, the sorting build -- is not read back, unless `must_stand`: then nothing downstream would catch its flag,
+// and a flagged sorting build is an error.
+template <class Build>
+static int kd_build_settled(nbco_ctx *c, Build build, const bool &rebuild, bool must_stand)
+{
+	for (;;)
+	{
+		NBCO_TRY(build());
+		if (!must_stand && !(rebuild && !c->force_sort_build)) return NBCO_OK;
+		int flag = 0;
+		NBCO_HIP(hipMemcpyAsync(&flag, c->counters.as<int>() + 110, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+		NBCO_HIP(hipStreamSynchronize(c->stream));
+		if (!flag)
+		{
+			if (rebuild && c->sel_warm_used) c->note_warm_ok();
+			return NBCO_OK;
+		}
+		if (!c->demote_build() && must_stand) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
+	}
+}
+
 // ---- upward pass of the tree that kd_build has left in c->kd: P2M + M2M (generated register-resident bodies of
 // k_farfield.hip) on the second stream
 static int kd_upward(nbco_ctx *c)
@@ -673,20 +696,8 @@ int kd_energy_fmm(nbco_ctx *c, long long n_own, double *half_phi_sum)
 	const int grid = (int)((le.own_n + kBlock - 1) / kBlock);
 	NBCO_TRY(c->reserve(c->part, sizeof(double) * (size_t)grid));
 	double *part = c->part.as<double>();
-	switch (le.order)
-	{
-	case 1: launch_potential<1>(c, grid, part); break;
-	case 2: launch_potential<2>(c, grid, part); break;
-	case 3: launch_potential<3>(c, grid, part); break;
-	case 4: launch_potential<4>(c, grid, part); break;
-	case 5: launch_potential<5>(c, grid, part); break;
-	case 6: launch_potential<6>(c, grid, part); break;
-	case 7: launch_potential<7>(c, grid, part); break;
-	case 8: launch_potential<8>(c, grid, part); break;
-	case 9: launch_potential<9>(c, grid, part); break;
-	case 10: launch_potential<10>(c, grid, part); break;
-	default: return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_energy_fmm: order");
-	}
+	if (!with_order(le.order, [&](auto p) { with_real(le.real_bytes == 8, [&](auto r) { launch_potential<decltype(p)::value, decltype(r)>(c, grid, part); }); }))
+		return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_energy_fmm: order");
 	NBCO_HIP(hipGetLastError());
 	std::vector<double> h((size_t)grid);
 	NBCO_HIP(hipMemcpyAsync(h.data(), part, sizeof(double) * (size_t)grid, hipMemcpyDeviceToHost, c->stream));
@@ -717,19 +728,10 @@ int kd_potential(nbco_ctx *c, long long n, const float *param, double *psi_dev, 
 	NBCO_TRY(c->reserve(c->pot_c0, sizeof(double) * (size_t)le.ntot));
 	NBCO_TRY(c->reserve(c->pot_slot, sizeof(double) * (size_t)nleaf));
 	double *c0 = c->pot_c0.as<double>(), *slot = c->pot_slot.as<double>(), *out = c->small.as<double>() + 8;
-	switch (le.order)
-	{
-	case 1: launch_kd_psi<1>(c, c0, slot, param, psi_dev); break;
-	case 2: launch_kd_psi<2>(c, c0, slot, param, psi_dev); break;
-	case 3: launch_kd_psi<3>(c, c0, slot, param, psi_dev); break;
-	case 4: launch_kd_psi<4>(c, c0, slot, param, psi_dev); break;
-	case 5: launch_kd_psi<5>(c, c0, slot, param, psi_dev); break;
-	case 6: launch_kd_psi<6>(c, c0, slot, param, psi_dev); break;
-	case 7: launch_kd_psi<7>(c, c0, slot, param, psi_dev); break;
-	case 8: launch_kd_psi<8>(c, c0, slot, param, psi_dev); break;
-	case 9: launch_kd_psi<9>(c, c0, slot, param, psi_dev); break;
-	default: launch_kd_psi<10>(c, c0, slot, param, psi_dev); break;
-	}
+	if (!with_order(le.order, [&](auto p) {
+		    with_real(le.real_bytes == 8, [&](auto r) { launch_kd_psi<decltype(p)::value, decltype(r)>(c, c0, slot, param, psi_dev); });
+	    }))
+		return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_kd_potential: order");   // (kd_potential_check has refused it already)
 	hipLaunchKernelGGL(kd_slot_sum_kernel, dim3(1), dim3(kBlock), 0, c->stream, (const double *)slot, nleaf, out);
 	NBCO_HIP(hipGetLastError());
 	NBCO_HIP(hipMemcpyAsync(half_psi_sum, out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -760,11 +762,8 @@ static int kd_probe_walk(nbco_ctx *c, const ProbeSrc &s, const float *t, long lo
 	NBCO_TRY(sort_pairs(c, c->probe_tmp, keys, keys_alt, idx, perm, m, 0u, 30u));
 	// (the table belongs to the tree: its order and particle count, not the options of this moment)
 	const AdmTab tab = kd_adm_table(s.n, s.L, s.order);
-	const bool f64 = s.real_bytes == 8;
-	with_order(s.order, [&](auto pc) {
-		constexpr int P = decltype(pc)::value;
-		if (f64) launch_probe_walk_t<P, double>(c, s, tab, perm, t, m, param, a, psi);
-		else launch_probe_walk_t<P, float>(c, s, tab, perm, t, m, param, a, psi);
+	with_order(s.order, [&](auto p) {
+		with_real(s.real_bytes == 8, [&](auto r) { launch_probe_walk<decltype(p)::value, decltype(r)>(c, s, tab, perm, t, m, param, a, psi); });
 	});
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
@@ -781,50 +780,38 @@ int kd_probe_check(nbco_ctx *c)
 	return NBCO_OK;
 }
 
+// what the walk needs of `tree` -- a KdTreeDev, or the LastEval that points into one -- with the root box of the context's tree
+template <class Tree>
+static ProbeSrc probe_src(const nbco_ctx *c, const Tree &tree, const float4 *pos, long long n)
+{
+	ProbeSrc s;
+	s.csz = tree.csz; s.pos = pos; s.mpole = tree.mpole; s.mult = tree.mult; s.index = tree.index;
+	s.lbound = c->kd.lbound; s.rbound = c->kd.rbound;
+	s.L = tree.L; s.ntot = tree.ntot; s.order = tree.order; s.real_bytes = tree.real_bytes; s.n = n;
+	return s;
+}
+
 // the walk over the tree, multipoles and tree-ordered positions of the last evaluation (the caller has run kd_probe_check); nothing of
 // that evaluation is written
 int kd_probe_last(nbco_ctx *c, const float *t, long long m, const float *param, double *a, double *psi)
 {
 	const nbco_ctx::LastEval &le = c->last_eval;
-	ProbeSrc s;
-	s.csz = le.csz; s.pos = le.pos; s.mpole = le.mpole; s.mult = le.mult; s.index = le.index;
-	s.lbound = c->kd.lbound; s.rbound = c->kd.rbound;   // (not sharded: the tree is the context's own)
-	s.L = le.L; s.ntot = le.ntot; s.order = le.order; s.real_bytes = le.real_bytes; s.n = le.n;
-	return kd_probe_walk(c, s, t, m, param, a, psi);
+	return kd_probe_walk(c, probe_src(c, le, le.pos, le.n), t, m, param, a, psi);   // (not sharded: the root box is that of the context's own tree)
 }
 
-// nbco_probe_tree, on the private context: tree and multipoles over x[0..n) and the walk.  The probes need kd_build + kd_upward only,
-// and a flagged build (pivot ties, a missed warm window) is settled right behind the build, the way a kd-domain's local build settles
-// it before its exchange (kd_dist_local_build): the flag is read back, and demote_build decides how the build is repeated.
+// nbco_probe_tree, on the private context: tree and multipoles over x[0..n) and the walk.  The probes need kd_build + kd_upward only.
 int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long m, const float *param, double *a, double *psi)
 {
 	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
 	c->last_eval.valid = false;   // the lists of an earlier evaluation belong to another tree
 	bool rebuild = false;
-	for (;;)
-	{
-		NBCO_TRY(kd_build(c, x, n, L, KdRoot{}, rebuild, nullptr));
-		int flag = 0;
-		NBCO_HIP(hipMemcpyAsync(&flag, c->counters.as<int>() + 110, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-		NBCO_HIP(hipStreamSynchronize(c->stream));
-		if (!flag)
-		{
-			if (rebuild && c->sel_warm_used) c->note_warm_ok();
-			break;
-		}
-		if (!c->demote_build()) return c->fail(NBCO_ERR_UNSUPPORTED, "kd-tree build: tie flag raised by the sorting build");
-	}
+	NBCO_TRY(kd_build_settled(c, [&] { return kd_build(c, x, n, L, KdRoot{}, rebuild, nullptr); }, rebuild, true));
 	NBCO_TRY(kd_upward(c));
 	NBCO_TRY(c->join_aux());
 	c->tree_valid = true;   // (the boxes in the tree arrays are this build's: the next build of the same shape may select around them)
 	c->tree_n = n;
 	c->tree_order = c->kd.order;
-	const KdTreeDev &k = c->kd;
-	ProbeSrc s;
-	s.csz = k.csz; s.pos = c->pos4.as<float4>(); s.mpole = k.mpole; s.mult = k.mult; s.index = k.index;
-	s.lbound = k.lbound; s.rbound = k.rbound;
-	s.L = k.L; s.ntot = k.ntot; s.order = k.order; s.real_bytes = k.real_bytes; s.n = n;
-	return kd_probe_walk(c, s, t, m, param, a, psi);
+	return kd_probe_walk(c, probe_src(c, c->kd, c->pos4.as<float4>(), n), t, m, param, a, psi);
 }
 
 // kd_fields has returned `rc`: twice the room for the lists (the caller's arrays are untouched), or reaction records sized from the

@@ -8,6 +8,7 @@
 // component c of the current target; a target's local expansion is stored exactly once, by one lane
 // per component, in a fixed order: no atomics, bit-reproducible.
 #include "nbco_internal.hpp"
+#include "dispatch.hpp"
 
 namespace {
 
@@ -135,20 +136,8 @@ static void launch(nbco_ctx *c, const float4 *csz, const T *mpole, T *local, con
 template <typename T>
 static int dispatch(nbco_ctx *c, int P, const float4 *csz, const T *mpole, T *local, const uint64_t *keys, const int *start, int shift, int ntot, int mstride)
 {
-	switch (P)
-	{
-	case 1: launch<1, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 2: launch<2, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 3: launch<3, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 4: launch<4, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 5: launch<5, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 6: launch<6, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 7: launch<7, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 8: launch<8, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 9: launch<9, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	case 10: launch<10, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); break;
-	default: return c->fail(NBCO_ERR_UNSUPPORTED, "launch_m2l_lanes: order not generated");
-	}
+	if (!with_order(P, [&](auto p) { launch<decltype(p)::value, T>(c, csz, mpole, local, keys, start, shift, ntot, mstride); }))
+		return c->fail(NBCO_ERR_UNSUPPORTED, "launch_m2l_lanes: order not generated");
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }

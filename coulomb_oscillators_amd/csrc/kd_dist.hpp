@@ -254,18 +254,10 @@ int kd_dist_local_build(nbco_ctx *c, float *buf_local, long long n_local, void *
 	const KdRoot root{root6, d > 0 ? top.splitdim : nullptr, (1 << d) + lay.rank};
 	KdStepLink link;
 	std::swap(link.prep_done, c->dist.prep_done);   // nbco_dist_turnaround's mark: this is the build it was made for
-	NBCO_TRY(kd_build(c, buf_local, n_local, lay.L_local, root, rebuild, &link));
-	while (rebuild && !c->force_sort_build && !let)
-	{
-		// A tie overflow of the selection build has to be caught BEFORE the exchange (the other domains are
-		// about to consume these positions and nodes); the retry with a more conservative build is purely local.
-		int flag = 0;
-		NBCO_HIP(hipMemcpyAsync(&flag, c->counters.as<int>() + 110, sizeof(int), hipMemcpyDeviceToHost, st));
-		NBCO_HIP(hipStreamSynchronize(st));
-		if (!flag) { if (c->sel_warm_used) c->note_warm_ok(); break; }
-		c->demote_build();   // (the loop ends with the sorting build)
-		NBCO_TRY(kd_build(c, buf_local, n_local, lay.L_local, root, rebuild, &link));
-	}
+	// A tie overflow of the selection build has to be caught BEFORE the exchange (the other domains are about to consume these
+	// positions and nodes); the retry with a more conservative build is purely local.  (let: the flags travel with the LET counts.)
+	auto build = [&] { return kd_build(c, buf_local, n_local, lay.L_local, root, rebuild, &link); };
+	NBCO_TRY(let ? build() : kd_build_settled(c, build, rebuild, false));
 	c->dist.rebuilt = rebuild;
 	if (pos_send) NBCO_HIP(hipMemcpyAsync(pos_send, c->pos4.ptr, sizeof(float4) * (size_t)n_local, hipMemcpyDeviceToDevice, st));
 	if (csz_send) NBCO_HIP(hipMemcpyAsync(csz_send, c->kd.csz, sizeof(float4) * (size_t)lay.ntot_local, hipMemcpyDeviceToDevice, st));

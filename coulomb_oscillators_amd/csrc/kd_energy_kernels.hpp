@@ -103,16 +103,11 @@ __global__ __launch_bounds__(kBlock) void kd_potential_kernel(nbco_ctx::LastEval
 	}
 }
 
-template <int P> static void launch_potential(nbco_ctx *c, int grid, double *part)
+// (T: the multipoles of the last evaluation are doubles when it ran with opts.far_fp64: LastEval::real_bytes)
+template <int P, typename T> static void launch_potential(nbco_ctx *c, int grid, double *part)
 {
-	// (the multipoles of the last evaluation are doubles when it ran with opts.far_fp64: LastEval::real_bytes)
-	if (c->last_eval.real_bytes == 8)
-		hipLaunchKernelGGL((kd_potential_kernel<P, double>), dim3(grid), dim3(kBlock), 0, c->stream, c->last_eval, (const uint64_t *)c->m2l_keys_alt.as<uint64_t>(),
-		                   (const int *)c->m2l_start.as<int>(), (const uint64_t *)c->p2p_keys_alt.as<uint64_t>(), (const int *)c->p2p_start.as<int>(), c->o.eps2,
-		                   part);
-	else
-		hipLaunchKernelGGL((kd_potential_kernel<P, float>), dim3(grid), dim3(kBlock), 0, c->stream, c->last_eval, (const uint64_t *)c->m2l_keys_alt.as<uint64_t>(),
-		                   (const int *)c->m2l_start.as<int>(), (const uint64_t *)c->p2p_keys_alt.as<uint64_t>(), (const int *)c->p2p_start.as<int>(), c->o.eps2,
-		                   part);
+	hipLaunchKernelGGL((kd_potential_kernel<P, T>), dim3(grid), dim3(kBlock), 0, c->stream, c->last_eval, (const uint64_t *)c->m2l_keys_alt.as<uint64_t>(),
+	                   (const int *)c->m2l_start.as<int>(), (const uint64_t *)c->p2p_keys_alt.as<uint64_t>(), (const int *)c->p2p_start.as<int>(), c->o.eps2,
+	                   part);
 }
 

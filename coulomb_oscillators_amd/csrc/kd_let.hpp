@@ -327,10 +327,10 @@ static int let_pack_segments(nbco_ctx *c, const nbco_dist_layout &lay, const lon
 	const bool f64 = c->kd.real_bytes == 8;
 	if (capped && nmax + lmax > 0)
 	{
-		if (f64) hipLaunchKernelGGL(let_pad_kernel<double>, dim3(grid1d(nmax + lmax, 256), G), dim3(kBlock), 0, c->stream, (const int *)v.cursors, nb, pb, rec,
-		                            (double *)mpole_send, (float4 *)pos_send);
-		else hipLaunchKernelGGL(let_pad_kernel<float>, dim3(grid1d(nmax + lmax, 256), G), dim3(kBlock), 0, c->stream, (const int *)v.cursors, nb, pb, rec,
-		                        (float *)mpole_send, (float4 *)pos_send);
+		with_real(f64, [&](auto r) {
+			hipLaunchKernelGGL(let_pad_kernel<decltype(r)>, dim3(grid1d(nmax + lmax, 256), G), dim3(kBlock), 0, c->stream, (const int *)v.cursors, nb, pb, rec,
+			                   (decltype(r) *)mpole_send, (float4 *)pos_send);
+		});
 	}
 	if (lmax > 0)   // (an upper bound of the lane count: every selected leaf holds at least one particle)
 		hipLaunchKernelGGL(let_pack_pos_kernel, dim3(grid1d(lmax << wlog, 2048), G), dim3(kBlock), 0, c->stream, (const float4 *)c->pos4.as<float4>(),
@@ -338,14 +338,10 @@ static int let_pack_segments(nbco_ctx *c, const nbco_dist_layout &lay, const lon
 		                   (const int *)v.cursors, pb, (float4 *)pos_send);
 	NBCO_TRY(c->join_aux());   // the upward pass
 	if (nmax > 0)
-	{
-		if (f64)
-			hipLaunchKernelGGL(let_pack_mpole_kernel<double>, dim3(grid1d(nmax * rec, 2048), G), dim3(kBlock), 0, c->stream, (const double *)c->kd.mpole, offM, rec,
-			                   lay.ntot_local, lay.d, lay.rank, (const int *)v.sel_node, (const int *)v.cursors, nb, (double *)mpole_send);
-		else
-			hipLaunchKernelGGL(let_pack_mpole_kernel<float>, dim3(grid1d(nmax * rec, 2048), G), dim3(kBlock), 0, c->stream, (const float *)c->kd.mpole, offM, rec,
-			                   lay.ntot_local, lay.d, lay.rank, (const int *)v.sel_node, (const int *)v.cursors, nb, (float *)mpole_send);
-	}
+		with_real(f64, [&](auto r) {
+			hipLaunchKernelGGL(let_pack_mpole_kernel<decltype(r)>, dim3(grid1d(nmax * rec, 2048), G), dim3(kBlock), 0, c->stream, (const decltype(r) *)c->kd.mpole,
+			                   offM, rec, lay.ntot_local, lay.d, lay.rank, (const int *)v.sel_node, (const int *)v.cursors, nb, (decltype(r) *)mpole_send);
+		});
 	NBCO_HIP(hipGetLastError());
 	c->dist.let_packed = true;
 	c->dist.let_capped = capped;
@@ -527,8 +523,9 @@ static int dist_finish_rest(nbco_ctx *c, const char *mp_blocks, size_t mp_stride
 		const bool f64 = g.real_bytes == 8;   // (dist_global_tree carved the global arrays under the same opts.far_fp64 as the local tree)
 		auto unpack_blocks = [&](const char *blocks, size_t stride, int nblocks, int r0) {
 			const int grid = grid1d((long long)nblocks * lay.ntot_local * offM);
-			if (f64) hipLaunchKernelGGL(dist_unpack_mpole_kernel<double>, dim3(grid), dim3(kBlock), 0, c->stream, tv, blocks, stride, lay.ntot_local, nblocks, r0, d, offM);
-			else hipLaunchKernelGGL(dist_unpack_mpole_kernel<float>, dim3(grid), dim3(kBlock), 0, c->stream, tv, blocks, stride, lay.ntot_local, nblocks, r0, d, offM);
+			with_real(f64, [&](auto r) {
+				hipLaunchKernelGGL(dist_unpack_mpole_kernel<decltype(r)>, dim3(grid), dim3(kBlock), 0, c->stream, tv, blocks, stride, lay.ntot_local, nblocks, r0, d, offM);
+			});
 		};
 		if (offM > 0 && !let_counts) unpack_blocks(mp_blocks, mp_stride, G, 0);
 		if (offM > 0 && let_counts)
@@ -536,14 +533,10 @@ static int dist_finish_rest(nbco_ctx *c, const char *mp_blocks, size_t mp_stride
 			// the own subtree straight from the local tree, the rest from the records
 			unpack_blocks((const char *)c->kd.mpole, (size_t)0, 1, lay.rank);
 			if (nodes_in > 0)
-			{
-				if (f64)
-					hipLaunchKernelGGL(let_unpack_mpole_kernel<double>, dim3(grid1d(nodes_in * rec, 4096)), dim3(kBlock), 0, c->stream, (const double *)mp_blocks, nodes_in, rec,
-					                   offM, g.ntot, (double *)tv.mpole, const_cast<unsigned char *>(have.node));
-				else
-					hipLaunchKernelGGL(let_unpack_mpole_kernel<float>, dim3(grid1d(nodes_in * rec, 4096)), dim3(kBlock), 0, c->stream, (const float *)mp_blocks, nodes_in, rec,
-					                   offM, g.ntot, tv.mpole, const_cast<unsigned char *>(have.node));
-			}
+				with_real(f64, [&](auto r) {
+					hipLaunchKernelGGL(let_unpack_mpole_kernel<decltype(r)>, dim3(grid1d(nodes_in * rec, 4096)), dim3(kBlock), 0, c->stream, (const decltype(r) *)mp_blocks,
+					                   nodes_in, rec, offM, g.ntot, (decltype(r) *)tv.mpole, const_cast<unsigned char *>(have.node));
+				});
 		}
 		if (d > 0) NBCO_TRY(launch_m2m_top_gen(c, P, tv.center, tv.mpole, tv.mult, d - 1, L, 0, f64 ? 1 : 0));
 		NBCO_HIP(hipGetLastError());

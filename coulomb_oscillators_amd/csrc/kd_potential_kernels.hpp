@@ -163,8 +163,9 @@ __global__ __launch_bounds__(kBlock) void kd_slot_sum_kernel(const double *__res
 	if (threadIdx.x == 0) out[0] = 0.5 * sh[0];
 }
 
+// (T: multipoles and locals of the last evaluation are doubles when it ran with opts.far_fp64: LastEval::real_bytes)
 template <int P, typename T>
-static void launch_kd_psi_t(nbco_ctx *c, double *c0, double *slot, const float *param, double *psi_out)
+static void launch_kd_psi(nbco_ctx *c, double *c0, double *slot, const float *param, double *psi_out)
 {
 	const nbco_ctx::LastEval &le = c->last_eval;
 	const T *mpole = reinterpret_cast<const T *>(le.mpole), *local = reinterpret_cast<const T *>(le.local);
@@ -176,10 +177,4 @@ static void launch_kd_psi_t(nbco_ctx *c, double *c0, double *slot, const float *
 	hipLaunchKernelGGL((kd_psi_leaf_kernel<P, T>), dim3(kd_cnt(le.L)), dim3(kPotWave), 0, st, le, local, (const double *)c0,
 	                   (const uint64_t *)c->p2p_keys_alt.as<uint64_t>(), (const int *)c->p2p_start.as<int>(), c->o.eps2, param, le.scatter ? le.unsort : nullptr,
 	                   psi_out, slot);
-}
-template <int P> static void launch_kd_psi(nbco_ctx *c, double *c0, double *slot, const float *param, double *psi_out)
-{
-	// (multipoles and locals of the last evaluation are doubles when it ran with opts.far_fp64: LastEval::real_bytes)
-	if (c->last_eval.real_bytes == 8) launch_kd_psi_t<P, double>(c, c0, slot, param, psi_out);
-	else launch_kd_psi_t<P, float>(c, c0, slot, param, psi_out);
 }

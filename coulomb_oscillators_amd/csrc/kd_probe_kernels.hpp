@@ -258,8 +258,8 @@ struct ProbeSrc
 };
 
 template <int P, typename T>
-static void launch_probe_walk_t(nbco_ctx *c, const ProbeSrc &s, const AdmTab &tab, const uint32_t *perm, const float *t, long long m, const float *param,
-                                double *a, double *psi)
+static void launch_probe_walk(nbco_ctx *c, const ProbeSrc &s, const AdmTab &tab, const uint32_t *perm, const float *t, long long m, const float *param,
+                              double *a, double *psi)
 {
 	const dim3 grid((unsigned)((m + kProbeWave - 1) / kProbeWave)), block(kProbeWave);
 	with_outputs(a, psi, [&](auto wa, auto wp) {

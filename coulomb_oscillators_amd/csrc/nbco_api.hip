@@ -2,6 +2,7 @@
 // of compute_force (integrator.cuh:22-28 over main3.cu:47-69) and the symplectic integrators
 // (integrator.cuh:32-167).
 #include "nbco_internal.hpp"
+#include "integ_compose.hpp"
 #include <chrono>
 #include <cstdio>
 #include <cmath>
@@ -551,19 +552,10 @@ int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, c
 		}
 		return (int)NBCO_OK;
 	};
-	const long double th = 1.3512071919596576340476878089715L;   // integrator.cuh:98
-	const long double xi = +0.1786178958448091E+00L, la = -0.2123418310626054E+00L, ch = -0.6626458266981849E-01L;  // :130-132
-	switch (scheme)
+	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, "unknown integrator scheme");
+	if (scheme == NBCO_INTEG_LEAPFROG)
 	{
-	case NBCO_INTEG_EULER:
-		NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt)); NBCO_TRY(F());
-		break;
-	case NBCO_INTEG_PRE_EULER:
-		NBCO_TRY(F()); NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt));
-		break;
-	case NBCO_INTEG_LEAPFROG:
-	{
-		long double ds = dt * scale * 0.5L;
+		const long double ds = dt * scale * 0.5L;
 		{
 			// K(ds) D(dt) fused into one pass over x, v, a
 			PhaseScope ph(c, NBCO_PH_AXPY);
@@ -571,30 +563,8 @@ int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, c
 		}
 		KdStepLink link;
 		NBCO_TRY(closing_kick(c, link, [&] { return eval_kind(c, kind, x, a, n, param, &link); }, buf, n, param, (float)ds, elastic != 0));
-		break;
 	}
-	case NBCO_INTEG_FORESTRUTH:
-	{
-		long double ds = dt * scale;
-		NBCO_TRY(D(dt * th / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * th))); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * th / 2));
-		break;
-	}
-	case NBCO_INTEG_PEFRL:
-	{
-		long double ds = dt * scale;
-		NBCO_TRY(D(dt * xi)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * (1 - 2 * (ch + xi)))); NBCO_TRY(F());
-		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * xi));
-		break;
-	}
-	default:
-		return c->fail(NBCO_ERR_ARG, "unknown integrator scheme");
-	}
+	else NBCO_TRY(integ_compose(scheme, dt, scale, K, D, F));
 	return maybe_sync(c);
 }
 
@@ -745,23 +715,32 @@ int nbco_kd_potential(nbco_ctx *c, const float *buf, long long n, const float *p
 	return energy_from_potential(c, buf, n, param, out3_host, phi_dev);
 }
 
-int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev)
+// The private context of nbco_energy_tree and nbco_probe_tree (`who`), created on first use: everything of theirs runs on it, and this
+// context's tree, lists, schedule and bookkeeping are not touched.  The child follows this context's expansion and tree options
+// (re-read at every call) and always rebuilds, in the caller's particle order.
+static int private_child(nbco_ctx *c, const char *who, nbco_ctx *&k)
 {
-	if (!c || !buf || !param || !out3_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_energy_tree: null pointer") : NBCO_ERR_ARG;
-	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_energy_tree: n must be positive");
-	if (n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_energy_tree: n too large for 32-bit tree indices");
-	// Everything runs on a private context: this one's tree, lists, schedule and bookkeeping are not touched.  The child follows
-	// this context's expansion and tree options (re-read here) and always rebuilds, in the caller's particle order.
 	nbco_opts o = c->o;
 	o.unsort = 1; o.tree_steps = 1; o.track_order = 0; o.p2p_mutual = 0; o.coll = 1; o.sync = 0;
 	if (!c->energy_child)
 	{
 		const int rc = nbco_create(&c->energy_child, &o);
-		if (rc != NBCO_OK) return c->fail(rc, "nbco_energy_tree: could not create the private context");
+		if (rc != NBCO_OK) return c->fail(rc, std::string(who) + ": could not create the private context");
 	}
-	nbco_ctx *k = c->energy_child;
+	k = c->energy_child;
+	const int rc = nbco_set_opts(k, &o);
+	if (rc != NBCO_OK) return c->fail(rc, std::string(who) + ": " + k->err);
+	return NBCO_OK;
+}
+
+int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev)
+{
+	if (!c || !buf || !param || !out3_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_energy_tree: null pointer") : NBCO_ERR_ARG;
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_energy_tree: n must be positive");
+	if (n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_energy_tree: n too large for 32-bit tree indices");
+	nbco_ctx *k;
+	NBCO_TRY(private_child(c, "nbco_energy_tree", k));
 	auto pass = [&]() -> int {
-		NBCO_TRY(nbco_set_opts(k, &o));
 		// scratch copy of the positions + room for the accelerations the evaluation writes
 		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 6 * (size_t)n));
 		float *x = k->pot_xa.as<float>(), *a = x + 3 * n;
@@ -806,18 +785,9 @@ int nbco_kd_probe(nbco_ctx *c, const float *t, long long m, const float *param, 
 int nbco_probe_tree(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a_dev, double *psi_dev)
 {
 	NBCO_TRY(probe_args(c, "nbco_probe_tree", true, p, n, t, m, param, a_dev, psi_dev));
-	// nbco_energy_tree's private context (this one's tree, lists, schedule and bookkeeping are not touched), under this context's
-	// expansion and tree options, re-read here; it always rebuilds, in the caller's particle order
-	nbco_opts o = c->o;
-	o.unsort = 1; o.tree_steps = 1; o.track_order = 0; o.p2p_mutual = 0; o.coll = 1; o.sync = 0;
-	if (!c->energy_child)
-	{
-		const int rc = nbco_create(&c->energy_child, &o);
-		if (rc != NBCO_OK) return c->fail(rc, "nbco_probe_tree: could not create the private context");
-	}
-	nbco_ctx *k = c->energy_child;
+	nbco_ctx *k;
+	NBCO_TRY(private_child(c, "nbco_probe_tree", k));
 	auto pass = [&]() -> int {
-		NBCO_TRY(nbco_set_opts(k, &o));
 		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
 		float *x = k->pot_xa.as<float>();
 		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));

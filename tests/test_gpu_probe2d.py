@@ -354,6 +354,42 @@ def test_one_context_serves_probes_between_energy_calls(engine, oracle32):
     assert np.array_equal(second[0], fourth[0]) and np.array_equal(second[1], fourth[1])
 
 
+def test_one_context_interleaves_the_three_tree_users(engine):
+    """nbco_2d_fmm, nbco_2d_probe_fmm and nbco_2d_energy_fmm lay the same scratch buffers out in three ways (with locals; without; with
+    locals and the potential's constants).  One context serves them in turn at changing n, order and depth: every result --
+    accelerations and reordered state, the three energies and psi, field and potential -- is finite and bit for bit a fresh context's"""
+    import torch
+    from coulomb_oscillators_amd import Engine
+
+    def fmm(e, n, m):
+        d, a = _dev(_kv(n)), torch.full((2 * n,), float("nan"), dtype=torch.float64, device="cuda")
+        e.fmm_2d(d, a, n, _dev(_param(n)))
+        return a.cpu().numpy(), d.cpu().numpy()
+
+    def energy(e, n, m):
+        psi = torch.full((n,), float("nan"), dtype=torch.float64, device="cuda")
+        return e.energy_fmm_2d(_dev(_kv(n)), n, _dev(_param(n)), psi), psi.cpu().numpy()
+
+    def probe(e, n, m):
+        return _call(e.probe_fmm_2d, _kv(n)[0], _around_beam(m), _param(n))
+
+    small = dict(fmm_order=7, tree_L=2)
+    steps = [(fmm, 3000, 0, dict(fmm_order=3)), (probe, 300, 65, small), (energy, 6000, 0, dict(fmm_order=5)), (fmm, 300, 0, small),
+             (energy, 3000, 0, dict(fmm_order=3)), (probe, 6000, 257, dict(fmm_order=5))]
+    got = []
+    for call, n, m, o in steps:
+        engine.set(**dict(BASE, **o))
+        got.append(call(engine, n, m))
+    for (call, n, m, o), g in zip(steps, got):
+        fresh = Engine(**dict(BASE, **o))
+        try:
+            want = call(fresh, n, m)
+        finally:
+            fresh.close()
+        for x, y in zip(g, want):
+            assert np.isfinite(x).all() and np.array_equal(x, y), (call.__name__, n, m, o)
+
+
 # ---- 6. the command line --------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def nbco(engine_lib):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import probe3d_numpy as p3
+import shapes3d
 
 pytestmark = pytest.mark.gpu
 
@@ -293,13 +294,19 @@ def test_side_stream_without_sync(states):
         assert np.isfinite(x).all() and np.array_equal(x, y)
 
 
-@pytest.mark.parametrize("opts", [dict(fmm_order=6), dict(fmm_order=4, far_fp64=1, tree_radius=1.5), dict(fmm_order=3, tree_L=5, eps2=1e-6)])
-def test_probe_tree_is_probe_kd_on_a_fresh_context(states, opts):
+@pytest.mark.parametrize("opts", [dict(fmm_order=6), dict(fmm_order=4, far_fp64=1, tree_radius=1.5), dict(fmm_order=3, tree_L=5, eps2=1e-6),
+                                  dict(fmm_order=4, shape="quant16")])
+def test_probe_tree_is_probe_kd_on_a_fresh_context(states, oracle32, opts):
     """in any state of the engine -- here before any evaluation, after nbco_direct and after an unsort = 0 run -- bit for bit what a
-    fresh context gives behind its own unsort = 1 evaluation"""
+    fresh context gives behind its own unsort = 1 evaluation.  shape: the sources are that shape of tests/shapes3d.py instead of the
+    ball; quant16's tied coordinates flag the selection builds, so that probe_tree settles its build by demotion"""
     from coulomb_oscillators_amd import Engine, EVAL_FMM_KDTREE, INTEG_PEFRL
     n = 4096
     buf, par = states(n)
+    opts = dict(opts)
+    shape = opts.pop("shape", None)
+    if shape:
+        buf = shapes3d.state(oracle32, shape, n)
     t = np.concatenate(list(p3.probe_sets(buf[0], 5).values()))
     m = len(t)
     d, prm, td = dev(buf), dev(par), dev(t)
@@ -307,6 +314,8 @@ def test_probe_tree_is_probe_kd_on_a_fresh_context(states, opts):
     eng = Engine(unsort=0, tree_steps=8, m2l_first=1, p2p_mutual=1, **opts)
     try:
         fresh.compute_force(EVAL_FMM_KDTREE, d.clone(), n, prm)
+        if shape == "quant16":   # the same cold build as probe_tree's: flagged twice, demoted to the sorting build
+            assert fresh.kd_info().build_mode == 2
         want = run(fresh.probe_kd, td, m, prm)
         got = run(eng.probe_tree, d[0], n, td, m, prm)
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
