@@ -685,6 +685,9 @@ static int kd_finish_order(nbco_ctx *c, float *p, long long n, KdStepLink *link)
 #include "kd_energy_kernels.hpp"   // FMM potential energy: multipole-to-particle potential and the per-particle pass
 #include "kd_potential_kernels.hpp"   // O(N) potential pass over the locals: per-node c0, downward, per-leaf psi, slot sum
 #include "kd_probe_kernels.hpp"   // probes: acceptance of a node by a point, multipole to point (field + potential), exact sums, keys, the walk
+#define NBCO_PAIR_STAT_WALK
+#include "pair_stat_kernels.hpp"   // pair statistics: the pair rule, the range-limited walk, the count of the pairs outside
+#undef NBCO_PAIR_STAT_WALK
 } // namespace
 
 // sum over the own particles of phi_i / 2 (the caller multiplies by param[0] = xi / N)
@@ -812,6 +815,45 @@ int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long 
 	c->tree_n = n;
 	c->tree_order = c->kd.order;
 	return kd_probe_walk(c, probe_src(c, c->kd, c->pos4.as<float4>(), n), t, m, param, a, psi);
+}
+
+// nbco_pair_hist_tree, on the private context: the tree over x[0..n) -- kd_build only: no upward pass, no traversal, no lists -- and
+// the range-limited walk over its boxes.  nn2 is written for every particle; the counts are cleared first and closed with the pairs outside.
+int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts, double *nn2)
+{
+	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
+	// The build finishes every leaf inside one workgroup's LDS slice of kSubS particles.  A tree_L that leaves more than that per
+	// leaf overruns the slice, and the unsort map that comes out of it is not a permutation: refused here, before anything is
+	// launched, because this walk scatters nn2 through that map.
+	if (((n + (1LL << L) - 1) >> L) > kSubS)
+		return c->fail(NBCO_ERR_UNSUPPORTED, "tree_L leaves more than " + std::to_string(kSubS) + " particles per leaf: the kd-tree build cannot hold them");
+	c->last_eval.valid = false;   // the lists of an earlier evaluation belong to another tree
+	bool rebuild = false;
+	NBCO_TRY(kd_build_settled(c, [&] { return kd_build(c, x, n, L, KdRoot{}, rebuild, nullptr); }, rebuild, true));
+	c->tree_valid = true;   // (the boxes in the tree arrays are this build's: the next build of the same shape may select around them)
+	c->tree_n = n;
+	c->tree_order = c->kd.order;
+	if (counts) NBCO_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * ((size_t)pb.bins + 1), c->stream));
+	// the LDS histogram while its 32-bit counters cannot wrap (a workgroup bins fewer than kPairWgParticles * n pairs) and the bins fit
+	const bool lds = pb.bins <= kPairLdsBins && (unsigned long long)kPairWgParticles * (unsigned long long)n < (1ull << 32);
+	const dim3 grid((unsigned)((n + kPairWgParticles - 1) / kPairWgParticles)), block(64 * kPairWalkWaves);
+	const KdTreeDev &k = c->kd;
+	const double R2m = pb.R2 * (1.0 + 1e-9);
+	auto launch = [&](auto use_lds) {
+		constexpr bool LDS = decltype(use_lds)::value;
+		const size_t bytes = LDS && counts ? sizeof(unsigned) * (size_t)pb.bins : 0;
+		with_outputs((const double *)counts, nn2, [&](auto wc, auto wn) {
+			hipLaunchKernelGGL((kd_pair_walk_kernel<LDS, decltype(wc)::value, decltype(wn)::value>), grid, block, bytes, c->stream, (const float *)k.lbound,
+			                   (const float *)k.rbound, (const int *)k.mult, (const int *)k.index, (const float4 *)c->pos4.as<float4>(),
+			                   (const int *)c->unsort.as<int>(), k.ntot, n, pb, R2m, counts, nn2);
+		});
+	};
+	if (lds) launch(std::true_type{});
+	else launch(std::false_type{});
+	if (counts)
+		hipLaunchKernelGGL(pair_outside_kernel, dim3(1), dim3(kBlock), 0, c->stream, counts, pb.bins, (unsigned long long)n * (unsigned long long)(n - 1) / 2ull);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
 }
 
 // kd_fields has returned `rc`: twice the room for the lists (the caller's arrays are untouched), or reaction records sized from the

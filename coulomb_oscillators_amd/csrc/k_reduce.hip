@@ -4,6 +4,8 @@
 // Pattern: grid-stride loads -> wave64 shuffle reduction -> LDS across the 4 waves of a block ->
 // one partial per block -> last stage in a single block (deterministic, no float atomics).
 #include "nbco_internal.hpp"
+#include "dispatch.hpp"
+#include <algorithm>
 #include <cfloat>
 
 namespace {
@@ -174,6 +176,9 @@ static int grid_for(long long n)
 }
 
 #include "beam_diag_kernels.hpp"   // beam diagnostics: the two moment passes and the histogram kernel
+#define NBCO_PAIR_STAT_EXACT
+#include "pair_stat_kernels.hpp"   // pair statistics: the pair rule, the all-pairs kernel, the count of the pairs outside
+#undef NBCO_PAIR_STAT_EXACT
 
 } // namespace
 
@@ -353,6 +358,40 @@ int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_h
 	NBCO_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * (size_t)(B + 1), c->stream));
 	if (dim == 3) hist_run<float, 3>(c, (const float *)buf, n, ax, (int)B, counts);
 	else hist_run<double, 2>(c, (const double *)buf, n, ax, (int)B, counts);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// ---- pair statistics, exact forms (pair_stat_kernels.hpp) ---------------------------------------
+template <class T, int D, bool LDS> static void pair_hist_run(nbco_ctx *c, const T *p, long long n, const PairBins &pb, unsigned long long *counts, double *nn2)
+{
+	const long long nt = (n + kBlock - 1) / kBlock, chunks = (nt + kPairSrcTiles - 1) / kPairSrcTiles;
+	const dim3 grid((unsigned)nt, (unsigned)std::min<long long>(chunks, kPairGridY));
+	const size_t lds = LDS && counts ? sizeof(unsigned) * (size_t)pb.bins : 0;
+	// (with_outputs looks only at which of the two pointers are given: a NULL output is compiled out)
+	with_outputs((const double *)counts, nn2, [&](auto wc, auto wn) {
+		hipLaunchKernelGGL((pair_hist_kernel<T, D, LDS, decltype(wc)::value, decltype(wn)::value>), grid, dim3(kBlock), lds, c->stream, p, n, pb, counts,
+		                   reinterpret_cast<unsigned long long *>(nn2));
+	});
+}
+
+int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const PairBins &pb, unsigned long long *counts, double *nn2)
+{
+	if (counts) NBCO_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * ((size_t)pb.bins + 1), c->stream));
+	if (nn2) hipLaunchKernelGGL(pair_fill_kernel, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, reinterpret_cast<unsigned long long *>(nn2), n, kPairInfBits);
+	const bool lds = pb.bins <= kPairLdsBins;
+	if (dim == 3)
+	{
+		if (lds) pair_hist_run<float, 3, true>(c, (const float *)p, n, pb, counts, nn2);
+		else pair_hist_run<float, 3, false>(c, (const float *)p, n, pb, counts, nn2);
+	}
+	else
+	{
+		if (lds) pair_hist_run<double, 2, true>(c, (const double *)p, n, pb, counts, nn2);
+		else pair_hist_run<double, 2, false>(c, (const double *)p, n, pb, counts, nn2);
+	}
+	if (counts)
+		hipLaunchKernelGGL(pair_outside_kernel, dim3(1), dim3(kBlock), 0, c->stream, counts, pb.bins, (unsigned long long)n * (unsigned long long)(n - 1) / 2ull);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }

@@ -3,6 +3,7 @@
 // (integrator.cuh:32-167).
 #include "nbco_internal.hpp"
 #include "integ_compose.hpp"
+#include <cfloat>
 #include <chrono>
 #include <cstdio>
 #include <cmath>
@@ -795,6 +796,62 @@ int nbco_probe_tree(nbco_ctx *c, const float *p, long long n, const float *t, lo
 	};
 	const int rc = pass();
 	if (rc != NBCO_OK) return c->fail(rc, "nbco_probe_tree: " + k->err);
+	return maybe_sync(c);
+}
+
+// ---- pair statistics ---------------------------------------------------------------------------
+// what all three calls refuse before any launch, and the window and bins of a good call (bins is ignored without counts)
+static int pair_args(nbco_ctx *c, const char *who, bool tree, const void *p, long long n, int bins, double rmax, const void *counts_dev, const void *nn2_dev,
+                     PairBins &pb)
+{
+	if (!c) return NBCO_ERR_ARG;
+	const std::string w(who);
+	if (!p) return c->fail(NBCO_ERR_ARG, w + ": null pointer");
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, w + ": n must be positive");
+	if (!counts_dev && !nn2_dev) return c->fail(NBCO_ERR_ARG, w + ": both outputs are NULL");
+	if (!std::isfinite(rmax) || !(rmax > 0.0)) return c->fail(NBCO_ERR_ARG, w + ": rmax must be finite and positive");
+	if (!counts_dev) bins = 1;
+	if (bins < 1 || bins > 65536) return c->fail(NBCO_ERR_ARG, w + ": bins must be 1..65536");
+	pb.bins = bins;
+	pb.R2 = rmax * rmax;
+	pb.width = rmax / (double)bins;
+	pb.inv_width = 1.0 / pb.width;
+	if (counts_dev && pb.width * pb.width < DBL_MIN) return c->fail(NBCO_ERR_ARG, w + ": the square of the bin width underflows");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit particle indices");
+	if (tree && n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit tree indices");
+	return NBCO_OK;
+}
+
+int nbco_pair_hist(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev)
+{
+	PairBins pb;
+	NBCO_TRY(pair_args(c, "nbco_pair_hist", false, p, n, bins, rmax, counts_dev, nn2_dev, pb));
+	NBCO_TRY(launch_pair_hist(c, p, 3, n, pb, counts_dev, nn2_dev));
+	return maybe_sync(c);
+}
+
+int nbco_2d_pair_hist(nbco_ctx *c, const double *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev)
+{
+	PairBins pb;
+	NBCO_TRY(pair_args(c, "nbco_2d_pair_hist", false, p, n, bins, rmax, counts_dev, nn2_dev, pb));
+	NBCO_TRY(launch_pair_hist(c, p, 2, n, pb, counts_dev, nn2_dev));
+	return maybe_sync(c);
+}
+
+int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev)
+{
+	PairBins pb;
+	NBCO_TRY(pair_args(c, "nbco_pair_hist_tree", true, p, n, bins, rmax, counts_dev, nn2_dev, pb));
+	nbco_ctx *k;
+	NBCO_TRY(private_child(c, "nbco_pair_hist_tree", k));
+	auto pass = [&]() -> int {
+		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
+		float *x = k->pot_xa.as<float>();
+		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
+		return kd_pair_hist_tree(k, x, n, pb, counts_dev, nn2_dev);
+	};
+	const int rc = pass();
+	if (rc != NBCO_OK) return c->fail(rc, "nbco_pair_hist_tree: " + k->err);
 	return maybe_sync(c);
 }
 

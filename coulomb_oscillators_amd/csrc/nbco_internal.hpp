@@ -362,7 +362,15 @@ int launch_energy(nbco_ctx *c, const float *buf, long long n, const float *param
 // beam diagnostics; dim 3: buf holds fp32 xyz triplets, dim 2: fp64 xy pairs
 int launch_beam_moments(nbco_ctx *c, const void *buf, int dim, long long n, nbco_moments *out_host);
 int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
+// pair statistics (pair_stat_kernels.hpp): the window and the bins of a call, formed once on the host by the rule of include/nbco.h
+struct PairBins
+{
+	int bins;
+	double R2, width, inv_width;   // R2 = rmax * rmax, width = rmax / bins; inv_width only seeds the bin search
+};
+int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
 // k_fmm_kd.hip
+int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
 int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);
 int kd_copy_out(nbco_ctx *c, int which, void *host_dst, long long host_bytes);
 int kd_count_pairs(nbco_ctx *c, long long *out);

@@ -196,6 +196,9 @@ def _load():
         "nbco_moments_derive": [C.POINTER(Moments)],
         "nbco_hist": [P, P, LL, C.POINTER(HistAxis), I, P],
         "nbco_2d_hist": [P, P, LL, C.POINTER(HistAxis), I, P],
+        "nbco_pair_hist": [P, P, LL, I, D, P, P],
+        "nbco_pair_hist_tree": [P, P, LL, I, D, P, P],
+        "nbco_2d_pair_hist": [P, P, LL, I, D, P, P],
         "nbco_2d_init_kv": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
         "nbco_2d_init_gaussian": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
     }
@@ -503,6 +506,34 @@ class Engine:
     def hist_2d(self, buf, n, axes, counts=None):
         """the same of the 2-D fp64 state (nbco_2d_hist); the coordinates are Q_X, Q_Y, Q_VX, Q_VY"""
         return self._hist(self.lib.nbco_2d_hist, buf, n, axes, counts)
+
+    # ---- pair statistics -------------------------------------------------------------------------
+    def _pair_hist(self, fn, p, n, bins, rmax, counts, nn2):
+        if counts is None:
+            room = int(bins) if 1 <= int(bins) <= 65536 else 0   # (the library refuses the call; nothing is sized by a bad count)
+            counts = self.torch.empty(room + 1, dtype=self.torch.int64, device=p.device)
+        elif counts is False:
+            counts = None
+        self._chk(fn(self.ctx, _ptr(p), n, int(bins), float(rmax), _ptr(counts), _ptr(nn2)))
+        return counts
+
+    def pair_hist(self, p, n, bins, rmax, counts=None, nn2=None):
+        """pair-distance histogram and nearest neighbours of the n positions p (float32 xyz triplets; the head of a state works), all
+        pairs, exact (nbco_pair_hist).  Returns an int64 device tensor of bins + 1 counts of the unordered pairs i < j: bin b holds
+        (b w)^2 <= r2 < ((b + 1) w)^2 with w = rmax / bins, in fp64 over the widened coordinates, the last entry the pairs with
+        r2 >= rmax^2.  `counts` (allocated if None) is overwritten; counts=False asks for no counts.  nn2: None or a float64 device
+        tensor of n that receives, per particle, the smallest r2 to another particle below rmax^2, +inf where there is none.
+        p is not modified."""
+        return self._pair_hist(self.lib.nbco_pair_hist, p, n, bins, rmax, counts, nn2)
+
+    def pair_hist_tree(self, p, n, bins, rmax, counts=None, nn2=None):
+        """the same bytes from a range-limited walk over a kd-tree of its own on a private context (nbco_pair_hist_tree): the cost
+        follows the number of pairs near rmax, not n^2; valid in any state of this engine, which it leaves untouched"""
+        return self._pair_hist(self.lib.nbco_pair_hist_tree, p, n, bins, rmax, counts, nn2)
+
+    def pair_hist_2d(self, p, n, bins, rmax, counts=None, nn2=None):
+        """the exact form for the 2-D fp64 positions (xy pairs; nbco_2d_pair_hist)"""
+        return self._pair_hist(self.lib.nbco_2d_pair_hist, p, n, bins, rmax, counts, nn2)
 
     # ---- multi-GPU kd-domain sharding (see dist.py for the orchestration) ---------------------------
     def dist_layout(self, n_global, world, rank):

@@ -71,6 +71,12 @@ const char *kHelp =
     "                    the charges at these points to <output>/probes<iter>_<ds>.bin: m x 3 doubles of field, then m doubles of\n"
     "                    potential, from a kd-tree walk of its own at the run's -p, -r and -eps (with -cpu: the exact fp64 sums).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -pairs <bins> <rmax>   At every snapshot write the pair statistics of the positions to <output>/pairs<iter>_<ds>.bin: bins + 1\n"
+    "                    unsigned 64-bit counts -- the pairs i < j with (b w)^2 <= r^2 < ((b + 1) w)^2, w = rmax / bins, then the pairs with\n"
+    "                    r >= rmax -- followed by n doubles: per particle, in the snapshot's order, the squared distance to its nearest\n"
+    "                    neighbour below rmax (inf where there is none).  From a range-limited kd-tree walk of its own\n"
+    "                    (nbco_pair_hist_tree; with -cpu: all pairs on the host, the same rule, the same bytes).\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -cpu              Run the simulation on the host: compensated direct sum O(N^2) over C++20 threads (small N; the test and\n"
     "                    tuning modes need the GPU).  -cpu-threads <n> sets the number of threads (default 8); -cacheline <n> is\n"
     "                    accepted and ignored.\n";
@@ -139,6 +145,23 @@ bool write_probes(const std::string &folder, int iter, SCAL dt, const std::vecto
 	std::ofstream f(folder + "/probes" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 	if (f) f.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)(out.size() * sizeof(double)));
 	if (!f) std::cerr << "Error: cannot write the probe file of iteration " << iter << " into \"" << folder << "\"" << std::endl;
+	return (bool)f;
+}
+
+// -pairs <bins> <rmax> (bins = 0: the flag was not given)
+struct PairsOpt
+{
+	int bins = 0;
+	double rmax = 0;
+};
+
+// <folder>/pairs<iter>_<dt>.bin: bins + 1 counts, then n doubles of nn2
+bool write_pairs(const std::string &folder, int iter, SCAL dt, const std::vector<unsigned long long> &counts, const std::vector<double> &nn2)
+{
+	std::ofstream f(folder + "/pairs" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+	if (f) f.write(reinterpret_cast<const char *>(counts.data()), (std::streamsize)(counts.size() * sizeof(unsigned long long)));
+	if (f) f.write(reinterpret_cast<const char *>(nn2.data()), (std::streamsize)(nn2.size() * sizeof(double)));
+	if (!f) std::cerr << "Error: cannot write the pair file of iteration " << iter << " into \"" << folder << "\"" << std::endl;
 	return (bool)f;
 }
 
@@ -291,8 +314,14 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes)
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs)
 	{
+		// -pairs: the counts and nn2 on the device, and the host copies that go into the files
+		const size_t pair_n = pairs.bins ? (size_t)n : 0, pair_c = pairs.bins ? (size_t)pairs.bins + 1 : 0;
+		DeviceArray<unsigned long long> pairs_counts(pair_c);
+		DeviceArray<double> pairs_nn2(pair_n);
+		std::vector<unsigned long long> pairs_counts_host(pair_c);
+		std::vector<double> pairs_nn2_host(pair_n), pairs_rows(input_order ? pair_n : 0);
 		EnergyLog elog(energy, folder);
 		MomentsLog mlog(moments, folder);
 		// -probes: the points and their results [field m x 3 | potential m] on the device, and the host copy that goes into the files
@@ -369,6 +398,20 @@ struct Session
 				HIPCHK(hipMemcpy(probes_host.data(), probes_out.ptr, probes_host.size() * sizeof(double), hipMemcpyDeviceToHost));
 				if (!write_probes(folder, snap, dt, probes_host)) return -1;
 			}
+			if (pairs.bins)
+			{
+				// the same private context: a tree over a scratch copy of the positions, walked by the particles themselves
+				check(nbco_pair_hist_tree(ctx(), state.ptr, n, pairs.bins, pairs.rmax, pairs_counts.ptr, pairs_nn2.ptr), "pair_hist_tree");
+				check(nbco_sync(ctx()), "sync");
+				HIPCHK(hipMemcpy(pairs_counts_host.data(), pairs_counts.ptr, pair_c * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(pairs_nn2_host.data(), pairs_nn2.ptr, pair_n * sizeof(double), hipMemcpyDeviceToHost));
+				if (input_order)
+				{
+					for (size_t i = 0; i < (size_t)n; ++i) pairs_rows[(size_t)order[i]] = pairs_nn2_host[i];   // (the rows of the snapshot file)
+					if (!write_pairs(folder, snap, dt, pairs_counts_host, pairs_rows)) return -1;
+				}
+				else if (!write_pairs(folder, snap, dt, pairs_counts_host, pairs_nn2_host)) return -1;
+			}
 			if (snap == 0) { loop_t0 = std::chrono::steady_clock::now(); loop_first = 1; }   // the timer below starts behind the first snapshot
 		}
 		check(nbco_sync(ctx()), "sync");
@@ -395,6 +438,7 @@ int main(int argc, const char **argv)
 	int nIters = 30001, nSteps = 200;
 	std::string strout("out"), strin, strprobes;
 	std::vector<float> probes;
+	PairsOpt pairs;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
@@ -512,6 +556,18 @@ int main(int argc, const char **argv)
 			strprobes = argv[++i];
 			if (!read_probes(strprobes, probes)) return -1;
 		}
+		else if (a == "-pairs")
+		{
+			if (!need(i, 2, "-pairs")) return -1;
+			pairs.bins = atoi(argv[i + 1]);
+			pairs.rmax = atof(argv[i + 2]);
+			if (pairs.bins < 1 || pairs.bins > 65536 || !std::isfinite(pairs.rmax) || !(pairs.rmax > 0))
+			{
+				std::cerr << "Error: invalid argument(s) to '-pairs': " << argv[i + 1] << ' ' << argv[i + 2] << " (1..65536 bins, rmax greater than 0)\n";
+				return -1;
+			}
+			i += 2;
+		}
 		else if (a == "-cpu-threads")
 		{
 			if (!need(i, 1, "-cpu-threads")) return -1;
@@ -612,6 +668,8 @@ int main(int argc, const char **argv)
 		EnergyLog elog(energy, strout);
 		MomentsLog mlog(moments, strout);
 		std::vector<double> probes_out(4 * (probes.size() / 3));
+		std::vector<unsigned long long> pairs_counts;
+		std::vector<double> pairs_nn2(pairs.bins ? (size_t)nBodies : 0);
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt);
@@ -644,6 +702,11 @@ int main(int argc, const char **argv)
 				cpu_probes(st.data(), nBodies, probes, par, o.eps2, probes_out);
 				if (!write_probes(strout, iter, dt, probes_out)) return -1;
 			}
+			if (pairs.bins)
+			{
+				nbco_cpu::pair_stats(st.data(), nBodies, pairs.bins, pairs.rmax, pairs_counts, pairs_nn2);
+				if (!write_pairs(strout, iter, dt, pairs_counts, pairs_nn2)) return -1;
+			}
 		}
 		std::cout << std::endl;
 		return 0;
@@ -656,7 +719,8 @@ int main(int argc, const char **argv)
 	{
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
-		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes);
+		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
+		                     b_accuracy ? PairsOpt{} : pairs);
 	}
 	return rc;
 }

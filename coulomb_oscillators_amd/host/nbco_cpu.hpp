@@ -141,6 +141,47 @@ inline void moment_sums(const V3 *buf, int n, double (&mean)[6], double (&mn)[6]
 	for (auto &row : m4) for (double &v : row) v /= (double)n;
 }
 
+// Pair statistics of the positions x[0..n) for `nbco3 -cpu -pairs`, by the pair rule of nbco_pair_hist (include/nbco.h) in fp64 over
+// the fp32 positions: r2 = (dx dx + dy dy) + dz dz with every product and sum rounded once (the program is compiled with
+// -ffp-contract=off), inside iff r2 < rmax * rmax, bin = the largest b with (b width)^2 <= r2, width = rmax / bins.  counts gets
+// bins + 1 values: the unordered pairs i < j per bin, then the pairs outside; nn2 gets n values: the smallest r2 to another particle
+// inside, +infinity where there is none.  Every worker owns a range of i, takes all j != i for the minimum and counts the pairs
+// with i < j into counts of its own, which are added at the end: integers, so the split does not show.
+inline void pair_stats(const V3 *x, int n, int bins, double rmax, std::vector<unsigned long long> &counts, std::vector<double> &nn2)
+{
+	const double R2 = rmax * rmax, width = rmax / (double)bins;
+	std::vector<double> lower2((size_t)bins);
+	for (int b = 0; b < bins; ++b) { const double e = (double)b * width; lower2[(size_t)b] = e * e; }
+	const int workers = std::max(1, std::min(threads(), n)), per = (n - 1) / workers + 1;
+	std::vector<unsigned long long> part((size_t)workers * (size_t)bins, 0ull);
+	unsigned long long *pp = part.data();
+	const double *l2 = lower2.data();
+	double *nn = nn2.data();
+	for_ranges(n, [=](int lo, int hi) {
+		unsigned long long *mine = pp + (size_t)(lo / per) * (size_t)bins;
+		for (int i = lo; i < hi; ++i)
+		{
+			double best = INFINITY;
+			for (int j = 0; j < n; ++j)
+			{
+				if (j == i) continue;
+				const double dx = (double)x[i].x - (double)x[j].x, dy = (double)x[i].y - (double)x[j].y, dz = (double)x[i].z - (double)x[j].z;
+				const double xx = dx * dx, yy = dy * dy, zz = dz * dz, xy = xx + yy, r2 = xy + zz;
+				if (!(r2 < R2)) continue;
+				best = std::min(best, r2);
+				if (i < j) ++mine[(std::upper_bound(l2, l2 + bins, r2) - l2) - 1];   // (lower2[0] = 0 <= r2: never before the first)
+			}
+			nn[i] = best;
+		}
+	});
+	counts.assign((size_t)bins + 1, 0ull);
+	unsigned long long inside = 0;
+	for (int w = 0; w < workers; ++w)
+		for (int b = 0; b < bins; ++b) counts[(size_t)b] += part[(size_t)w * (size_t)bins + (size_t)b];
+	for (int b = 0; b < bins; ++b) inside += counts[(size_t)b];
+	counts[(size_t)bins] = (unsigned long long)n * (unsigned long long)(n - 1) / 2ull - inside;
+}
+
 // one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call)
 enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
 inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt)

@@ -589,6 +589,38 @@ enum { NBCO_Q_X = 0, NBCO_Q_Y = 1, NBCO_Q_Z = 2, NBCO_Q_VX = 3, NBCO_Q_VY = 4, N
 typedef struct nbco_hist_axis { int coord; int bins; double lo, hi; } nbco_hist_axis;
 int nbco_hist(nbco_ctx *c, const float *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
 int nbco_2d_hist(nbco_ctx *c, const double *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
+/* nbco_pair_hist / nbco_pair_hist_tree / nbco_2d_pair_hist: how the particles sit relative to each other -- the histogram of the pair
+ * distances below rmax (the raw counts behind g(r)) and, per particle, the squared distance to its nearest neighbour within rmax.
+ * p holds n positions in DEVICE memory: fp32 xyz triplets (12-byte stride) in 3-D, fp64 xy pairs in 2-D; the head of a state buffer
+ * works as it is.  p is neither modified nor reordered.  Either output may be NULL, not both; a NULL output costs nothing.
+ * The pair rule, which is the whole numerical contract and uses no square root, so nothing depends on how a device rounds one:
+ * d_a = (double) x_i[a] - (double) x_j[a]; r2 = (dx dx + dy dy) + dz dz (2-D: dx dx + dy dy), every product and sum rounded once in
+ * this order, no fused multiply-add: the same bits for (i, j) and (j, i).  R2 = rmax * rmax (one product); a pair is inside iff
+ * r2 < R2 (a NaN is outside).  width = rmax / bins (once, on the host); lower2(b) = e * e with e = (double) b * width; the bin of an
+ * inside pair is the largest b in [0, bins - 1] with lower2(b) <= r2 (lower2 does not decrease with b, so it is unique).
+ * counts_dev[0 .. bins) receives the number of UNORDERED pairs i < j per bin, counts_dev[bins] the pairs outside
+ * (n (n - 1) / 2 less the others); the buffer is overwritten, not accumulated.  nn2_dev[i], in the caller's particle order, receives
+ * min { r2_ij : j != i, the pair inside }, +infinity for a particle without a partner inside.  j != i is by INDEX: two coincident
+ * particles are a pair with r2 = 0, in bin 0, and each has nn2 = 0.  Integer atomics only (a minimum over non-negative doubles is
+ * an unsigned 64-bit minimum): counts and minima do not depend on the order of arrival, a second call returns the same bytes, and
+ * THE TREE FORM RETURNS EXACTLY THE BYTES OF THE EXACT FORM -- the tree decides only what is skipped.
+ * Refused before any launch, the outputs untouched: with NBCO_ERR_ARG a NULL c or p, n <= 0, both outputs NULL, rmax not finite or
+ * <= 0, and with counts_dev given bins < 1, bins > 65536 or width * width below DBL_MIN (bins is ignored when counts_dev is NULL);
+ * with NBCO_ERR_UNSUPPORTED n >= 2^31, and for the tree form an n beyond what nbco_energy_tree takes or a tree_L that leaves more
+ * than 4096 particles per leaf (the kd-tree build finishes a leaf inside one workgroup's LDS).  The calls return as the
+ * evaluators do (opts.sync, opts.stream) and read no other option, the tree form also dens_inhom and tree_L (and fmm_order, which
+ * the level formula reads).  The exact forms count the pairs of a non-finite coordinate as outside; the tree form requires finite
+ * coordinates, as the evaluator does.
+ * State: the exact forms use no scratch of the context.  The tree form is self-contained like nbco_probe_tree: on the private
+ * context it takes a scratch copy of p, builds the kd-tree over it (the build only: no multipoles, no traversal, no lists) and
+ * walks it with the particles themselves, opening a node iff a particle of the wave is within rmax of its box.  This context's
+ * tree, rebuild schedule, warm-select history, order tracking and nbco_kd_get_info stay as they were, and a following evaluation
+ * or diagnostic returns the bits it would have returned.
+ * Not offered: a form on the tree of the LAST EVALUATION (with tree_steps > 1 its boxes are stale, and pruning by them would drop
+ * pairs), a 2-D tree form, weights, and the normalisation to g(r): a user divides by the shell volume and the density. */
+int nbco_pair_hist(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
+int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
+int nbco_2d_pair_hist(nbco_ctx *c, const double *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
 /* main.cu:120-145 initKV and :147-170 initGA over std::mt19937_64(seed) after discard(discard) (main.cu:779-784 uses
  * NBCO_REF_SEED / NBCO_REF_DISCARD); host_state = [pos n x 2 | vel n x 2] doubles in HOST memory, centred with exactly the
  * RMS A/2, omega A/2 (KV) or x, u (Gaussian) per axis.  initKV takes each angle's sine and cosine from one glibc sincos call,
