@@ -176,6 +176,7 @@ static int grid_for(long long n)
 }
 
 #include "beam_diag_kernels.hpp"   // beam diagnostics: the two moment passes and the histogram kernel
+#include "aperture_kernels.hpp"    // aperture: the rule, the classification pass, the scan of the workgroup counts, the scatter
 #define NBCO_PAIR_STAT_EXACT
 #include "pair_stat_kernels.hpp"   // pair statistics: the pair rule, the all-pairs kernel, the count of the pairs outside
 #undef NBCO_PAIR_STAT_EXACT
@@ -393,5 +394,72 @@ int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const Pai
 	if (counts)
 		hipLaunchKernelGGL(pair_outside_kernel, dim3(1), dim3(kBlock), 0, c->stream, counts, pb.bins, (unsigned long long)n * (unsigned long long)(n - 1) / 2ull);
 	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// ---- aperture (aperture_kernels.hpp) -------------------------------------------------------------
+// c->ap_cnt: the total (8 bytes, 16 reserved), then the levels of counts: tiles, tiles / 64, ..
+constexpr size_t kApHead = 16;
+static long long ap_level_size(long long tiles, int level) { for (int k = 0; k < level; ++k) tiles = (tiles + 63) >> kApGroupBits; return tiles; }
+
+int launch_aperture_classify(nbco_ctx *c, const void *p, int dim, long long n, const ApRule &ap, bool tiles, long long *lost_host)
+{
+	const long long nt = (n + kBlock - 1) / kBlock;
+	size_t ints = 0;
+	if (tiles) for (int k = 0; k <= kApLevels; ++k) ints += (size_t)ap_level_size(nt, k);
+	NBCO_TRY(c->reserve(c->ap_cnt, kApHead + sizeof(int) * ints));
+	unsigned long long *total = c->ap_cnt.as<unsigned long long>();
+	int *counts = reinterpret_cast<int *>(c->ap_cnt.as<char>() + kApHead);
+	NBCO_HIP(hipMemsetAsync(total, 0, sizeof *total, c->stream));
+	const dim3 grid((unsigned)nt), block(kBlock);
+	if (dim == 3)
+	{
+		if (tiles) hipLaunchKernelGGL((aperture_classify_kernel<float, 3, true>), grid, block, 0, c->stream, (const float *)p, n, ap, counts, total);
+		else hipLaunchKernelGGL((aperture_classify_kernel<float, 3, false>), grid, block, 0, c->stream, (const float *)p, n, ap, counts, total);
+	}
+	else
+	{
+		if (tiles) hipLaunchKernelGGL((aperture_classify_kernel<double, 2, true>), grid, block, 0, c->stream, (const double *)p, n, ap, counts, total);
+		else hipLaunchKernelGGL((aperture_classify_kernel<double, 2, false>), grid, block, 0, c->stream, (const double *)p, n, ap, counts, total);
+	}
+	NBCO_HIP(hipGetLastError());
+	unsigned long long h = 0;
+	NBCO_HIP(hipMemcpyAsync(&h, total, sizeof h, hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	*lost_host = (long long)h;
+	return NBCO_OK;
+}
+
+template <class T, int D>
+static void aperture_scatter(nbco_ctx *c, T *buf, long long n, long long nk, const ApRule &ap, const ApOffsets &off, void *lost_dev, int *lost_row_dev,
+                             const int *order_in, int *order_out)
+{
+	hipLaunchKernelGGL((aperture_scatter_kernel<T, D>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, (const T *)buf, n, nk, ap, off,
+	                   c->ap_state.as<T>(), (T *)lost_dev, lost_row_dev, order_in, order_out);
+}
+
+int launch_aperture_compact(nbco_ctx *c, void *buf, int dim, long long n, long long lost, const ApRule &ap, void *lost_dev, int *lost_row_dev,
+                            const int *order_in, int *order_out)
+{
+	const long long nk = n - lost;
+	const size_t row = dim == 3 ? 9 * sizeof(float) : 6 * sizeof(double);
+	NBCO_TRY(c->reserve(c->ap_state, row * (size_t)nk));   // (before anything is changed)
+	// the counts of the classification, level by level, until one group holds a level
+	ApOffsets off{};
+	int *level = reinterpret_cast<int *>(c->ap_cnt.as<char>() + kApHead);
+	long long m = (n + kBlock - 1) / kBlock;
+	for (int k = 0; k < kApLevels; ++k)
+	{
+		const long long groups = (m + 63) >> kApGroupBits;
+		hipLaunchKernelGGL(aperture_scan_kernel, dim3((unsigned)((groups + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, c->stream, level, m, level + m);
+		off.level[k] = level;
+		if (groups == 1) break;
+		level += m;
+		m = groups;
+	}
+	if (dim == 3) aperture_scatter<float, 3>(c, (float *)buf, n, nk, ap, off, lost_dev, lost_row_dev, order_in, order_out);
+	else aperture_scatter<double, 2>(c, (double *)buf, n, nk, ap, off, lost_dev, lost_row_dev, order_in, order_out);
+	NBCO_HIP(hipGetLastError());
+	if (nk) NBCO_HIP(hipMemcpyAsync(buf, c->ap_state.ptr, row * (size_t)nk, hipMemcpyDeviceToDevice, c->stream));
 	return NBCO_OK;
 }

@@ -855,6 +855,86 @@ int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, doub
 	return maybe_sync(c);
 }
 
+// ---- aperture ----------------------------------------------------------------------------------
+// what the four calls refuse before any launch, and the rule of a good call (dim 2 reads the first two axes)
+static int aperture_args(nbco_ctx *c, const char *who, int dim, const void *p, long long n, const nbco_aperture *ap, const void *count_host, long long lost_cap,
+                         ApRule &r)
+{
+	if (!c) return NBCO_ERR_ARG;
+	const std::string w(who);
+	if (!p || !ap || !count_host) return c->fail(NBCO_ERR_ARG, w + ": null pointer");
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, w + ": n must be positive");
+	if (ap->shape != NBCO_AP_ELLIPSOID && ap->shape != NBCO_AP_BOX) return c->fail(NBCO_ERR_ARG, w + ": unknown shape");
+	r.shape = ap->shape;
+	for (int a = 0; a < 3; ++a)
+	{
+		// (an axis the state does not have is open and centred: it decides nothing)
+		const double centre = a < dim ? ap->centre[a] : 0.0, half = a < dim ? ap->half[a] : INFINITY;
+		if (!std::isfinite(centre)) return c->fail(NBCO_ERR_ARG, w + ": centre must be finite");
+		if (!(half > 0.0)) return c->fail(NBCO_ERR_ARG, w + ": half must be positive (+infinity opens an axis)");
+		r.centre[a] = centre;
+		r.half[a] = half;
+		r.w[a] = 1.0 / half;
+	}
+	if (lost_cap < 0) return c->fail(NBCO_ERR_ARG, w + ": lost_cap must not be negative");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit row numbers");
+	return NBCO_OK;
+}
+
+// the classification, the refusal of a record that is too small, the compaction; live: the order map travels (3-D only)
+static int aperture_apply(nbco_ctx *c, const char *who, int dim, void *buf, long long n, const ApRule &r, long long *n_kept_host, void *lost_dev,
+                          int *lost_row_dev, long long lost_cap)
+{
+	long long lost = 0;
+	NBCO_TRY(launch_aperture_classify(c, buf, dim, n, r, true, &lost));
+	*n_kept_host = n - lost;
+	if (lost == 0) return NBCO_OK;
+	if ((lost_dev || lost_row_dev) && lost > lost_cap) return c->fail(NBCO_ERR_CAPACITY, std::string(who) + ": more particles are lost than the record holds");
+	const bool live = dim == 3 && c->o.track_order && c->order_n == n;
+	NBCO_TRY(launch_aperture_compact(c, buf, dim, n, lost, r, lost_dev, lost_row_dev, live ? c->order.as<int>() : nullptr, live ? c->order_alt.as<int>() : nullptr));
+	if (dim == 3)
+	{
+		// a new state: no tree, a new rebuild schedule (as nbco_set_opts), nothing of the last evaluation to read
+		c->tree_valid = false;
+		c->eval_counter = 0;
+		c->last_eval.valid = false;
+		if (live) { std::swap(c->order, c->order_alt); c->order_n = n - lost; }
+		else c->order_n = -1;
+	}
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	return NBCO_OK;
+}
+
+int nbco_aperture_count(nbco_ctx *c, const float *p, long long n, const nbco_aperture *ap_host, long long *n_lost_host)
+{
+	ApRule r;
+	NBCO_TRY(aperture_args(c, "nbco_aperture_count", 3, p, n, ap_host, n_lost_host, 0, r));
+	return launch_aperture_classify(c, p, 3, n, r, false, n_lost_host);
+}
+
+int nbco_2d_aperture_count(nbco_ctx *c, const double *p, long long n, const nbco_aperture *ap_host, long long *n_lost_host)
+{
+	ApRule r;
+	NBCO_TRY(aperture_args(c, "nbco_2d_aperture_count", 2, p, n, ap_host, n_lost_host, 0, r));
+	return launch_aperture_classify(c, p, 2, n, r, false, n_lost_host);
+}
+
+int nbco_aperture_apply(nbco_ctx *c, float *buf, long long n, const nbco_aperture *ap_host, long long *n_kept_host, float *lost_dev, int *lost_row_dev,
+                        long long lost_cap)
+{
+	ApRule r;
+	NBCO_TRY(aperture_args(c, "nbco_aperture_apply", 3, buf, n, ap_host, n_kept_host, lost_cap, r));
+	return aperture_apply(c, "nbco_aperture_apply", 3, buf, n, r, n_kept_host, lost_dev, lost_row_dev, lost_cap);
+}
+
+int nbco_2d_aperture_apply(nbco_ctx *c, double *buf, long long n, const nbco_aperture *ap_host, long long *n_kept_host, double *lost_dev,
+                           int *lost_row_dev, long long lost_cap)
+{
+	ApRule r;
+	NBCO_TRY(aperture_args(c, "nbco_2d_aperture_apply", 2, buf, n, ap_host, n_kept_host, lost_cap, r));
+	return aperture_apply(c, "nbco_2d_aperture_apply", 2, buf, n, r, n_kept_host, lost_dev, lost_row_dev, lost_cap);
+}
+
 // ---- introspection -----------------------------------------------------------------------------
 int nbco_kd_get_info(nbco_ctx *c, nbco_kd_info *info)
 {

@@ -298,6 +298,7 @@ struct nbco_ctx
 	nbco_ctx *energy_child = nullptr;   // nbco_energy_tree, nbco_probe_tree: a private context for the tree they build (created on first use, freed by nbco_destroy)
 	bool drifted = false;               // nbco_integrate has moved the particles since the last kd-tree evaluation (a scheme that ends on a drift): nbco_kd_probe refuses
 	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
+	DevBuf ap_cnt, ap_state;            // nbco_aperture_*: the total and the levels of workgroup counts; the compacted state before it is copied back
 	// bookkeeping of the last evaluation
 	nbco_kd_info info{};
 	long long eval_counter = 0;
@@ -369,6 +370,18 @@ struct PairBins
 	double R2, width, inv_width;   // R2 = rmax * rmax, width = rmax / bins; inv_width only seeds the bin search
 };
 int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
+// aperture (aperture_kernels.hpp): the rule of a call, formed once on the host by include/nbco.h: w[a] = 1.0 / half[a]
+struct ApRule
+{
+	int shape;
+	double centre[3], half[3], w[3];
+};
+// the classification pass; tiles: keep the per-workgroup counts in c->ap_cnt for launch_aperture_compact.  Synchronises.
+int launch_aperture_classify(nbco_ctx *c, const void *p, int dim, long long n, const ApRule &ap, bool tiles, long long *lost_host);
+// behind a classification with tiles that found `lost` > 0 rows outside: buf = [pos n | vel n | acc n] -> [pos n' | vel n' | acc n'] through
+// c->ap_state, the lost rows to the record, order_in -> order_out (n' entries) with the state; any of the last four may be NULL
+int launch_aperture_compact(nbco_ctx *c, void *buf, int dim, long long n, long long lost, const ApRule &ap, void *lost_dev, int *lost_row_dev,
+                            const int *order_in, int *order_out);
 // k_fmm_kd.hip
 int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
 int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);

@@ -86,6 +86,15 @@ class HistAxis(C.Structure):
 
 Q_X, Q_Y, Q_Z, Q_VX, Q_VY, Q_VZ = range(6)   # NBCO_Q_*: the coordinate of a histogram axis
 
+
+class Aperture(C.Structure):
+    """nbco_aperture"""
+    _fields_ = [("shape", C.c_int), ("centre", C.c_double * 3), ("half", C.c_double * 3)]
+
+
+AP_ELLIPSOID, AP_BOX = 0, 1   # NBCO_AP_*
+ERR_CAPACITY = 3              # NBCO_ERR_CAPACITY
+
 COLL_DONE, COLL_ALLREDUCE_MIN_I32, COLL_ALLREDUCE_SUM_I32, COLL_ALLGATHER, COLL_ALLTOALL = range(5)
 
 
@@ -199,6 +208,10 @@ def _load():
         "nbco_pair_hist": [P, P, LL, I, D, P, P],
         "nbco_pair_hist_tree": [P, P, LL, I, D, P, P],
         "nbco_2d_pair_hist": [P, P, LL, I, D, P, P],
+        "nbco_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
+        "nbco_aperture_apply": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL), P, P, LL],
+        "nbco_2d_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
+        "nbco_2d_aperture_apply": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL), P, P, LL],
         "nbco_2d_init_kv": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
         "nbco_2d_init_gaussian": [P, LL, P, P, C.c_ulonglong, C.c_ulonglong],
     }
@@ -534,6 +547,58 @@ class Engine:
     def pair_hist_2d(self, p, n, bins, rmax, counts=None, nn2=None):
         """the exact form for the 2-D fp64 positions (xy pairs; nbco_2d_pair_hist)"""
         return self._pair_hist(self.lib.nbco_2d_pair_hist, p, n, bins, rmax, counts, nn2)
+
+    # ---- aperture ---------------------------------------------------------------------------------
+    @staticmethod
+    def _aperture(dim, shape, half, centre):
+        half = [float(h) for h in half]
+        centre = [0.0] * dim if centre is None else [float(v) for v in centre]
+        if len(half) != dim or len(centre) != dim:
+            raise EngineError("aperture: half and centre take %d values" % dim)
+        pad = [0.0] * (3 - dim)
+        return Aperture(int(shape), (C.c_double * 3)(*(centre + pad)), (C.c_double * 3)(*(half + pad)))
+
+    def _aperture_count(self, fn, dim, p, n, shape, half, centre):
+        ap, lost = self._aperture(dim, shape, half, centre), C.c_longlong(-1)
+        self._chk(fn(self.ctx, _ptr(p), n, C.byref(ap), C.byref(lost)))
+        return lost.value
+
+    def _aperture_apply(self, fn, dim, buf, n, shape, half, centre, lost, lost_row):
+        ap, kept = self._aperture(dim, shape, half, centre), C.c_longlong(-1)
+        room = [t.numel() // w for t, w in ((lost, 2 * dim), (lost_row, 1)) if t is not None]
+
+        def where(t):   # (torch gives an empty view the address 0, which the library reads as "no output": a record without room is still one)
+            return None if t is None else C.c_void_p(t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size())
+        rc = fn(self.ctx, _ptr(buf), n, C.byref(ap), C.byref(kept), where(lost), where(lost_row), min(room) if room else 0)
+        if rc != 0:
+            e = EngineError("nbco status %d: %s" % (rc, self.lib.nbco_last_error(self.ctx).decode()), status=rc)
+            e.n_kept = kept.value if rc == ERR_CAPACITY else None   # (what the record of a second call is sized from)
+            raise e
+        return kept.value
+
+    def aperture_count(self, p, n, shape, half, centre=None):
+        """number of the n positions p (float32 xyz triplets) outside the aperture (nbco_aperture_count): shape AP_ELLIPSOID or AP_BOX,
+        half the three half axes (float("inf") opens an axis), centre the three coordinates of its centre (default 0).  The rule is
+        that of include/nbco.h, in fp64.  p and the engine's state are not touched.  Synchronises."""
+        return self._aperture_count(self.lib.nbco_aperture_count, 3, p, n, shape, half, centre)
+
+    def aperture(self, buf, n, shape, half, centre=None, lost=None, lost_row=None):
+        """drops the particles outside the aperture from the state buf = [pos n | vel n | acc n] (float32) and returns n_kept: buf then
+        holds [pos n_kept | vel n_kept | acc n_kept] at its head, the kept particles in their order (nbco_aperture_apply).
+        lost: None or a float32 device tensor that receives x y z vx vy vz per lost particle, in state order; lost_row: None or an
+        int32 device tensor that receives their rows in buf before the call.  The capacity of the record is taken from the tensors;
+        when more are lost, nothing is changed and the EngineError (status ERR_CAPACITY) carries n_kept.  A call that loses
+        nobody changes nothing at all; one that loses somebody drops the tree: energy_fmm / energy_kd / probe_kd must follow the next
+        evaluation.  Synchronises."""
+        return self._aperture_apply(self.lib.nbco_aperture_apply, 3, buf, n, shape, half, centre, lost, lost_row)
+
+    def aperture_count_2d(self, p, n, shape, half, centre=None):
+        """the same of the 2-D fp64 positions (xy pairs; nbco_2d_aperture_count); half and centre take two values"""
+        return self._aperture_count(self.lib.nbco_2d_aperture_count, 2, p, n, shape, half, centre)
+
+    def aperture_2d(self, buf, n, shape, half, centre=None, lost=None, lost_row=None):
+        """the same of the 2-D fp64 state (nbco_2d_aperture_apply); a loss record is x y vx vy, float64"""
+        return self._aperture_apply(self.lib.nbco_2d_aperture_apply, 2, buf, n, shape, half, centre, lost, lost_row)
 
     # ---- multi-GPU kd-domain sharding (see dist.py for the orchestration) ---------------------------
     def dist_layout(self, n_global, world, rank):

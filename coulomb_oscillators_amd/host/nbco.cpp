@@ -59,6 +59,14 @@ const char *kHelp =
     "                    write <dir>/probes<iter>_<ds>.bin: the M accelerations (pairs) and then the M potentials\n"
     "                    of the snapshot's particles at these points (nbco_2d_probe_fmm, order -p; the points feel\n"
     "                    the beam and do not act on it); no effect with -test\n"
+    "  -aperture <ellipse|box> <hx> <hy>\n"
+    "                    at every snapshot iteration, after the step and before the snapshot, drop the particles outside\n"
+    "                    the aperture with these half axes about the origin (`inf` opens an axis) from the run\n"
+    "                    (nbco_2d_aperture_apply): <dir>/lost<iter>_<ds>.bin receives k int32 rows (the rows the lost\n"
+    "                    particles had in the state), then k x 4 doubles x y vx vy -- empty when nobody was lost -- and\n"
+    "                    <dir>/losses.txt one line `iter n_lost n_left`; the snapshot and -energy, -moments, -probes\n"
+    "                    describe the survivors, and the snapshot files shrink with n; a run that loses everybody ends\n"
+    "                    with an error; refused with -test\n"
     "  -ga               Gaussian initial state instead of KV\n"
     "  -xi <v>           perveance\n"
     "  -omega0 <x> <y>   trap phase advances\n"
@@ -88,6 +96,8 @@ int main(const int argc, const char **argv)
 	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1;
 	std::string strout("out"), strin, strprobes;
 	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false, moments = false;
+	bool aperture = false;
+	nbco_aperture ap{NBCO_AP_ELLIPSOID, {0, 0, 0}, {0, 0, 0}};
 
 	// KV parameters matched to the emittances (main.cu:271-313)
 	const double twopi = 6.283185307179586476925286766559;
@@ -190,6 +200,19 @@ int main(const int argc, const char **argv)
 		else if (is(a, "energy")) energy = true;
 		else if (is(a, "moments")) moments = true;
 		else if (is(a, "probes")) { if (need(i, 1, a)) return missing(); strprobes = argv[++i]; }
+		else if (is(a, "aperture"))
+		{
+			if (need(i, 3, a)) return missing2();
+			const bool box = std::strcmp(argv[i + 1], "box") == 0;
+			ap.shape = box ? NBCO_AP_BOX : NBCO_AP_ELLIPSOID;
+			ap.half[0] = std::atof(argv[i + 2]);   // (`inf` opens the axis)
+			ap.half[1] = std::atof(argv[i + 3]);
+			if ((!box && std::strcmp(argv[i + 1], "ellipse") != 0) || !(ap.half[0] > 0) || !(ap.half[1] > 0))
+				return fail("Error: invalid argument(s) to " + opt + ": " + argv[i + 1] + " " + argv[i + 2] + " " + argv[i + 3] +
+				            " (ellipse or box, two half axes greater than 0)\n");
+			aperture = true;
+			i += 3;
+		}
 		else if (is(a, "xi"))
 		{
 			if (need(i, 1, a)) return missing();
@@ -206,6 +229,7 @@ int main(const int argc, const char **argv)
 		if (rc) return rc;
 	}
 	if (cpu) return fail("Error: '-cpu' is not available: this build evaluates on the GPU only\n");
+	if (aperture && test) return fail("Error: '-aperture' changes the run: it cannot be combined with -test\n");
 	if (fmm_order > 10) return fail("Error: invalid argument to '-p': " + std::to_string(fmm_order) + " (orders above 10 are not provided)\n");
 	if (calc_omega) omega = V2{u.x / x.x, u.y / x.y};
 	else if (calc_u) u = V2{omega.x * x.x, omega.y * x.y};
@@ -250,7 +274,7 @@ int main(const int argc, const char **argv)
 		                  : nbco_2d_init_kv(buf.data(), nBodies, a2, b2, NBCO_REF_SEED, NBCO_REF_DISCARD);
 		if (rc != NBCO_OK) return fail("Error: initial state failed\n");
 	}
-	const long long n = nBodies;
+	long long n = nBodies;   // (shrinks when -aperture loses particles)
 
 	if (!test)
 	{
@@ -291,7 +315,7 @@ int main(const int argc, const char **argv)
 		if (r != NBCO_OK) std::cerr << "Error: " << nbco_last_error(ctx) << '\n';
 		return r == NBCO_OK;
 	};
-	const size_t cpy = sizeof(double) * 4 * (size_t)n;
+	size_t cpy = sizeof(double) * 4 * (size_t)n;
 	if (!hip_ok(hipMalloc(&d_buf, sizeof(double) * 6 * (size_t)n)) || !hip_ok(hipMalloc(&d_par, sizeof par)) ||
 	    !hip_ok(hipMemcpy(d_buf, buf.data(), cpy, hipMemcpyHostToDevice)) || !hip_ok(hipMemcpy(d_par, par, sizeof par, hipMemcpyHostToDevice)))
 		return done(-1);
@@ -356,11 +380,29 @@ int main(const int argc, const char **argv)
 			return done(-1);
 		}
 	}
+	// -aperture: the loss record on the device (room for everybody), its host copies and <dir>/losses.txt
+	double *d_lost = nullptr;
+	int *d_lost_row = nullptr;
+	FILE *flo = nullptr;
+	std::vector<double> lost_recs;
+	std::vector<int> lost_rows;
 	auto finish = [&](int code) {
 		if (fen) std::fclose(fen);
 		if (fmo) std::fclose(fmo);
+		if (flo) std::fclose(flo);
+		if (d_lost) (void)hipFree(d_lost);
+		if (d_lost_row) (void)hipFree(d_lost_row);
 		return done(code);
 	};
+	if (aperture)
+	{
+		if (!(flo = std::fopen((strout + "/losses.txt").c_str(), "w")))
+		{
+			std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+			return finish(-1);
+		}
+		if (!hip_ok(hipMalloc(&d_lost, sizeof(double) * 4 * (size_t)n)) || !hip_ok(hipMalloc(&d_lost_row, sizeof(int) * (size_t)n))) return finish(-1);
+	}
 	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return finish(-1);
 	for (int iter = 0; iter < nIters; ++iter)
 	{
@@ -368,6 +410,35 @@ int main(const int argc, const char **argv)
 		if (iter % nSteps == 0)
 		{
 			std::cout << iter << ' ' << std::flush;
+			if (aperture)
+			{
+				// the lost particles leave the state on the device: [pos n | vel n | acc n] -> [pos n' | vel n' | acc n'], order kept
+				long long kept = 0;
+				if (!lib_ok(nbco_2d_aperture_apply(ctx, d_buf, n, &ap, &kept, d_lost, d_lost_row, n))) return finish(-1);
+				const size_t k = (size_t)(n - kept);
+				lost_rows.resize(k);
+				lost_recs.resize(4 * k);
+				if (k && (!hip_ok(hipMemcpy(lost_rows.data(), d_lost_row, sizeof(int) * k, hipMemcpyDeviceToHost)) ||
+				          !hip_ok(hipMemcpy(lost_recs.data(), d_lost, sizeof(double) * 4 * k, hipMemcpyDeviceToHost))))
+					return finish(-1);
+				std::ofstream flost(strout + "/lost" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+				if (flost) flost.write(reinterpret_cast<const char *>(lost_rows.data()), (std::streamsize)(sizeof(int) * k));
+				if (flost) flost.write(reinterpret_cast<const char *>(lost_recs.data()), (std::streamsize)(sizeof(double) * 4 * k));
+				if (!flost)
+				{
+					std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+					return finish(-1);
+				}
+				std::fprintf(flo, "%d %zu %lld\n", iter, k, kept);
+				std::fflush(flo);
+				n = kept;
+				cpy = sizeof(double) * 4 * (size_t)n;
+				if (n == 0)
+				{
+					std::cerr << "\nError: every particle is outside the aperture at iteration " << iter << ": nothing is left to simulate" << std::endl;
+					return finish(-1);
+				}
+			}
 			if (!hip_ok(hipMemcpy(buf.data(), d_buf, cpy, hipMemcpyDeviceToHost))) return finish(-1);
 			std::ofstream fout(strout + "/out" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)

@@ -7,6 +7,7 @@
 // need the GPU.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cstdio>
 #include <chrono>
@@ -77,6 +78,15 @@ const char *kHelp =
     "                    neighbour below rmax (inf where there is none).  From a range-limited kd-tree walk of its own\n"
     "                    (nbco_pair_hist_tree; with -cpu: all pairs on the host, the same rule, the same bytes).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -aperture <ellipsoid|box> <hx> <hy> <hz>   At every snapshot iteration, after the step and before the snapshot, drop the particles\n"
+    "                    outside the aperture with these half axes ('inf' opens an axis: pipes, slabs) from the run: they are lost and no\n"
+    "                    longer simulated (nbco_aperture_apply; with -cpu the same rule on the host).  Per snapshot\n"
+    "                    <output>/lost<iter>_<ds>.bin receives k int32 rows (the rows the lost particles had in the state; with\n"
+    "                    -snapshot-order input their particle numbers), then k x 6 floats x y z vx vy vz -- empty when nobody was lost --\n"
+    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs\n"
+    "                    describe the survivors; the snapshot files shrink with n.  A run that loses everybody ends with an error.\n"
+    "                    Refused with -test, -test2 and -accuracy.\n"
+    "  -aperture-centre <cx> <cy> <cz>   Centre of the aperture (default 0 0 0).\n"
     "  -cpu              Run the simulation on the host: compensated direct sum O(N^2) over C++20 threads (small N; the test and\n"
     "                    tuning modes need the GPU).  -cpu-threads <n> sets the number of threads (default 8); -cacheline <n> is\n"
     "                    accepted and ignored.\n";
@@ -164,6 +174,30 @@ bool write_pairs(const std::string &folder, int iter, SCAL dt, const std::vector
 	if (!f) std::cerr << "Error: cannot write the pair file of iteration " << iter << " into \"" << folder << "\"" << std::endl;
 	return (bool)f;
 }
+
+// -aperture <shape> <hx> <hy> <hz> and -aperture-centre <cx> <cy> <cz>
+struct ApertureOpt
+{
+	bool on = false;
+	nbco_aperture ap{NBCO_AP_ELLIPSOID, {0, 0, 0}, {0, 0, 0}};
+};
+
+// <folder>/lost<iter>_<dt>.bin: k int32 ids, then k x 6 floats; <folder>/losses.txt (emptied when the run starts): 'iter n_lost n_left'
+struct LossLog
+{
+	std::ofstream out;
+	std::string folder;
+	LossLog(bool on, const std::string &folder_) : folder(folder_) { if (on) out.open(folder + "/losses.txt", std::ios::out | std::ios::trunc); }
+	bool record(int iter, SCAL dt, const std::vector<int> &ids, const std::vector<float> &recs, long long n_left)
+	{
+		std::ofstream f(folder + "/lost" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+		if (f) f.write(reinterpret_cast<const char *>(ids.data()), (std::streamsize)(ids.size() * sizeof(int)));
+		if (f) f.write(reinterpret_cast<const char *>(recs.data()), (std::streamsize)(recs.size() * sizeof(float)));
+		out << iter << ' ' << ids.size() << ' ' << n_left << '\n' << std::flush;
+		if (!f || !out) std::cerr << "Error: cannot write the loss record of iteration " << iter << " into \"" << folder << "\"" << std::endl;
+		return f && out;
+	}
+};
 
 // `nbco3 -cpu -probes`: the exact sums in fp64 over the fp32 positions, every source at every probe (no self exclusion), eps2 widened
 // from float; out = [field m x 3 | potential m]
@@ -314,8 +348,16 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs)
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture)
 	{
+		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
+		const size_t ap_n = aperture.on ? (size_t)n : 0;
+		DeviceArray<float> lost_dev(6 * ap_n);
+		DeviceArray<int> lost_row_dev(ap_n);
+		std::vector<float> lost_recs;
+		std::vector<int> lost_ids, rank;
+		bool sparse = false;   // -snapshot-order input: somebody has been lost, the particle numbers of the state have gaps
+		LossLog llog(aperture.on, folder);
 		// -pairs: the counts and nn2 on the device, and the host copies that go into the files
 		const size_t pair_n = pairs.bins ? (size_t)n : 0, pair_c = pairs.bins ? (size_t)pairs.bins + 1 : 0;
 		DeviceArray<unsigned long long> pairs_counts(pair_c);
@@ -356,6 +398,43 @@ struct Session
 			const int snap = iter - 1;
 			std::cout << snap << ' ' << std::flush;
 			check(nbco_sync(ctx()), "sync");
+			// the engine composes the permutations of all tree rebuilds: row i of the state is particle order[i] of the initial state
+			if (input_order) check(nbco_kd_copy(ctx(), NBCO_KD_ORDER, order.data(), (long long)(order.size() * sizeof(int))), "kd_copy");
+			if (aperture.on)
+			{
+				// the lost particles leave the state on the device: [pos n | vel n | acc n] -> [pos n' | vel n' | acc n'], order kept
+				long long kept = 0;
+				check(nbco_aperture_apply(ctx(), state.ptr, n, &aperture.ap, &kept, lost_dev.ptr, lost_row_dev.ptr, (long long)n), "aperture_apply");
+				const size_t k = (size_t)(n - kept);
+				lost_ids.resize(k);
+				lost_recs.resize(6 * k);
+				if (k)
+				{
+					HIPCHK(hipMemcpy(lost_ids.data(), lost_row_dev.ptr, k * sizeof(int), hipMemcpyDeviceToHost));
+					HIPCHK(hipMemcpy(lost_recs.data(), lost_dev.ptr, 6 * k * sizeof(float), hipMemcpyDeviceToHost));
+				}
+				if (input_order && k)
+				{
+					// particle numbers instead of rows; the lost entries leave the host copy of the order map as they left the engine's
+					size_t next = 0, w = 0;
+					for (size_t i = 0; i < (size_t)n; ++i)
+					{
+						if (next < k && (size_t)lost_ids[next] == i) lost_ids[next++] = order[i];
+						else order[w++] = order[i];
+					}
+					order.resize(w);
+					sparse = true;
+				}
+				n = (int)kept;
+				state_bytes = 6 * (size_t)n * sizeof(float);
+				host.resize(6 * (size_t)n);
+				if (!llog.record(snap, dt, lost_ids, lost_recs, kept)) return -1;
+				if (n == 0)
+				{
+					std::cerr << "\nError: every particle is outside the aperture at iteration " << snap << ": nothing is left to simulate" << std::endl;
+					return -1;
+				}
+			}
 			HIPCHK(hipMemcpy(host.data(), state.ptr, state_bytes, hipMemcpyDeviceToHost));   // acc not copied
 			std::ofstream fout(folder + "/out" + std::to_string(snap) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)
@@ -365,13 +444,21 @@ struct Session
 			}
 			if (input_order)
 			{
-				// the engine composes the permutations of all tree rebuilds: row i of the state is particle order[i] of the initial state
-				check(nbco_kd_copy(ctx(), NBCO_KD_ORDER, order.data(), (long long)(order.size() * sizeof(int))), "kd_copy");
-				for (size_t i = 0; i < (size_t)n; ++i)
+				// rank[r]: the state row that goes into row r of the file -- the particles in increasing particle number, which is the
+				// inverse of the order map while nobody is lost and a sort by the (sparse) numbers afterwards
+				rank.resize((size_t)n);
+				if (!sparse)
+					for (size_t i = 0; i < (size_t)n; ++i) rank[(size_t)order[i]] = (int)i;
+				else
+				{
+					for (size_t i = 0; i < (size_t)n; ++i) rank[i] = (int)i;
+					std::sort(rank.begin(), rank.end(), [&](int a, int b) { return order[(size_t)a] < order[(size_t)b]; });
+				}
+				for (size_t r = 0; r < (size_t)n; ++r)
 					for (int k = 0; k < 3; ++k)
 					{
-						rows[3 * (size_t)order[i] + k] = host[3 * i + k];
-						rows[3 * ((size_t)n + order[i]) + k] = host[3 * ((size_t)n + i) + k];
+						rows[3 * r + k] = host[3 * (size_t)rank[r] + k];
+						rows[3 * ((size_t)n + r) + k] = host[3 * ((size_t)n + rank[r]) + k];
 					}
 				fout.write(reinterpret_cast<const char *>(rows.data()), (std::streamsize)state_bytes);
 			}
@@ -404,10 +491,12 @@ struct Session
 				check(nbco_pair_hist_tree(ctx(), state.ptr, n, pairs.bins, pairs.rmax, pairs_counts.ptr, pairs_nn2.ptr), "pair_hist_tree");
 				check(nbco_sync(ctx()), "sync");
 				HIPCHK(hipMemcpy(pairs_counts_host.data(), pairs_counts.ptr, pair_c * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-				HIPCHK(hipMemcpy(pairs_nn2_host.data(), pairs_nn2.ptr, pair_n * sizeof(double), hipMemcpyDeviceToHost));
+				pairs_nn2_host.resize((size_t)n);
+				HIPCHK(hipMemcpy(pairs_nn2_host.data(), pairs_nn2.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
 				if (input_order)
 				{
-					for (size_t i = 0; i < (size_t)n; ++i) pairs_rows[(size_t)order[i]] = pairs_nn2_host[i];   // (the rows of the snapshot file)
+					pairs_rows.resize((size_t)n);
+					for (size_t r = 0; r < (size_t)n; ++r) pairs_rows[r] = pairs_nn2_host[(size_t)rank[r]];   // (the rows of the snapshot file)
 					if (!write_pairs(folder, snap, dt, pairs_counts_host, pairs_rows)) return -1;
 				}
 				else if (!write_pairs(folder, snap, dt, pairs_counts_host, pairs_nn2_host)) return -1;
@@ -439,6 +528,7 @@ int main(int argc, const char **argv)
 	std::string strout("out"), strin, strprobes;
 	std::vector<float> probes;
 	PairsOpt pairs;
+	ApertureOpt aperture;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
@@ -568,6 +658,37 @@ int main(int argc, const char **argv)
 			}
 			i += 2;
 		}
+		else if (a == "-aperture")
+		{
+			if (!need(i, 4, "-aperture")) return -1;
+			const std::string_view v(argv[i + 1]);
+			bool ok = v == "ellipsoid" || v == "box";
+			aperture.ap.shape = v == "box" ? NBCO_AP_BOX : NBCO_AP_ELLIPSOID;
+			for (int k = 0; k < 3; ++k)
+			{
+				aperture.ap.half[k] = atof(argv[i + 2 + k]);   // ('inf' opens the axis)
+				ok = ok && aperture.ap.half[k] > 0;
+			}
+			if (!ok)
+			{
+				std::cerr << "Error: invalid argument(s) to '-aperture': " << argv[i + 1] << ' ' << argv[i + 2] << ' ' << argv[i + 3] << ' ' << argv[i + 4]
+				          << " (ellipsoid or box, three half axes greater than 0)\n";
+				return -1;
+			}
+			aperture.on = true;
+			i += 4;
+		}
+		else if (a == "-aperture-centre")
+		{
+			if (!need(i, 3, "-aperture-centre")) return -1;
+			for (int k = 0; k < 3; ++k) aperture.ap.centre[k] = atof(argv[i + 1 + k]);
+			if (!std::isfinite(aperture.ap.centre[0]) || !std::isfinite(aperture.ap.centre[1]) || !std::isfinite(aperture.ap.centre[2]))
+			{
+				std::cerr << "Error: invalid argument(s) to '-aperture-centre': " << argv[i + 1] << ' ' << argv[i + 2] << ' ' << argv[i + 3] << '\n';
+				return -1;
+			}
+			i += 3;
+		}
 		else if (a == "-cpu-threads")
 		{
 			if (!need(i, 1, "-cpu-threads")) return -1;
@@ -616,6 +737,12 @@ int main(int argc, const char **argv)
 		else { std::cerr << "Error: unrecognised option '" << argv[i] << "'\n"; return -1; }
 	}
 
+	if (aperture.on && (test || test2 || b_accuracy))
+	{
+		std::cerr << "Error: '-aperture' changes the run: it cannot be combined with -test, -test2 or -accuracy\n";
+		return -1;
+	}
+
 	// ---- state ---------------------------------------------------------------------------------------
 	std::vector<float> host;   // [pos | vel] as the state files hold them; the accelerations never leave the device
 	if (in)
@@ -640,7 +767,7 @@ int main(int argc, const char **argv)
 		}
 	}
 	if (nBodies <= 0) { std::cerr << "Error: no particles." << std::endl; return -1; }
-	const size_t state_bytes = host.size() * sizeof(float);
+	size_t state_bytes = host.size() * sizeof(float);
 
 	if (!test && !test2)
 	{
@@ -670,11 +797,27 @@ int main(int argc, const char **argv)
 		std::vector<double> probes_out(4 * (probes.size() / 3));
 		std::vector<unsigned long long> pairs_counts;
 		std::vector<double> pairs_nn2(pairs.bins ? (size_t)nBodies : 0);
+		LossLog llog(aperture.on, strout);
+		std::vector<int> lost_rows;
+		std::vector<float> lost_recs;
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt);
 			if (iter % nSteps != 0) continue;
 			std::cout << iter << ' ' << std::flush;
+			if (aperture.on)
+			{
+				// (the direct sum never permutes the state: a row is a particle number until somebody is lost)
+				nbco_cpu::aperture_apply(st, nBodies, aperture.ap.shape, aperture.ap.centre, aperture.ap.half, lost_rows, lost_recs);
+				state_bytes = 6 * (size_t)nBodies * sizeof(float);
+				pairs_nn2.resize(pairs.bins ? (size_t)nBodies : 0);
+				if (!llog.record(iter, dt, lost_rows, lost_recs, nBodies)) return -1;
+				if (nBodies == 0)
+				{
+					std::cerr << "\nError: every particle is outside the aperture at iteration " << iter << ": nothing is left to simulate" << std::endl;
+					return -1;
+				}
+			}
 			std::ofstream fout(strout + "/out" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)
 			{
@@ -720,7 +863,7 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs);
+		                     b_accuracy ? PairsOpt{} : pairs, aperture);
 	}
 	return rc;
 }

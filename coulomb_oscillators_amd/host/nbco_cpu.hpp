@@ -182,6 +182,50 @@ inline void pair_stats(const V3 *x, int n, int bins, double rmax, std::vector<un
 	counts[(size_t)bins] = (unsigned long long)n * (unsigned long long)(n - 1) / 2ull - inside;
 }
 
+// The aperture of `nbco3 -cpu -aperture`, by the rule of nbco_aperture_apply (include/nbco.h) in fp64 over the fp32 positions:
+// w_a = 1.0 / half_a (half_a = +infinity: w_a = 0, the axis is open), d_a = (double) x_a - centre_a, a non-finite coordinate is outside;
+// shape 0 (ellipsoid): u_a = d_a w_a, s = (u_x u_x + u_y u_y) + u_z u_z with every product and sum rounded once (the program is
+// compiled with -ffp-contract=off), inside iff s <= 1.0; shape 1 (box): inside iff fabs(d_a) <= half_a on every axis.
+inline bool aperture_inside(const V3 &p, int shape, const double (&centre)[3], const double (&half)[3])
+{
+	const double q[3]{(double)p.x, (double)p.y, (double)p.z};
+	double d[3], u[3];
+	bool finite = true, box = true;
+	for (int a = 0; a < 3; ++a)
+	{
+		const double w = 1.0 / half[a];
+		finite = finite && std::isfinite(q[a]);
+		d[a] = q[a] - centre[a];
+		box = box && std::fabs(d[a]) <= half[a];
+		u[a] = d[a] * w;
+	}
+	const double xx = u[0] * u[0], yy = u[1] * u[1], zz = u[2] * u[2], xy = xx + yy, s = xy + zz;
+	return finite && (shape == 1 ? box : s <= 1.0);
+}
+
+// Stable compaction of buf = [pos n | vel n | acc n] to the particles inside: they keep their order and their bits, buf is resized to
+// 3 n' and n becomes n'.  rows receives the rows of the lost particles before the call, in state order, recs one x y z vx vy vz each.
+inline void aperture_apply(std::vector<V3> &buf, int &n, int shape, const double (&centre)[3], const double (&half)[3], std::vector<int> &rows,
+                           std::vector<float> &recs)
+{
+	rows.clear();
+	recs.clear();
+	std::vector<char> keep((size_t)n);
+	for (int i = 0; i < n; ++i) keep[(size_t)i] = aperture_inside(buf[(size_t)i], shape, centre, half);
+	int kept = 0;
+	for (int i = 0; i < n; ++i) kept += keep[(size_t)i];
+	if (kept == n) return;
+	std::vector<V3> out(3 * (size_t)kept);
+	for (int i = 0, j = 0; i < n; ++i)
+	{
+		const V3 x = buf[(size_t)i], v = buf[(size_t)n + i], a = buf[2 * (size_t)n + i];
+		if (keep[(size_t)i]) { out[(size_t)j] = x; out[(size_t)kept + j] = v; out[2 * (size_t)kept + j] = a; ++j; }
+		else { rows.push_back(i); recs.insert(recs.end(), {x.x, x.y, x.z, v.x, v.y, v.z}); }
+	}
+	buf.swap(out);
+	n = kept;
+}
+
 // one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call)
 enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
 inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt)

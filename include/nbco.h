@@ -621,6 +621,49 @@ int nbco_2d_hist(nbco_ctx *c, const double *buf, long long n, const nbco_hist_ax
 int nbco_pair_hist(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
 int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
 int nbco_2d_pair_hist(nbco_ctx *c, const double *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
+/* ---- aperture: particles that cross a boundary (a pipe wall, an electrode) are lost -- dropped from the state on the device,
+ * recorded, and no longer simulated.  nbco_aperture_count / nbco_aperture_apply serve the 3-D fp32 state, the nbco_2d_ forms the
+ * 2-D fp64 state (they read centre[0..1] and half[0..1] only).  *ap_host lies in HOST memory.
+ * The rule, which is the whole numerical contract: in fp64 over the widened coordinates, no fused multiply-add, no division and no
+ * square root on the device.  w_a = 1.0 / half_a is computed once on the host; half_a = +infinity gives w_a = 0: that axis is open
+ * (pipes, slabs).  d_a = (double) x_a - centre_a.  A particle with a non-finite coordinate is outside in both shapes.
+ *   NBCO_AP_ELLIPSOID: u_a = d_a * w_a; s = (u_x u_x + u_y u_y) + u_z u_z (2-D: u_x u_x + u_y u_y), every product and sum rounded
+ *   once in this order; inside iff s <= 1.0.
+ *   NBCO_AP_BOX: inside iff fabs(d_a) <= half_a on every axis.
+ * Only positions decide.
+ * nbco_aperture_count: the classification pass alone (one read of the positions p, wave ballots, integer sums).  p is not modified
+ * and the context is not touched; *n_lost_host receives the number of particles outside.  The call synchronises.
+ * nbco_aperture_apply: buf = [pos n | vel n | acc n] in DEVICE memory; all three blocks are read.  The particles inside keep their
+ * relative order and buf becomes [pos n' | vel n' | acc n'] at the head of the same allocation, every kept row with the bits it had;
+ * what lies behind 9 n' floats (2-D: 6 n' doubles) is unspecified.  The blocks move, so the state is compacted out of place into
+ * scratch of the context and copied back.  The accelerations travel with the state: the next half kick of a leapfrog step uses
+ * them, and the force a lost particle exerted at its last instant was real.  param is not touched: the coupling stays xi / N0,
+ * because the charge per particle does not change when others are lost.
+ * The loss record: lost_dev receives one row x y z vx vy vz (2-D: x y vx vy) per lost particle, in state order, and
+ * lost_row_dev[k] that particle's row in buf before the call.  Either may be NULL; lost_cap is the room of the non-NULL outputs, in
+ * records.  A row's slot is the number of lost (kept) rows before it -- ballot prefix + wave offset + workgroup offset from a scan
+ * of the workgroup counts: no atomic decides a position, and a second call returns the same bytes.
+ * The call always synchronises and always writes *n_kept_host = n - lost.  If an output is given and lost > lost_cap it returns
+ * NBCO_ERR_CAPACITY and buf, the outputs and the context stay exactly as they were: the caller sizes the record from *n_kept_host
+ * and calls again.  n' = 0 is a legal result.
+ * The context.  lost == 0: nothing at all changes -- no copy, no invalidation; the tree, the rebuild schedule, the warm-select
+ * history, order tracking, nbco_kd_get_info and a valid nbco_energy_fmm / nbco_kd_potential / nbco_kd_probe return the bits they
+ * would have returned.  lost > 0: the state is a new state -- the tree is dropped and the rebuild schedule restarts, as nbco_set_opts
+ * does for a new state, and nbco_energy_fmm / nbco_kd_potential / nbco_kd_probe refuse with NBCO_ERR_ARG until the next
+ * nbco_fmm_kdtree.  With live order tracking (opts.track_order and a tracked evaluation of these n particles behind it) the order
+ * map is compacted with the state: NBCO_KD_ORDER keeps meaning "particle number in the state the first tracked evaluation
+ * received", and the numbers become sparse.  (The 2-D evaluators keep nothing between calls.)
+ * Refused before any launch, everything untouched: with NBCO_ERR_ARG a NULL c, buf / p, ap_host or count pointer, n <= 0, an unknown
+ * shape, a centre that is not finite, a half that is NaN or <= 0, lost_cap < 0; with NBCO_ERR_UNSUPPORTED n >= 2^31.
+ * Not offered: sharded (nbco_dist_*) runs -- their domains must stay equal-sized; a sharded run gathers its state first. */
+enum { NBCO_AP_ELLIPSOID = 0, NBCO_AP_BOX = 1 };
+typedef struct nbco_aperture { int shape; double centre[3]; double half[3]; } nbco_aperture;   /* 2-D calls read [0], [1] */
+int nbco_aperture_count(nbco_ctx *c, const float *p, long long n, const nbco_aperture *ap_host, long long *n_lost_host);
+int nbco_aperture_apply(nbco_ctx *c, float *buf, long long n, const nbco_aperture *ap_host, long long *n_kept_host, float *lost_dev,
+                        int *lost_row_dev, long long lost_cap);
+int nbco_2d_aperture_count(nbco_ctx *c, const double *p, long long n, const nbco_aperture *ap_host, long long *n_lost_host);
+int nbco_2d_aperture_apply(nbco_ctx *c, double *buf, long long n, const nbco_aperture *ap_host, long long *n_kept_host, double *lost_dev,
+                           int *lost_row_dev, long long lost_cap);
 /* main.cu:120-145 initKV and :147-170 initGA over std::mt19937_64(seed) after discard(discard) (main.cu:779-784 uses
  * NBCO_REF_SEED / NBCO_REF_DISCARD); host_state = [pos n x 2 | vel n x 2] doubles in HOST memory, centred with exactly the
  * RMS A/2, omega A/2 (KV) or x, u (Gaussian) per axis.  initKV takes each angle's sine and cosine from one glibc sincos call,
