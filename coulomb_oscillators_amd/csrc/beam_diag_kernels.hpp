@@ -104,8 +104,29 @@ __global__ __launch_bounds__(kBlock) void beam_sums_stage2(const double *__restr
 // number of central sums: the upper triangle of the covariance, then 5 fourth-order products per plane (q_k, p_k)
 constexpr int beam_central_count(int D) { return D * (2 * D + 1) + 5 * D; }
 
-// pass 2, first stage: d = (double) q - mean; per block the sums of d_a d_b (a <= b, row by row), then per plane k with
-// x = d_k, e = d_(D + k): x^4, x^3 e, x^2 e^2, x e^3, e^4
+// acc += the central products of one particle's deviations d: d_a d_b (a <= b, row by row), then per plane k with x = d_k,
+// e = d_(D + k): x^4, x^3 e, x^2 e^2, x e^3, e^4
+template <int D> __device__ inline void beam_central_add(const double (&d)[2 * D], double (&acc)[beam_central_count(D)])
+{
+	constexpr int Q = 2 * D;
+	int k = 0;
+#pragma unroll
+	for (int a = 0; a < Q; ++a)
+#pragma unroll
+		for (int b = a; b < Q; ++b) acc[k++] += d[a] * d[b];
+#pragma unroll
+	for (int p = 0; p < D; ++p)
+	{
+		const double x2 = d[p] * d[p], e2 = d[D + p] * d[D + p], xe = d[p] * d[D + p];
+		acc[k++] += x2 * x2;
+		acc[k++] += x2 * xe;
+		acc[k++] += x2 * e2;
+		acc[k++] += xe * e2;
+		acc[k++] += e2 * e2;
+	}
+}
+
+// pass 2, first stage: d = (double) q - mean; per block the sums of the central products
 template <class T, int D>
 __global__ __launch_bounds__(kBlock) void beam_central_stage1(const T *__restrict__ buf, long long n, const double *__restrict__ mean,
                                                                double *__restrict__ part)
@@ -122,21 +143,7 @@ __global__ __launch_bounds__(kBlock) void beam_central_stage1(const T *__restric
 		beam_load<T, D>(buf, n, i, d);
 #pragma unroll
 		for (int a = 0; a < Q; ++a) d[a] -= m[a];
-		int k = 0;
-#pragma unroll
-		for (int a = 0; a < Q; ++a)
-#pragma unroll
-			for (int b = a; b < Q; ++b) acc[k++] += d[a] * d[b];
-#pragma unroll
-		for (int p = 0; p < D; ++p)
-		{
-			const double x2 = d[p] * d[p], e2 = d[D + p] * d[D + p], xe = d[p] * d[D + p];
-			acc[k++] += x2 * x2;
-			acc[k++] += x2 * xe;
-			acc[k++] += x2 * e2;
-			acc[k++] += xe * e2;
-			acc[k++] += e2 * e2;
-		}
+		beam_central_add<D>(d, acc);
 	}
 	beam_block_sum<K>(acc, part + (size_t)blockIdx.x * K);
 }

@@ -4,7 +4,7 @@
 // Pattern: grid-stride loads -> wave64 shuffle reduction -> LDS across the 4 waves of a block ->
 // one partial per block -> last stage in a single block (deterministic, no float atomics).
 #include "nbco_internal.hpp"
-#include "dispatch.hpp"
+#include "host_util.hpp"
 #include <algorithm>
 #include <cfloat>
 
@@ -177,6 +177,7 @@ static int grid_for(long long n)
 
 #include "beam_diag_kernels.hpp"   // beam diagnostics: the two moment passes and the histogram kernel
 #include "aperture_kernels.hpp"    // aperture: the rule, the classification pass, the scan of the workgroup counts, the scatter
+#include "slice_diag_kernels.hpp" // slice diagnostics: the keys, the slice and chunk tables, the two moment passes per chunk and per slice
 #define NBCO_PAIR_STAT_EXACT
 #include "pair_stat_kernels.hpp"   // pair statistics: the pair rule, the all-pairs kernel, the count of the pairs outside
 #undef NBCO_PAIR_STAT_EXACT
@@ -327,6 +328,22 @@ template <class T, int D> static void hist_run(nbco_ctx *c, const T *buf, long l
 	else hipLaunchKernelGGL((hist_kernel<T, D, false>), dim3(grid_for(n)), dim3(kBlock), 0, c->stream, buf, n, ax, counts);
 }
 
+// element offset of a coordinate in buf = [pos n | vel n | ..]
+static long long hist_coord_offset(int coord, int dim, long long n) { return coord < 3 ? (long long)coord : (long long)dim * n + (coord - 3); }
+
+// what nbco_hist and nbco_slice_moments refuse in an axis
+static int hist_axis_check(nbco_ctx *c, const char *who, int dim, const nbco_hist_axis &x)
+{
+	const std::string w = std::string(who) + ": ";
+	const bool have = dim == 3 ? x.coord >= NBCO_Q_X && x.coord <= NBCO_Q_VZ
+	                           : x.coord == NBCO_Q_X || x.coord == NBCO_Q_Y || x.coord == NBCO_Q_VX || x.coord == NBCO_Q_VY;
+	if (!have) return c->fail(NBCO_ERR_ARG, w + "the state has no such coordinate");
+	if (x.bins < 1 || x.bins > 65536) return c->fail(NBCO_ERR_ARG, w + "bins must be 1..65536");
+	if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !std::isfinite(x.hi - x.lo)) return c->fail(NBCO_ERR_ARG, w + "lo and hi must be finite");
+	if (!(x.lo < x.hi)) return c->fail(NBCO_ERR_ARG, w + "lo must be below hi");
+	return NBCO_OK;
+}
+
 int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axes, int naxes, unsigned long long *counts)
 {
 	if (n <= 0) return c->fail(NBCO_ERR_ARG, "hist: n must be positive");
@@ -334,18 +351,11 @@ int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_h
 	long long B = 1;
 	for (int a = 0; a < naxes; ++a)
 	{
-		const nbco_hist_axis &x = axes[a];
-		const bool have = dim == 3 ? x.coord >= NBCO_Q_X && x.coord <= NBCO_Q_VZ
-		                           : x.coord == NBCO_Q_X || x.coord == NBCO_Q_Y || x.coord == NBCO_Q_VX || x.coord == NBCO_Q_VY;
-		if (!have) return c->fail(NBCO_ERR_ARG, "hist: the state has no such coordinate");
-		if (x.bins < 1 || x.bins > 65536) return c->fail(NBCO_ERR_ARG, "hist: bins must be 1..65536");
-		if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !std::isfinite(x.hi - x.lo)) return c->fail(NBCO_ERR_ARG, "hist: lo and hi must be finite");
-		if (!(x.lo < x.hi)) return c->fail(NBCO_ERR_ARG, "hist: lo must be below hi");
-		B *= x.bins;
+		NBCO_TRY(hist_axis_check(c, "hist", dim, axes[a]));
+		B *= axes[a].bins;
 	}
 	if (B > (1LL << 24)) return c->fail(NBCO_ERR_ARG, "hist: more than 2^24 bins");
-	// element offset of a coordinate in buf = [pos n | vel n | ..]
-	auto off = [&](int coord) { return coord < 3 ? (long long)coord : (long long)dim * n + (coord - 3); };
+	auto off = [&](int coord) { return hist_coord_offset(coord, dim, n); };
 	HistAxes ax{};
 	ax.off0 = off(axes[0].coord);
 	ax.bins0 = axes[0].bins; ax.lo0 = axes[0].lo; ax.hi0 = axes[0].hi; ax.scale0 = (double)axes[0].bins / (axes[0].hi - axes[0].lo);
@@ -361,6 +371,75 @@ int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_h
 	else hist_run<double, 2>(c, (const double *)buf, n, ax, (int)B, counts);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
+}
+
+// ---- slice diagnostics (slice_diag_kernels.hpp) --------------------------------------------------
+// Scratch of the call's own (c->sl_*): a kd evaluation's buffers, the reduction partials and c->small are not touched.
+template <class T, int D>
+static int slice_moments(nbco_ctx *c, const T *buf, long long n, const nbco_hist_axis &x, nbco_moments *out_host, long long *n_outside_host)
+{
+	constexpr int Q = 2 * D, K = beam_central_count(D), R = 3 * Q + K;   // doubles of a slice's record on the device: mean, min, max, central sums
+	static_assert(4 * Q <= K, "a slab of the first pass fits a slab of the second");
+	const int bins = x.bins, ni = (int)n;
+	const SliceAxis ax{hist_coord_offset(x.coord, D, n), bins, x.lo, x.hi, (double)bins / (x.hi - x.lo)};
+	// at most n / kSliceChunk full chunks and one partial chunk per slice that holds anybody
+	const long long grid = n / kSliceChunk + std::min<long long>(bins, n);
+	// the table: start[bins + 2] and first[bins + 1] as ints, then the records
+	const size_t ints = ((size_t)2 * bins + 3 + 1) & ~(size_t)1, tab_bytes = sizeof(int) * ints + sizeof(double) * R * (size_t)bins;
+	NBCO_TRY(c->reserve(c->sl_keys, sizeof(unsigned) * 3 * (size_t)n));
+	NBCO_TRY(c->reserve(c->sl_tab, tab_bytes));
+	NBCO_TRY(c->reserve(c->sl_part, sizeof(double) * K * (size_t)grid));   // (4 Q <= K)
+	unsigned *key = c->sl_keys.as<unsigned>(), *key_sorted = key + n;
+	int *perm = reinterpret_cast<int *>(key + 2 * n), *start = c->sl_tab.as<int>(), *first = start + bins + 2;
+	double *rec = reinterpret_cast<double *>(start + ints), *part = c->sl_part.as<double>();
+	unsigned key_bits = 0;
+	while ((bins >> key_bits) != 0) ++key_bits;   // the keys are 0 .. bins
+	hipLaunchKernelGGL((slice_key_kernel<T, D>), dim3(grid_for(n)), dim3(kBlock), 0, c->stream, buf, n, ax, key);
+	NBCO_TRY(sort_pairs(c, c->sl_tmp, key, key_sorted, rocprim::counting_iterator<int>(0), perm, n, 0, key_bits));
+	hipLaunchKernelGGL(slice_start_kernel, dim3(ceil_div(bins + 2, kBlock)), dim3(kBlock), 0, c->stream, key_sorted, ni, bins, start);
+	NBCO_TRY(exclusive_scan(c, c->sl_tmp, rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), SliceChunksOf{start, bins}), first, 0,
+	                        (size_t)bins + 1));
+	// two passes, no host round trip in between: the chunk table and the slices' means stay on the device
+	const dim3 chunks((unsigned)grid), slices((unsigned)ceil_div(bins, kBlock / 64)), block(kBlock);
+	hipLaunchKernelGGL((slice_sums_stage1<T, D>), chunks, block, 0, c->stream, buf, n, perm, first, start, bins, part);
+	hipLaunchKernelGGL(slice_sums_stage2<Q>, slices, block, 0, c->stream, part, first, start, bins, R, rec);
+	hipLaunchKernelGGL((slice_central_stage1<T, D>), chunks, block, 0, c->stream, buf, n, perm, first, start, bins, R, rec, part);
+	hipLaunchKernelGGL((slice_central_stage2<Q, K>), slices, block, 0, c->stream, part, first, bins, R, rec);
+	NBCO_HIP(hipGetLastError());
+	std::vector<char> host(tab_bytes);
+	NBCO_HIP(hipMemcpyAsync(host.data(), start, tab_bytes, hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	const int *h_start = reinterpret_cast<const int *>(host.data());
+	const double *h_rec = reinterpret_cast<const double *>(h_start + ints);
+	for (int s = 0; s < bins; ++s)
+	{
+		nbco_moments m;
+		memset(&m, 0, sizeof m);
+		m.n = h_start[s + 1] - h_start[s];
+		m.dim = D;
+		if (m.n)
+		{
+			const double *h = h_rec + (size_t)R * s, *t = h + 3 * Q;
+			for (int a = 0; a < Q; ++a) { m.mean[a] = h[a]; m.min[a] = h[Q + a]; m.max[a] = h[2 * Q + a]; }
+			for (int a = 0; a < Q; ++a)
+				for (int b = a; b < Q; ++b) m.cov[a][b] = m.cov[b][a] = *t++ / (double)m.n;
+			for (int p = 0; p < D; ++p)
+				for (int j = 0; j < 5; ++j) m.m4[p][j] = *t++ / (double)m.n;
+		}
+		nbco_moments_derive(&m);
+		out_host[s] = m;
+	}
+	*n_outside_host = n - h_start[bins];
+	return NBCO_OK;
+}
+
+int launch_slice_moments(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axis_host, nbco_moments *out_host, long long *n_outside_host)
+{
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, "slice_moments: n must be positive");
+	NBCO_TRY(hist_axis_check(c, "slice_moments", dim, *axis_host));
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, "slice_moments: n must be below 2^31");
+	return dim == 3 ? slice_moments<float, 3>(c, (const float *)buf, n, *axis_host, out_host, n_outside_host)
+	                : slice_moments<double, 2>(c, (const double *)buf, n, *axis_host, out_host, n_outside_host);
 }
 
 // ---- pair statistics, exact forms (pair_stat_kernels.hpp) ---------------------------------------

@@ -685,6 +685,16 @@ int nbco_2d_hist(nbco_ctx *c, const double *buf, long long n, const nbco_hist_ax
 	NBCO_TRY(launch_hist(c, buf, 2, n, axes_host, naxes, counts_dev));
 	return maybe_sync(c);
 }
+int nbco_slice_moments(nbco_ctx *c, const float *buf, long long n, const nbco_hist_axis *axis_host, nbco_moments *out_host, long long *n_outside_host)
+{
+	if (!c || !buf || !axis_host || !out_host || !n_outside_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_slice_moments: null pointer") : NBCO_ERR_ARG;
+	return launch_slice_moments(c, buf, 3, n, axis_host, out_host, n_outside_host);
+}
+int nbco_2d_slice_moments(nbco_ctx *c, const double *buf, long long n, const nbco_hist_axis *axis_host, nbco_moments *out_host, long long *n_outside_host)
+{
+	if (!c || !buf || !axis_host || !out_host || !n_outside_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_2d_slice_moments: null pointer") : NBCO_ERR_ARG;
+	return launch_slice_moments(c, buf, 2, n, axis_host, out_host, n_outside_host);
+}
 
 int nbco_energy_fmm(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host)
 {

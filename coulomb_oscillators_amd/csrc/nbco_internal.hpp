@@ -299,6 +299,7 @@ struct nbco_ctx
 	bool drifted = false;               // nbco_integrate has moved the particles since the last kd-tree evaluation (a scheme that ends on a drift): nbco_kd_probe refuses
 	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
 	DevBuf ap_cnt, ap_state;            // nbco_aperture_*: the total and the levels of workgroup counts; the compacted state before it is copied back
+	DevBuf sl_keys, sl_tmp, sl_tab, sl_part;   // nbco_slice_moments: keys and permutation, the sort's and the scan's scratch, the slice table and records, the chunk slabs
 	// bookkeeping of the last evaluation
 	nbco_kd_info info{};
 	long long eval_counter = 0;
@@ -363,6 +364,8 @@ int launch_energy(nbco_ctx *c, const float *buf, long long n, const float *param
 // beam diagnostics; dim 3: buf holds fp32 xyz triplets, dim 2: fp64 xy pairs
 int launch_beam_moments(nbco_ctx *c, const void *buf, int dim, long long n, nbco_moments *out_host);
 int launch_hist(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
+// slice diagnostics (slice_diag_kernels.hpp): bins records to out_host; refuses a bad axis before any launch.  Synchronises.
+int launch_slice_moments(nbco_ctx *c, const void *buf, int dim, long long n, const nbco_hist_axis *axis_host, nbco_moments *out_host, long long *n_outside_host);
 // pair statistics (pair_stat_kernels.hpp): the window and the bins of a call, formed once on the host by the rule of include/nbco.h
 struct PairBins
 {

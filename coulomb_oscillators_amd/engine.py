@@ -205,6 +205,8 @@ def _load():
         "nbco_moments_derive": [C.POINTER(Moments)],
         "nbco_hist": [P, P, LL, C.POINTER(HistAxis), I, P],
         "nbco_2d_hist": [P, P, LL, C.POINTER(HistAxis), I, P],
+        "nbco_slice_moments": [P, P, LL, C.POINTER(HistAxis), C.POINTER(Moments), C.POINTER(LL)],
+        "nbco_2d_slice_moments": [P, P, LL, C.POINTER(HistAxis), C.POINTER(Moments), C.POINTER(LL)],
         "nbco_pair_hist": [P, P, LL, I, D, P, P],
         "nbco_pair_hist_tree": [P, P, LL, I, D, P, P],
         "nbco_2d_pair_hist": [P, P, LL, I, D, P, P],
@@ -519,6 +521,24 @@ class Engine:
     def hist_2d(self, buf, n, axes, counts=None):
         """the same of the 2-D fp64 state (nbco_2d_hist); the coordinates are Q_X, Q_Y, Q_VX, Q_VY"""
         return self._hist(self.lib.nbco_2d_hist, buf, n, axes, counts)
+
+    def _slice_moments(self, fn, buf, n, axis):
+        ax = HistAxis(int(axis[0]), int(axis[1]), float(axis[2]), float(axis[3]))
+        records = (Moments * (ax.bins if 1 <= ax.bins <= 65536 else 1))()   # (the library refuses the call; nothing is sized by a bad count)
+        outside = C.c_longlong(0)
+        self._chk(fn(self.ctx, _ptr(buf), n, C.byref(ax), records, C.byref(outside)))
+        return records, outside.value
+
+    def slice_moments(self, buf, n, axis):
+        """the moments of beam_moments per slice along one phase-space coordinate (nbco_slice_moments): axis is one
+        (coord, bins, lo, hi) tuple, a particle's slice the bin of hist's rule on that coordinate.  Returns (records, n_outside):
+        a ctypes array of `bins` Moments, each of its slice's particles alone (an empty slice: n = 0 and zeros), and the number
+        of particles outside the window.  fp64, fixed order, a slice's sums independent of the other slices; buf is not modified."""
+        return self._slice_moments(self.lib.nbco_slice_moments, buf, n, axis)
+
+    def slice_moments_2d(self, buf, n, axis):
+        """the same of the 2-D fp64 state (nbco_2d_slice_moments); the coordinates are Q_X, Q_Y, Q_VX, Q_VY"""
+        return self._slice_moments(self.lib.nbco_2d_slice_moments, buf, n, axis)
 
     # ---- pair statistics -------------------------------------------------------------------------
     def _pair_hist(self, fn, p, n, bins, rmax, counts, nn2):

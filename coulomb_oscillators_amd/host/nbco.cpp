@@ -4,7 +4,8 @@
 //
 // Additions: -energy writes the energies of every snapshot to energy.txt (nbco_2d_energy_fmm); -probes <file> writes the field and
 // the potential at the file's points for every snapshot (nbco_2d_probe_fmm); -moments writes the beam's phase-space moments of every
-// snapshot to moments.txt (nbco_2d_beam_moments); without them nothing changes.
+// snapshot to moments.txt (nbco_2d_beam_moments); -slices writes them per slice along one coordinate to slices<iter>_<ds>.txt
+// (nbco_2d_slice_moments); without them nothing changes.
 // Deviations: -cpu / -cpu-threads are refused (main.cu -cpu runs a host FMM, which this product does not have); -gpu, -gridsize
 // and -cacheline are validated as main.cu does and then have no effect; -p above 10 is refused by the library (NBCO_ERR_ARG).
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include <string>
 #include <vector>
 #include "../../include/nbco.h"
+#include "slices_file.hpp"
 
 namespace {
 
@@ -55,6 +57,13 @@ const char *kHelp =
     "                    (nbco_2d_beam_moments): `iter`, the means of (x, y, vx, vy), then per plane (x, vx), (y, vy)\n"
     "                    `sig_q sig_p cov_qp emit halo_q halo`; the file starts with a `#` line naming the columns;\n"
     "                    no effect with -test\n"
+    "  -slices <x|y|vx|vy> <bins> <lo> <hi>\n"
+    "                    at every snapshot write the moments of -moments per slice along that coordinate to\n"
+    "                    <dir>/slices<iter>_<ds>.txt (nbco_2d_slice_moments): a particle's slice is the bin\n"
+    "                    (int) ((q - lo) bins / (hi - lo)) of the window lo <= q < hi; a `#` line names the columns,\n"
+    "                    `# outside <k>` counts the particles outside the window, then one line per slice: `s lo_s n`,\n"
+    "                    the 4 means, then per plane `sig_q sig_p cov_qp emit halo_q halo` of the slice's particles\n"
+    "                    alone (an empty slice: zeros); no effect with -test\n"
     "  -probes <file>    binary file of probe points as pairs of doubles (M = file size / 16).  At every snapshot\n"
     "                    write <dir>/probes<iter>_<ds>.bin: the M accelerations (pairs) and then the M potentials\n"
     "                    of the snapshot's particles at these points (nbco_2d_probe_fmm, order -p; the points feel\n"
@@ -97,6 +106,7 @@ int main(const int argc, const char **argv)
 	std::string strout("out"), strin, strprobes;
 	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false, moments = false;
 	bool aperture = false;
+	SlicesOpt slices;
 	nbco_aperture ap{NBCO_AP_ELLIPSOID, {0, 0, 0}, {0, 0, 0}};
 
 	// KV parameters matched to the emittances (main.cu:271-313)
@@ -199,6 +209,14 @@ int main(const int argc, const char **argv)
 		else if (is(a, "ga")) ga = true;
 		else if (is(a, "energy")) energy = true;
 		else if (is(a, "moments")) moments = true;
+		else if (is(a, "slices"))
+		{
+			if (need(i, 4, a)) return missing2();
+			if (!parse_slices(2, argv[i + 1], argv[i + 2], argv[i + 3], argv[i + 4], slices))
+				return fail("Error: invalid argument(s) to " + opt + ": " + argv[i + 1] + " " + argv[i + 2] + " " + argv[i + 3] + " " + argv[i + 4] +
+				            " (x, y, vx or vy, 1..65536 bins, lo below hi, both finite)\n");
+			i += 4;
+		}
 		else if (is(a, "probes")) { if (need(i, 1, a)) return missing(); strprobes = argv[++i]; }
 		else if (is(a, "aperture"))
 		{
@@ -368,6 +386,7 @@ int main(const int argc, const char **argv)
 		std::fprintf(fmo, "\n");
 		std::fflush(fmo);
 	}
+	std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 	std::vector<double> pout;
 	if (nprobes > 0)
 	{
@@ -465,6 +484,16 @@ int main(const int argc, const char **argv)
 					             mom.emit[k], mom.halo_q[k], mom.halo[k]);
 				std::fprintf(fmo, "\n");
 				std::fflush(fmo);
+			}
+			if (slices.on)
+			{
+				long long outside = 0;
+				if (!lib_ok(nbco_2d_slice_moments(ctx, d_buf, n, &slices.axis, slice_recs.data(), &outside))) return finish(-1);
+				if (!write_slices(strout, iter, std::to_string(dt), 2, slices.axis, slice_recs.data(), outside))
+				{
+					std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+					return finish(-1);
+				}
 			}
 			if (nprobes > 0)
 			{

@@ -22,6 +22,7 @@
 
 #include "nbco_reference_api.hpp"
 #include "nbco_cpu.hpp"
+#include "slices_file.hpp"
 
 using namespace nbco_ref;
 using namespace std::chrono;
@@ -67,6 +68,12 @@ const char *kHelp =
     "  -moments          At every snapshot append the beam's phase-space moments to <output>/moments.txt (nbco_beam_moments; with -cpu the\n"
     "                    same two-pass fp64 sums on the host): 'iter', the 6 means of (x, y, z, vx, vy, vz), then per plane (x, vx),\n"
     "                    (y, vy), (z, vz) 'sig_q sig_p cov_qp emit halo_q halo'.  The file starts with a '#' line naming the columns.\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -slices <x|y|z|vx|vy|vz> <bins> <lo> <hi>   At every snapshot write the moments of -moments per slice along that coordinate\n"
+    "                    to <output>/slices<iter>_<ds>.txt (nbco_slice_moments; with -cpu the same bin rule and two-pass sums on the host): a\n"
+    "                    particle's slice is the bin (int) ((q - lo) bins / (hi - lo)) of the window lo <= q < hi.  A '#' line names the\n"
+    "                    columns, '# outside <k>' counts the particles outside the window, then one line per slice: 's lo_s n', the 6\n"
+    "                    means, then per plane 'sig_q sig_p cov_qp emit halo_q halo' of the slice's particles alone (an empty slice: zeros).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -probes <file>    <file> holds probe points (fp32 xyz triplets, no header).  At every snapshot write the field and the potential of\n"
     "                    the charges at these points to <output>/probes<iter>_<ds>.bin: m x 3 doubles of field, then m doubles of\n"
@@ -348,8 +355,9 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture)
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture, const SlicesOpt &slices)
 	{
+		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
 		const size_t ap_n = aperture.on ? (size_t)n : 0;
 		DeviceArray<float> lost_dev(6 * ap_n);
@@ -477,6 +485,17 @@ struct Session
 				check(nbco_beam_moments(ctx(), state.ptr, n, &mom), "beam_moments");
 				mlog.line(snap, mom);
 			}
+			if (slices.on)
+			{
+				// grouped by slice in scratch of the call's own: the state and the run's tree are not touched
+				long long outside = 0;
+				check(nbco_slice_moments(ctx(), state.ptr, n, &slices.axis, slice_recs.data(), &outside), "slice_moments");
+				if (!write_slices(folder, snap, std::to_string(dt), 3, slices.axis, slice_recs.data(), outside))
+				{
+					std::cerr << "Error: cannot write the slice file of iteration " << snap << " into \"" << folder << "\"" << std::endl;
+					return -1;
+				}
+			}
 			if (m)
 			{
 				// the same private context: a tree over a scratch copy of the positions, walked by the probes
@@ -529,6 +548,7 @@ int main(int argc, const char **argv)
 	std::vector<float> probes;
 	PairsOpt pairs;
 	ApertureOpt aperture;
+	SlicesOpt slices;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
@@ -640,6 +660,17 @@ int main(int argc, const char **argv)
 		else if (a == "-cpu") cpu = true;
 		else if (a == "-energy") energy = true;
 		else if (a == "-moments") moments = true;
+		else if (a == "-slices")
+		{
+			if (!need(i, 4, "-slices")) return -1;
+			if (!parse_slices(3, argv[i + 1], argv[i + 2], argv[i + 3], argv[i + 4], slices))
+			{
+				std::cerr << "Error: invalid argument(s) to '-slices': " << argv[i + 1] << ' ' << argv[i + 2] << ' ' << argv[i + 3] << ' ' << argv[i + 4]
+				          << " (x, y, z, vx, vy or vz, 1..65536 bins, lo below hi, both finite)\n";
+				return -1;
+			}
+			i += 4;
+		}
 		else if (a == "-probes")
 		{
 			if (!need(i, 1, "-probes")) return -1;
@@ -800,6 +831,7 @@ int main(int argc, const char **argv)
 		LossLog llog(aperture.on, strout);
 		std::vector<int> lost_rows;
 		std::vector<float> lost_recs;
+		std::vector<nbco_moments> slice_recs;
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt);
@@ -840,6 +872,15 @@ int main(int argc, const char **argv)
 				nbco_moments_derive(&mom);
 				mlog.line(iter, mom);
 			}
+			if (slices.on)
+			{
+				const long long outside = nbco_cpu::slice_moments(st.data(), nBodies, slices.axis, slice_recs);
+				if (!write_slices(strout, iter, std::to_string(dt), 3, slices.axis, slice_recs.data(), outside))
+				{
+					std::cerr << "Error: cannot write the slice file of iteration " << iter << " into \"" << strout << "\"" << std::endl;
+					return -1;
+				}
+			}
 			if (!probes.empty())
 			{
 				cpu_probes(st.data(), nBodies, probes, par, o.eps2, probes_out);
@@ -863,7 +904,7 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs, aperture);
+		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices);
 	}
 	return rc;
 }

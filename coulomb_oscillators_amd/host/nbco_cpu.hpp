@@ -11,6 +11,7 @@
 #include <cmath>
 #include <thread>
 #include <vector>
+#include "../../include/nbco.h"
 
 namespace nbco_cpu {
 
@@ -139,6 +140,40 @@ inline void moment_sums(const V3 *buf, int n, double (&mean)[6], double (&mn)[6]
 	for (int a = 0; a < 6; ++a)
 		for (int b = a; b < 6; ++b) cov[b][a] = cov[a][b] = cov[a][b] / (double)n;
 	for (auto &row : m4) for (double &v : row) v /= (double)n;
+}
+
+// The records of nbco_slice_moments for `nbco3 -cpu -slices`: a particle's slice by the bin rule of nbco_hist on the widened
+// coordinate (scale = bins / (hi - lo) once; inside iff q >= lo && q < hi, so a NaN is outside; b = (int) ((q - lo) * scale), clamped to
+// bins - 1), then moment_sums over each slice's particles in state order and nbco_moments_derive.  An empty slice is n = 0, dim and zeros.
+// rec gets ax.bins records; returns the number of particles outside the window.
+inline long long slice_moments(const V3 *buf, int n, const nbco_hist_axis &ax, std::vector<nbco_moments> &rec)
+{
+	const double scale = (double)ax.bins / (ax.hi - ax.lo);
+	std::vector<std::vector<int>> rows((size_t)ax.bins);
+	long long outside = 0;
+	for (int i = 0; i < n; ++i)
+	{
+		const V3 &r = buf[ax.coord < 3 ? i : n + i];
+		const double q = (double)(ax.coord % 3 == 0 ? r.x : ax.coord % 3 == 1 ? r.y : r.z);
+		if (!(q >= ax.lo && q < ax.hi)) { ++outside; continue; }
+		const double t = (q - ax.lo) * scale;
+		rows[(size_t)(t < (double)ax.bins ? (int)t : ax.bins - 1)].push_back(i);
+	}
+	rec.assign((size_t)ax.bins, nbco_moments{});
+	std::vector<V3> part;
+	for (int s = 0; s < ax.bins; ++s)
+	{
+		nbco_moments &m = rec[(size_t)s];
+		const int k = (int)rows[(size_t)s].size();
+		m.n = k;
+		m.dim = 3;
+		if (!k) continue;
+		part.resize(2 * (size_t)k);
+		for (int j = 0; j < k; ++j) { part[(size_t)j] = buf[rows[(size_t)s][(size_t)j]]; part[(size_t)(k + j)] = buf[n + rows[(size_t)s][(size_t)j]]; }
+		moment_sums(part.data(), k, m.mean, m.min, m.max, m.cov, m.m4);
+		nbco_moments_derive(&m);
+	}
+	return outside;
 }
 
 // Pair statistics of the positions x[0..n) for `nbco3 -cpu -pairs`, by the pair rule of nbco_pair_hist (include/nbco.h) in fp64 over

@@ -589,6 +589,36 @@ enum { NBCO_Q_X = 0, NBCO_Q_Y = 1, NBCO_Q_Z = 2, NBCO_Q_VX = 3, NBCO_Q_VY = 4, N
 typedef struct nbco_hist_axis { int coord; int bins; double lo, hi; } nbco_hist_axis;
 int nbco_hist(nbco_ctx *c, const float *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
 int nbco_2d_hist(nbco_ctx *c, const double *buf, long long n, const nbco_hist_axis *axes_host, int naxes, unsigned long long *counts_dev);
+/* nbco_slice_moments / nbco_2d_slice_moments: how the beam differs along its length -- the moments above per slice along one
+ * phase-space coordinate (slice emittance, slice centroid, rms size and halo per slice).  *axis_host = {coord, bins, lo, hi} in HOST
+ * memory names the slicing coordinate (any NBCO_Q_* the state has) and the window; out_host receives bins records,
+ * *n_outside_host the number of particles outside the window.  The call synchronises.
+ * Membership: the slice of a particle is exactly nbco_hist's bin rule on that coordinate (a NaN there is outside); summed over the
+ * slices, out_host[s].n plus *n_outside_host equals n.
+ * A slice's record is what nbco_beam_moments means, applied to the slice's particles alone: n, dim, mean (over the slice, not over
+ * the beam), the exact min / max, the central cov, the central m4 of every plane and, from nbco_moments_derive once per slice, emit /
+ * halo_q / halo.  The min == max rule holds per slice -- a flat axis and a one-particle slice have deviations of exactly 0 -- and
+ * so do the zero conventions.  An empty slice has n = 0 and the right dim; every other field is 0, never NaN.
+ * Order and independence: the particles are grouped by slice with a stable sort of (slice, row) pairs, so a slice's particles
+ * enter its sums in state order; a slice is cut into chunks of a fixed number of particles, one workgroup per chunk, and one wave
+ * adds a slice's chunks in chunk order.  The shape of the summation depends on the slice's own population and on nothing else:
+ * a second call returns the same bytes, and a slice's mean, cov and m4 are the same bytes whatever the other slices hold, however
+ * many there are and wherever the window lies.  No float atomics.  A non-finite value in another coordinate of a particle reaches
+ * that particle's slice only.  The sums behind the means are compensated -- carried as (sum, rounding error) pairs, the mean
+ * (sum + error) / n, roughly twice the working precision -- so that a thin slice far from the origin (particles a bin's width
+ * apart) keeps its fourth central moments, which answer an error eps of the mean with 4 eps <d^3>.  An infinite coordinate therefore
+ * makes that coordinate's mean of its slice NaN (inf - inf in the compensation), where nbco_beam_moments would return inf.
+ * State: the call uses scratch of its own.  The tree, the rebuild schedule, the warm-select history and the order tracking are
+ * untouched, and a valid nbco_energy_fmm / nbco_kd_potential / nbco_kd_probe returns the bits it would have returned, also after
+ * 2-D calls on the same context.
+ * Refused before any launch, out_host and *n_outside_host left as they were: with NBCO_ERR_ARG a NULL pointer, n <= 0, a coordinate
+ * the state does not have (Z and VZ in 2-D), bins < 1 or > 65536, lo or hi not finite, lo >= hi; with NBCO_ERR_UNSUPPORTED
+ * n >= 2^31.  Sharded runs: the note above applies -- the call describes the particles it is given.
+ * Not offered: radial slices, weights, two slicing axes. */
+int nbco_slice_moments(nbco_ctx *c, const float *buf, long long n, const nbco_hist_axis *axis_host, nbco_moments *out_host,
+                       long long *n_outside_host);
+int nbco_2d_slice_moments(nbco_ctx *c, const double *buf, long long n, const nbco_hist_axis *axis_host, nbco_moments *out_host,
+                          long long *n_outside_host);
 /* nbco_pair_hist / nbco_pair_hist_tree / nbco_2d_pair_hist: how the particles sit relative to each other -- the histogram of the pair
  * distances below rmax (the raw counts behind g(r)) and, per particle, the squared distance to its nearest neighbour within rmax.
  * p holds n positions in DEVICE memory: fp32 xyz triplets (12-byte stride) in 3-D, fp64 xy pairs in 2-D; the head of a state buffer
