@@ -125,6 +125,7 @@ __global__ __launch_bounds__(kBlock) void aperture_scatter_kernel(const T *__res
 	if (!is_lost)
 	{
 		const long long j = i - before;
+		if (!NBCO_CHECKED_OK(j >= 0 && j < nk, NBCO_CHK_GROUP)) return;   // (a survivor's slot: the checked build counts one outside the compacted state)
 		reinterpret_cast<V *>(out)[j] = x;
 		reinterpret_cast<V *>(out + D * nk)[j] = u;
 		reinterpret_cast<V *>(out + 2 * D * nk)[j] = acc[i];
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(kBlock) void aperture_scatter_kernel(const T *__res
 	}
 	else
 	{
+		if (!NBCO_CHECKED_OK(before >= 0 && before < n - nk, NBCO_CHK_GROUP)) return;   // (a lost row's slot in the record of n - nk rows)
 		if (lost)
 		{
 			V *row = reinterpret_cast<V *>(lost) + 2 * before;

@@ -542,3 +542,5 @@ int launch_aperture_compact(nbco_ctx *c, void *buf, int dim, long long n, long l
 	if (nk) NBCO_HIP(hipMemcpyAsync(buf, c->ap_state.ptr, row * (size_t)nk, hipMemcpyDeviceToDevice, c->stream));
 	return NBCO_OK;
 }
+
+NBCO_CHECKED_COLLECT(nbco_checked_collect_reduce)

@@ -73,9 +73,14 @@ __global__ __launch_bounds__(kBlock) void kd_c0_own_kernel(const float4 *__restr
 	{
 		const float4 ct = csz[node];
 		const double eps2 = (double)eps2f;
-		for (int e = m2l_start[node] + lane; e < m2l_start[node + 1]; e += kPotWave)
+		// (the node's run of the sorted list and the source node of an entry; the checked build counts a run outside the list, which it
+		// takes as empty, and a source outside the tree, for which the node itself stands in)
+		const int e0 = m2l_start[node];
+		const int e1 = NBCO_CHECKED_OK(e0 >= 0 && e0 <= m2l_start[node + 1] && m2l_start[node + 1] <= m2l_start[ntot], NBCO_CHK_WALK) ? m2l_start[node + 1] : e0;
+		for (int e = e0 + lane; e < e1; e += kPotWave)
 		{
-			const int sn = (int)(m2l_keys[e] & mask);
+			int sn = (int)(m2l_keys[e] & mask);
+			if (!NBCO_CHECKED_OK((unsigned)sn < (unsigned)ntot, NBCO_CHK_WALK)) sn = node;
 			const float4 cs = csz[sn];
 			s += m2p_potential<P, T>(mpole + (size_t)sn * offM, (double)ct.x - (double)cs.x, (double)ct.y - (double)cs.y, (double)ct.z - (double)cs.z, eps2);
 		}
@@ -113,10 +118,14 @@ __global__ __launch_bounds__(kPotWave) void kd_psi_leaf_kernel(nbco_ctx::LastEva
 	const int beg = kd_beg(le.L), lf = blockIdx.x, leaf = beg + lf, t = threadIdx.x;
 	expand_local_lds<P, T>(local + (size_t)leaf * offL, F, t);
 	const uint64_t mask = (1ull << le.shift) - 1;
-	const int i0 = le.index[leaf], m = le.mult[leaf];
+	// (the checked build counts a particle range outside [0, n) and a run outside the sorted list, which it takes as empty, and a source
+	// leaf outside the leaf level, for which the leaf itself stands in)
+	const int i0 = le.index[leaf];
+	const int m = NBCO_CHECKED_OK(i0 >= 0 && le.mult[leaf] >= 0 && (long long)i0 + le.mult[leaf] <= le.n, NBCO_CHK_WALK) ? le.mult[leaf] : 0;
 	const double cx = (double)le.center[3 * leaf], cy = (double)le.center[3 * leaf + 1], cz = (double)le.center[3 * leaf + 2];
 	const double eps2 = (double)eps2f, c0l = c0[leaf], p0 = (double)param[0];
-	const int e0 = le.have_p2p ? p2p_start[lf] : 0, e1 = le.have_p2p ? p2p_start[lf + 1] : 0;
+	const int e0 = le.have_p2p ? p2p_start[lf] : 0, e1raw = le.have_p2p ? p2p_start[lf + 1] : 0;
+	const int e1 = NBCO_CHECKED_OK(!le.have_p2p || (e0 >= 0 && e0 <= e1raw && e1raw <= p2p_start[gridDim.x]), NBCO_CHK_WALK) ? e1raw : e0;
 	double acc = 0.0;
 	for (int j = t; j < m; j += kPotWave)
 	{
@@ -125,8 +134,10 @@ __global__ __launch_bounds__(kPotWave) void kd_psi_leaf_kernel(nbco_ctx::LastEva
 		double phi = 0.0;
 		for (int e = e0; e < e1; ++e)
 		{
-			const int src = beg + (int)(p2p_keys[e] & mask);
-			const int is = le.index[src], ms = le.mult[src];
+			const int sl = (int)(p2p_keys[e] & mask);
+			const int src = beg + (NBCO_CHECKED_OK((unsigned)sl < gridDim.x, NBCO_CHK_WALK) ? sl : lf);
+			const int is = le.index[src];
+			const int ms = NBCO_CHECKED_OK(is >= 0 && le.mult[src] >= 0 && (long long)is + le.mult[src] <= le.n, NBCO_CHK_WALK) ? le.mult[src] : 0;
 			for (int k = 0; k < ms; ++k)
 			{
 				if (is + k == i) continue;

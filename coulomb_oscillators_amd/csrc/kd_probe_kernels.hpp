@@ -168,7 +168,8 @@ template <int P, typename T, bool WANT_A, bool WANT_PSI>
 __global__ __launch_bounds__(kProbeWave) void kd_probe_walk_kernel(const float4 *__restrict__ csz, const T *__restrict__ mpole, const int *__restrict__ mult,
                                                                    const int *__restrict__ index, const float4 *__restrict__ pos, int ntot, AdmTab tab_arg,
                                                                    float par, float eps2f, const uint32_t *__restrict__ perm, const float *t, long long m,
-                                                                   const float *__restrict__ param, double *__restrict__ a, double *__restrict__ psi)
+                                                                   const float *__restrict__ param, double *__restrict__ a, double *__restrict__ psi
+                                                                   NBCO_CHECKED_ARG(long long n))
 {
 	constexpr int offM = sym_offset(P);
 	__shared__ AdmTab tab;   // LDS copy: the table is indexed by the node's level
@@ -178,7 +179,8 @@ __global__ __launch_bounds__(kProbeWave) void kd_probe_walk_kernel(const float4 
 	__syncthreads();
 	const long long s = (long long)blockIdx.x * kProbeWave + lane;
 	const bool valid = s < m;
-	const uint32_t dst = valid ? perm[s] : 0u;
+	uint32_t dst = valid ? perm[s] : 0u;
+	if (!NBCO_CHECKED_OK((long long)dst < m, NBCO_CHK_WALK)) dst = 0u;   // (the sort's permutation of [0, m))
 	const float tx = valid ? t[3 * (size_t)dst] : 0.f, ty = valid ? t[3 * (size_t)dst + 1] : 0.f, tz = valid ? t[3 * (size_t)dst + 2] : 0.f;
 	const double X = (double)tx, Y = (double)ty, Z = (double)tz, eps2 = (double)eps2f;
 	double ax = 0.0, ay = 0.0, az = 0.0, ps = 0.0;
@@ -209,12 +211,14 @@ __global__ __launch_bounds__(kProbeWave) void kd_probe_walk_kernel(const float4 
 		if (leaf && any_open)
 		{
 			const int i0 = index[k];
-			for (int j0 = 0; j0 < ml; j0 += kProbeWave)
+			// (a leaf's range lies inside [0, n) by the build; the checked build counts one that does not and takes the leaf as empty)
+			const int nl = NBCO_CHECKED_OK(i0 >= 0 && ml >= 0 && (long long)i0 + ml <= n, NBCO_CHK_WALK) ? ml : 0;
+			for (int j0 = 0; j0 < nl; j0 += kProbeWave)
 			{
 				__syncthreads();
-				if (j0 + lane < ml) tile[lane] = pos[(size_t)i0 + j0 + lane];
+				if (j0 + lane < nl) tile[lane] = pos[(size_t)i0 + j0 + lane];
 				__syncthreads();
-				const int cnt = min(kProbeWave, ml - j0);
+				const int cnt = min(kProbeWave, nl - j0);
 				if (open)
 					for (int u = 0; u < cnt; ++u)
 					{
@@ -264,6 +268,6 @@ static void launch_probe_walk(nbco_ctx *c, const ProbeSrc &s, const AdmTab &tab,
 	const dim3 grid((unsigned)((m + kProbeWave - 1) / kProbeWave)), block(kProbeWave);
 	with_outputs(a, psi, [&](auto wa, auto wp) {
 		hipLaunchKernelGGL((kd_probe_walk_kernel<P, T, decltype(wa)::value, decltype(wp)::value>), grid, block, 0, c->stream, s.csz, (const T *)s.mpole, s.mult,
-		                   s.index, s.pos, s.ntot, tab, c->o.tree_radius, c->o.eps2, perm, t, m, param, a, psi);
+		                   s.index, s.pos, s.ntot, tab, c->o.tree_radius, c->o.eps2, perm, t, m, param, a, psi NBCO_CHECKED_ARG(s.n));
 	});
 }

@@ -202,6 +202,8 @@ int nbco_create(nbco_ctx **out, const nbco_opts *o)
 	if (getenv("NBCO_SEL_WARM")) c->sel_warm_enabled = atoi(getenv("NBCO_SEL_WARM")) != 0;
 	if (hipMalloc(&c->small.ptr, 4096) != hipSuccess) { delete c; return NBCO_ERR_HIP; }
 	c->small.bytes = 4096;
+	// (the counters, totals and flags of many calls live here: none of them may rely on a zero that it has not written)
+	if (c->poison && hipMemsetAsync(c->small.ptr, 0x7f, 4096, c->stream) != hipSuccess) { delete c; return NBCO_ERR_HIP; }
 	*out = c;
 	return NBCO_OK;
 }
@@ -978,6 +980,7 @@ int nbco_debug_violations(nbco_ctx *c, long long *out8)
 	NBCO_TRY(nbco_checked_collect_kd(v));
 	NBCO_TRY(nbco_checked_collect_oct(v));
 	NBCO_TRY(nbco_checked_collect_far(v));
+	NBCO_TRY(nbco_checked_collect_reduce(v));
 	for (int i = 0; i < NBCO_CHK_SITES; ++i) out8[i] = v[i];
 	return NBCO_OK;
 #else

@@ -41,6 +41,8 @@ enum
 	NBCO_CHK_CHUNK = 3,      // pair kernels: work-unit record
 	NBCO_CHK_DESC = 4,       // pair kernels: source descriptor
 	NBCO_CHK_L2P = 5,        // l2p_gen_kernel: chunk range, reaction record
+	NBCO_CHK_WALK = 6,       // probe walk, pair walk, potential pass: sorted probe, leaf and node ranges, decoded list entries, unsort map
+	NBCO_CHK_GROUP = 7,      // slice and aperture kernels: chunk table, sorted row, slab range, compaction slot
 	NBCO_CHK_SITES = 8
 };
 #ifdef NBCO_CHECKED
@@ -54,11 +56,16 @@ namespace { __device__ unsigned nbco_violation_count[NBCO_CHK_SITES]; }
 		for (int i = 0; i < NBCO_CHK_SITES; ++i) out[i] += v[i];                                                      \
 		return NBCO_OK;                                                                                               \
 	}
+// a bound that only a check reads: a trailing kernel parameter and its argument exist in the checked build alone, so the production
+// kernels keep their signatures (the name is used inside NBCO_CHECKED_OK conditions only, which the production build discards)
+#define NBCO_CHECKED_ARG(...) , __VA_ARGS__
 #else
 #define NBCO_CHECKED_OK(cond, site) (true)
 #define NBCO_CHECKED_COLLECT(fn) int fn(unsigned *) { return NBCO_OK; }
+#define NBCO_CHECKED_ARG(...)
 #endif
 int nbco_checked_collect_kd(unsigned *out);
+int nbco_checked_collect_reduce(unsigned *out);
 int nbco_checked_collect_oct(unsigned *out);
 int nbco_checked_collect_far(unsigned *out);
 
@@ -152,7 +159,9 @@ struct nbco_ctx
 	long long host_calls = 0;
 	bool aux_is_main = false;   // NBCO_AUX_SERIAL=1 (diagnostics): the second stream is the main stream
 	bool poison = false;        // NBCO_POISON=1 (diagnostics): every new scratch allocation is filled with 0x7f bytes, the way a recycled
-	                            // allocation holds stale data: nothing may depend on fresh memory being zero
+	                            // allocation holds stale data: nothing may depend on fresh memory being zero.  That includes `small`, the block
+	                            // of device scalars (filled in nbco_create), and the private child context (energy_child), which is created
+	                            // through nbco_create and reads the same variable
 	// traversal counts / flags land in pinned host memory; looked at after the rest of the evaluation is enqueued
 	int *h_flags = nullptr;
 	hipEvent_t ev_flags = nullptr;

@@ -237,9 +237,11 @@ __global__ __launch_bounds__(64 * kPairWalkWaves) void kd_pair_walk_kernel(const
 			const bool leaf = 2 * k + 1 >= ntot;
 			if (leaf && any_need)
 			{
-				// (a leaf's range lies inside [0, n) by the build; the clamp keeps a damaged tree from reading past the array)
+				// (a leaf's range lies inside [0, n) by the build; the clamp keeps a damaged tree from reading past the array, and the
+				// checked build counts what the clamp would have hidden)
 				const long long i0 = index[k];
 				long long ml = mult[k];
+				(void)NBCO_CHECKED_OK(i0 >= 0 && ml >= 0 && i0 + ml <= n, NBCO_CHK_WALK);
 				if (i0 < 0 || i0 >= n) ml = 0;
 				else if (ml > n - i0) ml = n - i0;
 				for (long long j0 = 0; j0 < ml; j0 += 64)
@@ -278,6 +280,7 @@ __global__ __launch_bounds__(64 * kPairWalkWaves) void kd_pair_walk_kernel(const
 		if (WANT_NN && valid)
 		{
 			const long long dst = unsort[s];   // (a permutation of [0, n) by the build; the check keeps a damaged map from writing outside nn2)
+			(void)NBCO_CHECKED_OK(dst >= 0 && dst < n, NBCO_CHK_WALK);
 			if (dst >= 0 && dst < n) nn2[dst] = tmin;
 		}
 	}

@@ -56,7 +56,9 @@ struct SliceChunksOf
 };
 
 // the chunk of this workgroup: its slice s and the places [lo, hi) of the sorted order.  false: a surplus workgroup of the upper bound
-__device__ inline bool slice_chunk(const int *__restrict__ first, const int *__restrict__ start, int bins, int &s, int &lo, int &hi)
+// (n: read by the checked build alone, which counts a table that does not bracket this workgroup or a chunk outside [0, n) and drops
+// the workgroup)
+__device__ inline bool slice_chunk(const int *__restrict__ first, const int *__restrict__ start, int bins, long long n, int &s, int &lo, int &hi)
 {
 	const int b = blockIdx.x;
 	if (b >= first[bins]) return false;
@@ -68,8 +70,10 @@ __device__ inline bool slice_chunk(const int *__restrict__ first, const int *__r
 		else z = m;
 	}
 	s = a;
+	if (!NBCO_CHECKED_OK(first[s] <= b && b < first[s + 1], NBCO_CHK_GROUP)) return false;
 	lo = start[s] + (b - first[s]) * kSliceChunk;
 	hi = lo + min(kSliceChunk, start[s + 1] - lo);   // (lo + kSliceChunk may pass 2^31 for the last chunk of a state near that size)
+	if (!NBCO_CHECKED_OK(0 <= lo && lo <= hi && hi <= n, NBCO_CHK_GROUP)) return false;
 	return true;
 }
 
@@ -103,14 +107,15 @@ __global__ __launch_bounds__(kBlock) void slice_sums_stage1(const T *__restrict_
 {
 	constexpr int Q = 2 * D;
 	int slice, lo, hi;
-	if (!slice_chunk(first, start, bins, slice, lo, hi)) return;   // (the whole workgroup)
+	if (!slice_chunk(first, start, bins, n, slice, lo, hi)) return;   // (the whole workgroup)
 	double s[Q], c[Q], mn[Q], mx[Q];
 #pragma unroll
 	for (int a = 0; a < Q; ++a) { s[a] = 0; c[a] = 0; mn[a] = DBL_MAX; mx[a] = -DBL_MAX; }
 	for (int j = lo + threadIdx.x; j < hi; j += kBlock)
 	{
 		double q[Q];
-		beam_load<T, D>(buf, n, perm[j], q);
+		const int row = NBCO_CHECKED_OK((unsigned)perm[j] < (unsigned long long)n, NBCO_CHK_GROUP) ? perm[j] : 0;   // (the sort's permutation of [0, n))
+		beam_load<T, D>(buf, n, row, q);
 #pragma unroll
 		for (int a = 0; a < Q; ++a) { two_sum(s[a], c[a], q[a], 0.0); mn[a] = fmin(mn[a], q[a]); mx[a] = fmax(mx[a], q[a]); }
 	}
@@ -148,7 +153,9 @@ __global__ __launch_bounds__(kBlock) void slice_sums_stage2(const double *__rest
 {
 	const int slice = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (slice >= bins) return;   // (the whole wave)
-	const int c0 = first[slice], c1 = first[slice + 1], cnt = start[slice + 1] - start[slice];
+	// (the checked build counts a run of slabs outside the chunk table and takes the slice's chunks as none)
+	const int c0 = first[slice], cnt = start[slice + 1] - start[slice];
+	const int c1 = NBCO_CHECKED_OK(0 <= c0 && c0 <= first[slice + 1] && first[slice + 1] <= first[bins], NBCO_CHK_GROUP) ? first[slice + 1] : c0;
 	double *rec = out + (size_t)slice * stride;
 #pragma unroll
 	for (int a = 0; a < Q; ++a)
@@ -180,7 +187,7 @@ __global__ __launch_bounds__(kBlock) void slice_central_stage1(const T *__restri
 {
 	constexpr int Q = 2 * D, K = beam_central_count(D);
 	int slice, lo, hi;
-	if (!slice_chunk(first, start, bins, slice, lo, hi)) return;   // (the whole workgroup)
+	if (!slice_chunk(first, start, bins, n, slice, lo, hi)) return;   // (the whole workgroup)
 	const double *mean = out + (size_t)slice * stride;
 	double m[Q], acc[K];
 #pragma unroll
@@ -190,7 +197,8 @@ __global__ __launch_bounds__(kBlock) void slice_central_stage1(const T *__restri
 	for (int j = lo + threadIdx.x; j < hi; j += kBlock)
 	{
 		double d[Q];
-		beam_load<T, D>(buf, n, perm[j], d);
+		const int row = NBCO_CHECKED_OK((unsigned)perm[j] < (unsigned long long)n, NBCO_CHK_GROUP) ? perm[j] : 0;
+		beam_load<T, D>(buf, n, row, d);
 #pragma unroll
 		for (int a = 0; a < Q; ++a) d[a] -= m[a];
 		beam_central_add<D>(d, acc);
@@ -205,7 +213,8 @@ __global__ __launch_bounds__(kBlock) void slice_central_stage2(const double *__r
 {
 	const int slice = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (slice >= bins) return;   // (the whole wave)
-	const int c0 = first[slice], c1 = first[slice + 1];
+	const int c0 = first[slice];
+	const int c1 = NBCO_CHECKED_OK(0 <= c0 && c0 <= first[slice + 1] && first[slice + 1] <= first[bins], NBCO_CHK_GROUP) ? first[slice + 1] : c0;
 	double *rec = out + (size_t)slice * stride + 3 * Q;
 #pragma unroll
 	for (int k = 0; k < K; ++k)

@@ -9,7 +9,12 @@ allocations make that situation deterministic, the device-side checks turn any s
 Part 3 of the script puts the walks of tests/test_gpu_context_reuse.py that aim at stale launch estimates and shared scratch (its
 parts A, first alternation, and D) through the same build: a stale index then shows up as a count in one of the eight sites.
 
-Runs once, in a subprocess (the checked library is selected with NBCO_LIB before the package loads)."""
+test_checked_build_runs_the_snapshot_sequences puts the drivers of tests/test_gpu_snapshots.py -- every diagnostic on one long-lived
+context, at an n smaller than one the context has seen -- through the same build: the walks of the probes, the pair statistics and
+the potential pass report to the site NBCO_CHK_WALK, the slice and aperture kernels to NBCO_CHK_GROUP, and under NBCO_POISON the
+block of device scalars (`small`) starts as 0x7f bytes as well.
+
+Each of the two tests runs once, in a subprocess of its own (the checked library is selected with NBCO_LIB before the package loads)."""
 import json
 import os
 import subprocess
@@ -121,6 +126,59 @@ def test_checked_build_with_poisoned_allocations():
     assert out["violations_total"] == [0] * 8, out
     assert out["interrupted_schedule_identical"], out
     assert out["violations_context_reuse"] == [0] * 8, out
+
+
+SNAPSHOT_SCRIPT = textwrap.dedent('''
+    import json, sys
+    import numpy as np, torch
+    sys.path.insert(0, %r)
+    sys.path.insert(0, %r)
+    from coulomb_oscillators_amd import Engine, EVAL_FMM_KDTREE, Q_Z, lib_path
+    from oracle.pyoracle import Oracle
+    assert lib_path().endswith("libnbco_hip_checked.so")
+    o = Oracle(np.float32)
+    out = {}
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+
+    # 1. something in the allocator's pool: node ids and tables of a deeper tree, and of 4096 slices
+    n = 1 << 18
+    big = Engine(fmm_order=4, unsort=1)
+    d, prm = dev(o.init_reference(n)), dev(o.params(n))
+    t = d[0][:300] * 1.2
+    big.compute_force(EVAL_FMM_KDTREE, d, n, prm)
+    big.energy_tree(d, n, prm, torch.zeros(n, dtype=torch.float64, device="cuda"))
+    big.probe_tree(d, n, t, 300, prm, torch.zeros((300, 3), dtype=torch.float64, device="cuda"), torch.zeros(300, dtype=torch.float64, device="cuda"))
+    big.pair_hist_tree(d, n, 64, 0.0005, nn2=torch.zeros(n, dtype=torch.float64, device="cuda"))
+    big.slice_moments(d, n, (Q_Z, 4096, -0.03, 0.03))
+    torch.cuda.synchronize()
+    out["violations_big"] = big.violations()
+    big.close(); del d, t
+
+    # 2. the drivers of tests/test_gpu_snapshots.py, with that module's own assertions
+    import test_gpu_snapshots as T
+    T.drive_a(o)
+    out["violations_a"] = Engine().violations()
+    T.run_size_walk_3d(o)
+    T.run_size_walk_2d()
+    out["violations_b"] = Engine().violations()
+    T.drive_c()
+
+    # 3. the counts of every site, all contexts of the process together
+    out["violations"] = Engine().violations()
+    print(json.dumps(out))
+''') % (ROOT, os.path.join(ROOT, "tests"))
+
+
+def test_checked_build_runs_the_snapshot_sequences():
+    """the snapshot sequences and size walks of tests/test_gpu_snapshots.py on the checked build with poisoned allocations, behind a
+    context that left a deeper tree's tables in the allocator's pool: every assertion of that module holds and no site has counted"""
+    if not os.path.exists(CHECKED):
+        pytest.fail("libnbco_hip_checked.so is not built (make -C coulomb_oscillators_amd/csrc)")
+    env = dict(os.environ, NBCO_LIB=CHECKED, NBCO_POISON="1")
+    r = subprocess.run([sys.executable, "-c", SNAPSHOT_SCRIPT], capture_output=True, text=True, env=env, timeout=1800)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["violations"] == [0] * 8, out
 
 
 def test_production_build_has_no_checks(engine):
