@@ -4,6 +4,8 @@
 // most 10 blocks x 128 threads (constants.cuh:36-37); here every kernel is a grid-stride loop over
 // 16-byte vectors sized to fill 256 CUs.
 #include "nbco_internal.hpp"
+#include "helix.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -106,15 +108,83 @@ __global__ __launch_bounds__(kBlock) void pack4_kernel(float4 *__restrict__ dst,
 		dst[i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0.f);
 }
 
-// fused K(ks) D(ds): v += a*ks; x += v*ds  (the first two step() calls of leapfrog, integrator.cuh:85-89)
+// fused K(ks) D(ds): v += a*ks; x += v*ds  (the first two step() calls of leapfrog, integrator.cuh:85-89).  Drift = float: the
+// straight drift over the flat view of n3 floats, as ever.  Drift = Helix3: the drift in a uniform magnetic field (helix.hpp), one
+// whole particle per lane -- the tail and the unaligned case of launch_kick_drift_b.
+template <class Drift>
 __global__ __launch_bounds__(kBlock) void kick_drift_kernel(float *__restrict__ x, float *__restrict__ v, const float *__restrict__ a,
-                                                            float ks, float ds, long long n3)
+                                                            float ks, Drift ds, long long n3)
 {
-	for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n3; i += (long long)gridDim.x * kBlock)
+	if constexpr (std::is_same<Drift, float>::value)
 	{
-		float vi = fmaf(ks, a[i], v[i]);
-		v[i] = vi;
-		x[i] = fmaf(ds, vi, x[i]);
+		for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n3; i += (long long)gridDim.x * kBlock)
+		{
+			float vi = fmaf(ks, a[i], v[i]);
+			v[i] = vi;
+			x[i] = fmaf(ds, vi, x[i]);
+		}
+	}
+	else
+	{
+		const long long n = n3 / 3;
+		for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
+		{
+			float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]}, vi[3];
+#pragma unroll
+			for (int c = 0; c < 3; ++c) vi[c] = fmaf(ks, a[3 * i + c], v[3 * i + c]);
+			helix_drift(ds, xi, vi);
+#pragma unroll
+			for (int c = 0; c < 3; ++c) { x[3 * i + c] = xi[c]; v[3 * i + c] = vi[c]; }
+		}
+	}
+}
+
+// the helix drift alone over the particles [beg, n), one per lane (tails and unaligned arrays)
+__global__ __launch_bounds__(kBlock) void drift_b_scalar(float *__restrict__ x, float *__restrict__ v, Helix3 h, long long beg, long long n)
+{
+	for (long long i = beg + (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
+	{
+		float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]}, vi[3] = {v[3 * i], v[3 * i + 1], v[3 * i + 2]};
+		helix_drift(h, xi, vi);
+#pragma unroll
+		for (int c = 0; c < 3; ++c) { x[3 * i + c] = xi[c]; v[3 * i + c] = vi[c]; }
+	}
+}
+
+// 12 floats = 4 whole particles per thread, three 16-byte accesses per array (as elastic_vec); KICK: v += a*ks first
+__device__ __forceinline__ void unpack4(const float4 &q0, const float4 &q1, const float4 &q2, float (&p)[4][3])
+{
+	p[0][0] = q0.x; p[0][1] = q0.y; p[0][2] = q0.z; p[1][0] = q0.w; p[1][1] = q1.x; p[1][2] = q1.y;
+	p[2][0] = q1.z; p[2][1] = q1.w; p[2][2] = q2.x; p[3][0] = q2.y; p[3][1] = q2.z; p[3][2] = q2.w;
+}
+__device__ __forceinline__ void pack4(const float (&p)[4][3], float4 *__restrict__ dst)
+{
+	dst[0] = make_float4(p[0][0], p[0][1], p[0][2], p[1][0]);
+	dst[1] = make_float4(p[1][1], p[1][2], p[2][0], p[2][1]);
+	dst[2] = make_float4(p[2][2], p[3][0], p[3][1], p[3][2]);
+}
+template <bool KICK>
+__global__ __launch_bounds__(kBlock) void helix_vec(float4 *__restrict__ x, float4 *__restrict__ v, const float4 *__restrict__ a, float ks, Helix3 h,
+                                                    long long ngroups)
+{
+	for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < ngroups; g += (long long)gridDim.x * kBlock)
+	{
+		float xp[4][3], vp[4][3];
+		unpack4(x[3 * g], x[3 * g + 1], x[3 * g + 2], xp);
+		unpack4(v[3 * g], v[3 * g + 1], v[3 * g + 2], vp);
+		if constexpr (KICK)
+		{
+			float ap[4][3];
+			unpack4(a[3 * g], a[3 * g + 1], a[3 * g + 2], ap);
+#pragma unroll
+			for (int u = 0; u < 4; ++u)
+#pragma unroll
+				for (int c = 0; c < 3; ++c) vp[u][c] = fmaf(ks, ap[u][c], vp[u][c]);
+		}
+#pragma unroll
+		for (int u = 0; u < 4; ++u) helix_drift(h, xp[u], vp[u]);
+		pack4(xp, x + 3 * g);
+		pack4(vp, v + 3 * g);
 	}
 }
 
@@ -211,10 +281,34 @@ int launch_pack4(nbco_ctx *c, float4 *dst, const float *src3, long long n)
 int launch_kick_drift(nbco_ctx *c, float *x, float *v, const float *a, float ks, float ds, long long n3)
 {
 	if (n3 <= 0) return NBCO_OK;
-	hipLaunchKernelGGL(kick_drift_kernel, dim3(stream_grid(n3)), dim3(kBlock), 0, c->stream, x, v, a, ks, ds, n3);
+	hipLaunchKernelGGL(kick_drift_kernel<float>, dim3(stream_grid(n3)), dim3(kBlock), 0, c->stream, x, v, a, ks, ds, n3);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }
+
+// K(ks) and the helix drift of n particles in one pass; ks = 0 with a = nullptr: the drift alone (nbco_drift_b)
+static int launch_helix(nbco_ctx *c, float *x, float *v, const float *a, float ks, const Helix3 &h, long long n)
+{
+	if (n <= 0) return NBCO_OK;
+	const long long groups = (aligned16(x) && aligned16(v) && aligned16(a)) ? n / 4 : 0;
+	if (groups > 0)
+	{
+		if (a) hipLaunchKernelGGL(helix_vec<true>, dim3(stream_grid(groups)), dim3(kBlock), 0, c->stream, (float4 *)x, (float4 *)v, (const float4 *)a, ks, h, groups);
+		else hipLaunchKernelGGL(helix_vec<false>, dim3(stream_grid(groups)), dim3(kBlock), 0, c->stream, (float4 *)x, (float4 *)v, (const float4 *)nullptr, 0.f, h, groups);
+	}
+	const long long done = 4 * groups;
+	if (done < n)
+	{
+		if (a) hipLaunchKernelGGL(kick_drift_kernel<Helix3>, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, x + 3 * done, v + 3 * done, a + 3 * done, ks, h, 3 * (n - done));
+		else hipLaunchKernelGGL(drift_b_scalar, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, x, v, h, done, n);
+	}
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+int launch_drift_b(nbco_ctx *c, float *x, float *v, const Helix3 &h, long long n) { return launch_helix(c, x, v, nullptr, 0.f, h, n); }
+
+int launch_kick_drift_b(nbco_ctx *c, float *x, float *v, const float *a, float ks, const Helix3 &h, long long n) { return launch_helix(c, x, v, a, ks, h, n); }
 
 int launch_finish_kick(nbco_ctx *c, const float *x, const float *v_in, float *v, float *a, const float *param, float ks, long long n, bool elastic)
 {

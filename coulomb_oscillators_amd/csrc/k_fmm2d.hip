@@ -25,7 +25,9 @@
 #include "nbco_internal.hpp"
 #include "host_util.hpp"
 #include "integ_compose.hpp"
+#include "helix.hpp"
 #include <algorithm>
+#include <string>
 #include <cmath>
 #include <random>
 
@@ -54,6 +56,20 @@ __host__ __device__ constexpr double binom(int n, int k)
 __global__ __launch_bounds__(kB) void f2d_axpy_kernel(double *__restrict__ b, const double *__restrict__ a, double ds, long long n2)
 {
 	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n2; i += (long long)gridDim.x * kB) b[i] += a[i] * ds;
+}
+
+// the drift in a uniform magnetic field out of the plane (include/nbco.h, nbco_2d_drift_b): x += A v, v = R v, both from the old v
+__global__ __launch_bounds__(kB) void f2d_drift_b_kernel(double2 *__restrict__ x, double2 *__restrict__ v, Helix2 h, long long n)
+{
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		double2 p = x[i];
+		const double2 u = v[i];
+		p.x = fma(h.A[1], u.y, fma(h.A[0], u.x, p.x));
+		p.y = fma(h.A[3], u.y, fma(h.A[2], u.x, p.y));
+		x[i] = p;
+		v[i] = make_double2(fma(h.R[1], u.y, h.R[0] * u.x), fma(h.R[3], u.y, h.R[2] * u.x));
+	}
 }
 
 __global__ __launch_bounds__(kB) void f2d_elastic_kernel(const double2 *__restrict__ x, double2 *__restrict__ a, long long n,
@@ -830,6 +846,16 @@ static int f2d_step(nbco_ctx *c, double *b, const double *a, long double ds, lon
 	return NBCO_OK;
 }
 
+static int f2d_drift_b(nbco_ctx *c, double *x, double *v, double omega, long double ds, long long n)
+{
+	Helix2 h;
+	if (nbco_2d_helix_matrices(omega, (double)ds, h.R, h.A) != NBCO_OK) return c->fail(NBCO_ERR_ARG, "nbco_2d_drift_b: omega and s must be finite");
+	if (n <= 0) return NBCO_OK;
+	hipLaunchKernelGGL(f2d_drift_b_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, c->stream, (double2 *)x, (double2 *)v, h, n);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
 static int f2d_eval(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)
 {
 	double *a = buf + 4 * n;
@@ -903,34 +929,69 @@ int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double 
 	return f2d_done(c);
 }
 
-int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt_, double scale_, int elastic)
+// omega = 0: the straight drift of the reference; otherwise the helix drift replaces it (nbco_2d_integrate_b)
+static int f2d_integrate(nbco_ctx *c, const char *who, int scheme, int kind, double *buf, long long n, const double *param, double dt_, double scale_,
+                         int elastic, double omega)
 {
 	if (!c) return NBCO_ERR_ARG;
-	if (!buf || !param || n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: bad arguments");
-	if (kind < NBCO_2D_EVAL_DIRECT || kind > NBCO_2D_EVAL_FMM) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown evaluator kind");
-	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate: unknown scheme");
+	const std::string w(who);
+	if (!buf || !param || n <= 0) return c->fail(NBCO_ERR_ARG, w + ": bad arguments");
+	if (kind < NBCO_2D_EVAL_DIRECT || kind > NBCO_2D_EVAL_FMM) return c->fail(NBCO_ERR_ARG, w + ": unknown evaluator kind");
+	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, w + ": unknown scheme");
+	if (omega != 0.0 && (!std::isfinite(omega) || !std::isfinite(omega * dt_))) return c->fail(NBCO_ERR_ARG, w + ": omega must be finite");
 	if (kind == NBCO_2D_EVAL_FMM) NBCO_TRY(f2d_fmm_check(c, n));
 	double *x = buf, *v = buf + 2 * n, *a = buf + 4 * n;
 	const long double dt = dt_, scale = scale_;
 	auto K = [&](long double s) { return f2d_step(c, v, a, s, n); };
-	auto D = [&](long double s) { return f2d_step(c, x, v, s, n); };
+	auto D = [&](long double s) { return omega == 0.0 ? f2d_step(c, x, v, s, n) : f2d_drift_b(c, x, v, omega, s, n); };
 	auto F = [&]() { return f2d_eval(c, kind, buf, n, param, elastic); };
 	NBCO_TRY(integ_compose(scheme, dt, scale, K, D, F));
 	return f2d_done(c);
 }
 
-int nbco_2d_integrate_steps(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
-                            int elastic, int steps)
+static int f2d_integrate_steps(nbco_ctx *c, const char *who, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                               int elastic, int steps, double omega)
 {
 	if (!c) return NBCO_ERR_ARG;
-	if (steps < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate_steps: steps < 0");
+	if (steps < 0) return c->fail(NBCO_ERR_ARG, std::string(who) + ": steps < 0");
 	const int save = c->o.sync;
 	c->o.sync = 0;
 	int rc = NBCO_OK;
-	for (int s = 0; s < steps && rc == NBCO_OK; ++s) rc = nbco_2d_integrate(c, scheme, kind, buf, n, param, dt, scale, elastic);
+	for (int s = 0; s < steps && rc == NBCO_OK; ++s) rc = f2d_integrate(c, who, scheme, kind, buf, n, param, dt, scale, elastic, omega);
 	c->o.sync = save;
 	if (rc != NBCO_OK) return rc;
 	return f2d_done(c);
+}
+
+int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale, int elastic)
+{
+	return f2d_integrate(c, "nbco_2d_integrate", scheme, kind, buf, n, param, dt, scale, elastic, 0.0);
+}
+
+int nbco_2d_integrate_steps(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                            int elastic, int steps)
+{
+	return f2d_integrate_steps(c, "nbco_2d_integrate_steps", scheme, kind, buf, n, param, dt, scale, elastic, steps, 0.0);
+}
+
+int nbco_2d_drift_b(nbco_ctx *c, double *x, double *v, long long n, double omega, double s)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!x || !v || n < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_drift_b: bad arguments");
+	NBCO_TRY(f2d_drift_b(c, x, v, omega, s, n));
+	return f2d_done(c);
+}
+
+int nbco_2d_integrate_b(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale, int elastic,
+                        double omega)
+{
+	return f2d_integrate(c, "nbco_2d_integrate_b", scheme, kind, buf, n, param, dt, scale, elastic, omega);
+}
+
+int nbco_2d_integrate_steps_b(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                              int elastic, int steps, double omega)
+{
+	return f2d_integrate_steps(c, "nbco_2d_integrate_steps_b", scheme, kind, buf, n, param, dt, scale, elastic, steps, omega);
 }
 
 int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host)

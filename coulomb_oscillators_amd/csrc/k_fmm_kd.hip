@@ -32,6 +32,8 @@
 #include "k_p2p.hpp"
 #include "kd_common.hpp"
 #include "host_util.hpp"
+#include "helix.hpp"
+#include <type_traits>
 #include <chrono>
 #include <cmath>
 #include <algorithm>
@@ -902,7 +904,9 @@ int kd_finish_pending_order(nbco_ctx *c, float *p, long long n, KdStepLink *link
 
 // nbco_integrate_steps, between the force evaluation of one leapfrog step and that of the next (kd_turnaround_kernel).  link->v_now:
 // where the velocities are (the caller's array or the scratch copy of the turnaround before), and where they are afterwards.
-int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6)
+// helix: null, or the matrices of the drift in a magnetic field, which then replaces x += v ds (nbco_integrate_steps_b).
+int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6,
+                  const Helix3 *helix)
 {
 	const bool gather = link->order_pending;
 	link->order_pending = false;
@@ -928,10 +932,15 @@ int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds,
 	PhaseScope ph(c, NBCO_PH_AXPY);
 	TreeView tv = view_of(c->kd);
 	hipStream_t st = c->stream;
-#define NBCO_TURN_ARGS c->pos4.as<float4>(), c->unsort.as<int>(), x, v_in, v_out, (const float *)a, param, ks, ds, elastic ? 1 : 0, n, next_rebuild ? 1 : 0, \
+#define NBCO_TURN_ARGS(drift) c->pos4.as<float4>(), c->unsort.as<int>(), x, v_in, v_out, (const float *)a, param, ks, drift, elastic ? 1 : 0, n, next_rebuild ? 1 : 0, \
 	c->sel_hist.as<uint32_t>(), words_a, c->sel_nodes.as<uint32_t>(), words_b, c->counters.as<int>() + 110, c->prep_state.as<unsigned>(), tv, root6
-	if (gather) hipLaunchKernelGGL(kd_turnaround_kernel<true>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS);
-	else hipLaunchKernelGGL(kd_turnaround_kernel<false>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS);
+	if (helix)
+	{
+		if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, Helix3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix));
+		else hipLaunchKernelGGL((kd_turnaround_kernel<false, Helix3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix));
+	}
+	else if (gather) hipLaunchKernelGGL(kd_turnaround_kernel<true>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds));
+	else hipLaunchKernelGGL(kd_turnaround_kernel<false>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds));
 #undef NBCO_TURN_ARGS
 	NBCO_HIP(hipGetLastError());
 	link->prep_done = next_rebuild ? 1 : 2;

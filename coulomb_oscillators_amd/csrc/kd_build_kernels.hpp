@@ -1,6 +1,7 @@
 // kd_build_kernels.hpp -- part of k_fmm_kd.hip (included there, in this place: one translation unit, one anonymous namespace)
 // tree geometry (rounded like the oracle), build prologue, the fused turnaround pass, per-level kernels of the sorting build, the in-LDS subtree build
-// (no include guard on purpose: this is a section of that file, not a header)
+// (no include guard on purpose: this is a section of that file, not a header; it sits inside that file's anonymous namespace, so it
+// includes nothing itself: std::is_same and helix_drift come from <type_traits> and helix.hpp, which k_fmm_kd.hip includes at its top)
 // ---- tree geometry: every function below must round exactly like the oracle ---------------------
 #pragma clang fp contract(off)
 
@@ -100,10 +101,11 @@ __global__ __launch_bounds__(kPrepBlock) void kd_prep_kernel(const float *__rest
 // cleared selection state (kd_prep_kernel).  Here every particle goes through exactly those operations, in that order and
 // with the same roundings, in registers.  GATHER: the evaluation rebuilt the tree (velocities come through `unsort`, v_out
 // must not be v_in); PREP: 1 = the next evaluation rebuilds (full build prologue), 0 = it reuses the tree (positions packed only).
-template <bool GATHER>
+// Drift = float: the straight drift x += v ds, as ever.  Drift = Helix3: nbco_integrate_steps_b, the drift of kick_drift_kernel<Helix3>.
+template <bool GATHER, class Drift = float>
 __global__ __launch_bounds__(kPrepBlock) void kd_turnaround_kernel(float4 *__restrict__ pos4, int *__restrict__ unsort, float *__restrict__ x3,
                                                                    const float *v_in, float *v_out, const float *__restrict__ a3,
-                                                                   const float *__restrict__ param, float ks, float ds, int elastic, long long n, int prep,
+                                                                   const float *__restrict__ param, float ks, Drift ds, int elastic, long long n, int prep,
                                                                    uint32_t *__restrict__ zero_a, long long words_a, uint32_t *__restrict__ zero_b,
                                                                    long long words_b, int *__restrict__ flag, unsigned *__restrict__ state, TreeView t,
                                                                    const float *__restrict__ root6)
@@ -151,9 +153,10 @@ __global__ __launch_bounds__(kPrepBlock) void kd_turnaround_kernel(float4 *__res
 				if (elastic) ai = fmaf(-k3[c], x[u][c], ai);
 				float vi = fmaf(ks, ai, v[u][c]);
 				vi = fmaf(ks, ai, vi);                                     // kick_drift_kernel
-				x[u][c] = fmaf(ds, vi, x[u][c]);
+				if constexpr (std::is_same<Drift, float>::value) x[u][c] = fmaf(ds, vi, x[u][c]);
 				v[u][c] = vi;
 			}
+			if constexpr (!std::is_same<Drift, float>::value) helix_drift(ds, x[u], v[u]);
 			x3[3 * i] = x[u][0]; x3[3 * i + 1] = x[u][1]; x3[3 * i + 2] = x[u][2];
 			v_out[3 * i] = v[u][0]; v_out[3 * i + 1] = v[u][1]; v_out[3 * i + 2] = v[u][2];
 			pos4[i] = make_float4(x[u][0], x[u][1], x[u][2], 0.f);          // kd_prep_kernel / pack4

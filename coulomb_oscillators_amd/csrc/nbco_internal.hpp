@@ -362,6 +362,10 @@ int launch_pack4(nbco_ctx *c, float4 *dst, const float *src3, long long n);
 // fused integrator pieces
 int launch_kick_drift(nbco_ctx *c, float *x, float *v, const float *a, float ks, float ds, long long n3);
 int launch_finish_kick(nbco_ctx *c, const float *x, const float *v_in, float *v, float *a, const float *param, float ks, long long n, bool elastic);
+// the drift in a uniform magnetic field (helix.hpp), alone and behind the kick K(ks)
+struct Helix3;
+int launch_drift_b(nbco_ctx *c, float *x, float *v, const Helix3 &h, long long n);
+int launch_kick_drift_b(nbco_ctx *c, float *x, float *v, const float *a, float ks, const Helix3 &h, long long n);
 // k_direct.hip
 int launch_direct(nbco_ctx *c, const float *p, float *a, long long n, const float *param, bool kahan);
 // k_reduce.hip
@@ -418,7 +422,8 @@ int dpart_workspace(nbco_ctx *c, long long n_global, int world, long long *bytes
 int dpart_begin(nbco_ctx *c, float *state_local, long long n_global, int world, int rank, void *work, long long work_bytes, nbco_dist_step *out);
 int dpart_next(nbco_ctx *c, nbco_dist_step *out);
 int kd_finish_pending_order(nbco_ctx *c, float *p, long long n, KdStepLink *link);
-int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6 = nullptr);
+int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6 = nullptr,
+                  const Helix3 *helix = nullptr);
 int kd_dist_turnaround(nbco_ctx *c, float *buf_local, long long n_local, const float *param, float ks, float ds, bool elastic);
 int kd_dist_let_select(nbco_ctx *c, const void *csz_all, long long *counts);
 int kd_dist_let_pack(nbco_ctx *c, const long long *counts_all, void *pos_send, void *mpole_send);

@@ -147,6 +147,14 @@ def _load():
         "nbco_force": [P, I, P, LL, P, I],
         "nbco_integrate": [P, I, I, P, LL, P, D, D, I],
         "nbco_integrate_steps": [P, I, I, P, LL, P, D, D, I, I],
+        "nbco_helix_matrices": [C.POINTER(D), D, C.POINTER(D), C.POINTER(D)],
+        "nbco_2d_helix_matrices": [D, D, C.POINTER(D), C.POINTER(D)],
+        "nbco_drift_b": [P, P, P, LL, C.POINTER(D), D],
+        "nbco_integrate_b": [P, I, I, P, LL, P, D, D, I, C.POINTER(D)],
+        "nbco_integrate_steps_b": [P, I, I, P, LL, P, D, D, I, I, C.POINTER(D)],
+        "nbco_2d_drift_b": [P, P, P, LL, D, D],
+        "nbco_2d_integrate_b": [P, I, I, P, LL, P, D, D, I, D],
+        "nbco_2d_integrate_steps_b": [P, I, I, P, LL, P, D, D, I, I, D],
         "nbco_minmax": [P, P, LL, P],
         "nbco_mean_relerr": [P, P, P, LL, C.POINTER(F)],
         "nbco_pow_sum": [P, P, I, LL, C.POINTER(D)],
@@ -259,6 +267,31 @@ def init2d(n, kind="kv", a=None, b=None, seed=REF_SEED, discard=REF_DISCARD):
     if rc != 0:
         raise EngineError("nbco_2d_init_%s failed with status %d" % (kind, rc), status=rc)
     return out
+
+
+def _omega3(omega):
+    return None if omega is None else (C.c_double * 3)(*[float(w) for w in omega])
+
+
+def helix_matrices(omega, s):
+    """(R, A), float64 3 x 3: the helix drift of a uniform magnetic field Omega = omega over s, v <- R v, x <- x + A v with the old v
+    (nbco_helix_matrices, include/nbco.h).  Host only, needs no GPU; the one place the matrices are formed."""
+    import numpy as np
+    R, A = (C.c_double * 9)(), (C.c_double * 9)()
+    rc = _load().nbco_helix_matrices(_omega3(omega), float(s), R, A)
+    if rc != 0:
+        raise EngineError("nbco_helix_matrices failed with status %d" % rc, status=rc)
+    return np.array(R[:], dtype=np.float64).reshape(3, 3), np.array(A[:], dtype=np.float64).reshape(3, 3)
+
+
+def helix_matrices_2d(omega, s):
+    """the 2-D form: omega a scalar (the field points out of the plane), (R, A) float64 2 x 2 (nbco_2d_helix_matrices)"""
+    import numpy as np
+    R, A = (C.c_double * 4)(), (C.c_double * 4)()
+    rc = _load().nbco_2d_helix_matrices(float(omega), float(s), R, A)
+    if rc != 0:
+        raise EngineError("nbco_2d_helix_matrices failed with status %d" % rc, status=rc)
+    return np.array(R[:], dtype=np.float64).reshape(2, 2), np.array(A[:], dtype=np.float64).reshape(2, 2)
 
 
 def default_opts(**kw):
@@ -376,6 +409,34 @@ class Engine:
     def integrate_steps(self, scheme, kind, buf, n, param, dt, steps, scale=1.0, elastic=True):
         """`steps` steps in one call (nbco_integrate_steps): same final state as `steps` calls of integrate()"""
         self._chk(self.lib.nbco_integrate_steps(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps)))
+
+    # ---- uniform magnetic field: the drift along a helix (include/nbco.h) ---------------------------------------------------
+    helix_matrices = staticmethod(helix_matrices)
+    helix_matrices_2d = staticmethod(helix_matrices_2d)
+
+    def drift_b(self, x, v, n, omega, s):
+        """the helix drift of n particles in the uniform field omega = (wx, wy, wz) over s (nbco_drift_b): x and v are float32 device
+        tensors of xyz triplets, both rewritten from the old v"""
+        self._chk(self.lib.nbco_drift_b(self.ctx, _ptr(x), _ptr(v), n, _omega3(omega), float(s)))
+
+    def integrate_b(self, scheme, kind, buf, n, param, dt, omega, scale=1.0, elastic=True):
+        """integrate() with the drift replaced by the helix drift of the uniform field omega, in radians per unit of dt
+        (nbco_integrate_b); omega = (0, 0, 0) is integrate() itself"""
+        self._chk(self.lib.nbco_integrate_b(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), _omega3(omega)))
+
+    def integrate_steps_b(self, scheme, kind, buf, n, param, dt, steps, omega, scale=1.0, elastic=True):
+        """`steps` steps in one call (nbco_integrate_steps_b): same final state as `steps` calls of integrate_b()"""
+        self._chk(self.lib.nbco_integrate_steps_b(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps), _omega3(omega)))
+
+    def drift_b_2d(self, x, v, n, omega, s):
+        """the 2-D form: float64 xy pairs, omega a scalar (nbco_2d_drift_b)"""
+        self._chk(self.lib.nbco_2d_drift_b(self.ctx, _ptr(x), _ptr(v), n, float(omega), float(s)))
+
+    def integrate_b_2d(self, scheme, kind, buf, n, param, dt, omega, scale=1.0, elastic=True):
+        self._chk(self.lib.nbco_2d_integrate_b(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), float(omega)))
+
+    def integrate_steps_b_2d(self, scheme, kind, buf, n, param, dt, steps, omega, scale=1.0, elastic=True):
+        self._chk(self.lib.nbco_2d_integrate_steps_b(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps), float(omega)))
 
     # ---- 2-D fp64 evaluators (main.cu): float64 tensors, xy pairs, param = {xi/N, 0, kx, ky} -------------------------------
     def direct_2d(self, p, a, n, param=None):

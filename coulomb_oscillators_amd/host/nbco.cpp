@@ -76,6 +76,9 @@ const char *kHelp =
     "                    <dir>/losses.txt one line `iter n_lost n_left`; the snapshot and -energy, -moments, -probes\n"
     "                    describe the survivors, and the snapshot files shrink with n; a run that loses everybody ends\n"
     "                    with an error; refused with -test\n"
+    "  -B <w>            uniform magnetic field out of the plane, Omega = (q/m) B in radians per unit of -ds: the force\n"
+    "                    (vy, -vx) w, integrated exactly -- the drift of every scheme becomes a rotation\n"
+    "                    (nbco_2d_integrate_b); 0 is the run without the flag; no effect with -test\n"
     "  -ga               Gaussian initial state instead of KV\n"
     "  -xi <v>           perveance\n"
     "  -omega0 <x> <y>   trap phase advances\n"
@@ -102,7 +105,7 @@ int main(const int argc, const char **argv)
 {
 	int nBodies = 30001, nIters = 30001, nSteps = 200, integ = NBCO_INTEG_LEAPFROG;
 	int fmm_order = 5, tree_radius = 1;
-	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1;
+	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1, omega_b = 0;
 	std::string strout("out"), strin, strprobes;
 	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false, moments = false;
 	bool aperture = false;
@@ -199,6 +202,13 @@ int main(const int argc, const char **argv)
 			if (need(i, 1, a)) return missing();
 			dens_inhom = std::atof(argv[i + 1]);
 			if (dens_inhom <= 0) return invalid(argv[i + 1], " (should be greater than 0)");
+			++i;
+		}
+		else if (is(a, "B"))
+		{
+			if (need(i, 1, a)) return missing();
+			omega_b = std::atof(argv[i + 1]);
+			if (!std::isfinite(omega_b)) return invalid(argv[i + 1], " (should be finite)");
 			++i;
 		}
 		else if (is(a, "ncoll")) coll = false;
@@ -425,7 +435,7 @@ int main(const int argc, const char **argv)
 	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return finish(-1);
 	for (int iter = 0; iter < nIters; ++iter)
 	{
-		if (!lib_ok(nbco_2d_integrate(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1))) return finish(-1);
+		if (!lib_ok(nbco_2d_integrate_b(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1, omega_b))) return finish(-1);
 		if (iter % nSteps == 0)
 		{
 			std::cout << iter << ' ' << std::flush;

@@ -94,6 +94,9 @@ const char *kHelp =
     "                    describe the survivors; the snapshot files shrink with n.  A run that loses everybody ends with an error.\n"
     "                    Refused with -test, -test2 and -accuracy.\n"
     "  -aperture-centre <cx> <cy> <cz>   Centre of the aperture (default 0 0 0).\n"
+    "  -B <wx> <wy> <wz> Uniform magnetic field Omega = (q/m) B in radians per unit of -ds: the force v x Omega, integrated exactly -- the\n"
+    "                    drift of every scheme becomes the motion along a helix (nbco_integrate_steps_b; with -cpu the same matrices and\n"
+    "                    arithmetic on the host).  0 0 0 is the run without the flag.  No effect with -test, -test2 or -accuracy.\n"
     "  -cpu              Run the simulation on the host: compensated direct sum O(N^2) over C++20 threads (small N; the test and\n"
     "                    tuning modes need the GPU).  -cpu-threads <n> sets the number of threads (default 8); -cacheline <n> is\n"
     "                    accepted and ignored.\n";
@@ -355,7 +358,8 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture, const SlicesOpt &slices)
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture, const SlicesOpt &slices,
+	             const double *omega)
 	{
 		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
@@ -400,7 +404,8 @@ struct Session
 				if (iter == kSteadyFrom) { check(nbco_sync(ctx()), "sync"); steady_t0 = std::chrono::steady_clock::now(); steady_first = iter; }
 				else if (iter < kSteadyFrom) run = std::min(run, kSteadyFrom - iter);   // (K steps in one call == the same steps in two calls, bit for bit)
 			}
-			check(nbco_integrate_steps(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run), "integrate");
+			if (omega) check(nbco_integrate_steps_b(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega), "integrate_b");
+			else check(nbco_integrate_steps(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run), "integrate");
 			iter += run;
 			if ((iter - 1) % nSteps != 0) continue;
 			const int snap = iter - 1;
@@ -549,7 +554,8 @@ int main(int argc, const char **argv)
 	PairsOpt pairs;
 	ApertureOpt aperture;
 	SlicesOpt slices;
-	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false;
+	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false, bfield = false;
+	double omega_b[3]{0, 0, 0};
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
 	SCAL xi = (SCAL)2.e-6;
@@ -720,6 +726,18 @@ int main(int argc, const char **argv)
 			}
 			i += 3;
 		}
+		else if (a == "-B")
+		{
+			if (!need(i, 3, "-B")) return -1;
+			for (int k = 0; k < 3; ++k) omega_b[k] = atof(argv[i + 1 + k]);
+			if (!std::isfinite(omega_b[0]) || !std::isfinite(omega_b[1]) || !std::isfinite(omega_b[2]))
+			{
+				std::cerr << "Error: invalid argument(s) to '-B': " << argv[i + 1] << ' ' << argv[i + 2] << ' ' << argv[i + 3] << " (three finite components)\n";
+				return -1;
+			}
+			bfield = omega_b[0] != 0 || omega_b[1] != 0 || omega_b[2] != 0;   // (0 0 0 IS the run without the flag, on the host path too)
+			i += 3;
+		}
 		else if (a == "-cpu-threads")
 		{
 			if (!need(i, 1, "-cpu-threads")) return -1;
@@ -834,7 +852,7 @@ int main(int argc, const char **argv)
 		std::vector<nbco_moments> slice_recs;
 		for (int iter = 0; iter < nIters; ++iter)
 		{
-			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt);
+			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr);
 			if (iter % nSteps != 0) continue;
 			std::cout << iter << ' ' << std::flush;
 			if (aperture.on)
@@ -904,7 +922,7 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices);
+		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr);
 	}
 	return rc;
 }

@@ -261,13 +261,35 @@ inline void aperture_apply(std::vector<V3> &buf, int &n, int shape, const double
 	n = kept;
 }
 
-// one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call)
+// The drift in a uniform magnetic field Omega over s (`nbco3 -cpu -B`; include/nbco.h, nbco_drift_b): the matrices from
+// nbco_helix_matrices, narrowed to float, and per particle the fmaf order of the device kernels, both lines from the old v.
+inline void drift_b(V3 *x, V3 *v, const double *omega, double s, int n)
+{
+	double Rd[9], Ad[9];
+	nbco_helix_matrices(omega, s, Rd, Ad);
+	float R[9], A[9];
+	for (int i = 0; i < 9; ++i) { R[i] = (float)Rd[i]; A[i] = (float)Ad[i]; }
+	const float *r = R, *m = A;
+	for_ranges(n, [=](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			const V3 u = v[i], p = x[i];
+			x[i] = V3{std::fmaf(m[2], u.z, std::fmaf(m[1], u.y, std::fmaf(m[0], u.x, p.x))), std::fmaf(m[5], u.z, std::fmaf(m[4], u.y, std::fmaf(m[3], u.x, p.y))),
+			          std::fmaf(m[8], u.z, std::fmaf(m[7], u.y, std::fmaf(m[6], u.x, p.z)))};
+			v[i] = V3{std::fmaf(r[2], u.z, std::fmaf(r[1], u.y, r[0] * u.x)), std::fmaf(r[5], u.z, std::fmaf(r[4], u.y, r[3] * u.x)),
+			          std::fmaf(r[8], u.z, std::fmaf(r[7], u.y, r[6] * u.x))};
+		}
+	});
+}
+
+// one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call); omega: null, or
+// the uniform magnetic field whose helix drift replaces x += v c
 enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
-inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt)
+inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega = nullptr)
 {
 	V3 *x = buf, *v = buf + n, *a = buf + 2 * (size_t)n;
 	auto K = [&](long double c) { step(v, a, (float)c, n); };
-	auto D = [&](long double c) { step(x, v, (float)c, n); };
+	auto D = [&](long double c) { if (omega) drift_b(x, v, omega, (double)c, n); else step(x, v, (float)c, n); };
 	auto F = [&] { force(buf, n, par, eps2); };
 	switch (s)
 	{

@@ -156,6 +156,42 @@ int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, c
 int nbco_integrate_steps(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
                          double dt, double scale, int elastic, int steps);
 
+/* ---- uniform magnetic field: the drift along a helix -------------------------------------------------------------------------
+ * A uniform field Omega = (q/m) B adds the velocity-dependent force a_mag = v x Omega, which no kick v += a s expresses.  The flow
+ * of "free motion in a uniform field" is known in closed form, and it replaces the drift D(s): x += v s of the five schemes, which
+ * stay symplectic and keep their order; a free particle gyrates exactly at any step.  With w = |Omega|, n = Omega / w,
+ * N v = n x v and theta = w s (s may be negative: PEFRL has negative drift coefficients)
+ *
+ *   R(s) = I - sin(theta) N + (1 - cos(theta)) N^2                          v <- R v
+ *   A(s) = s I - ((1 - cos(theta)) / w) N + ((theta - sin(theta)) / w) N^2   x <- x + A v   (with the OLD v)
+ *
+ * (dA/ds = R, dR/ds = -w N R, which is dv/dt = v x Omega).  In 2-D Omega is a scalar, the field points out of the plane, and
+ * N = [[0, -1], [1, 0]].  Omega is given in radians per unit of dt; `scale` multiplies kicks only and does not touch Omega.
+ *
+ * nbco_helix_matrices forms the two matrices, row-major, in double; host only, no GPU needed, and the one place they are formed:
+ * the device calls below, `nbco3 -cpu` and the tests take them from it.  1 - cos(theta) is 2 sin^2(theta / 2) and theta - sin(theta)
+ * a series below |theta| = 0.5, w and theta carry a correction term each, so every element is within a few ulp of the matrix's
+ * largest at any theta; w = 0 gives R = I and A = s I exactly.  NBCO_ERR_ARG: a null pointer or a non-finite Omega or s. */
+int nbco_helix_matrices(const double *omega3, double s, double *R9, double *A9);
+int nbco_2d_helix_matrices(double omega, double s, double *R4, double *A4);
+/* The helix drift of n particles on the context's stream.  The state is fp32: the matrices are narrowed to float once on the host,
+ * and per component c, one rounding per fmaf, both lines from the old v:
+ *   x'[c] = fmaf(A[c][2], vz, fmaf(A[c][1], vy, fmaf(A[c][0], vx, x[c])))
+ *   v'[c] = fmaf(R[c][2], vz, fmaf(R[c][1], vy, R[c][0] * vx))
+ * Every kernel that contains the drift uses this order.  Like a drift of nbco_integrate it marks the particles as moved since the
+ * last kd-tree evaluation (nbco_kd_probe refuses).  NBCO_ERR_ARG: a null pointer, n < 0, a non-finite Omega or s. */
+int nbco_drift_b(nbco_ctx *c, float *x, float *v, long long n, const double *omega3_host, double s);
+/* nbco_integrate and nbco_integrate_steps with the drift replaced by the helix drift; K and F are as they are.  Omega = 0 exactly:
+ * the call IS the counterpart, the bytes are identical.  Leapfrog fuses as there: the kick and the drift are one pass, and over the
+ * kd-tree evaluator (opts.unsort = 0, no order tracking, steps >= 2) what lies between two force evaluations is one pass; the
+ * final state of nbco_integrate_steps_b is bit-identical to `steps` calls of nbco_integrate_b.  Refused before any launch, the state
+ * untouched: NBCO_ERR_ARG for a null omega3_host or a non-finite Omega, and everything the counterparts refuse.
+ * Not offered: the nbco_dist_* path (nbco_dist_turnaround drifts straight) and non-uniform fields. */
+int nbco_integrate_b(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
+                     double dt, double scale, int elastic, const double *omega3_host);
+int nbco_integrate_steps_b(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
+                           double dt, double scale, int elastic, int steps, const double *omega3_host);
+
 /* ---- reductions (reductions.cuh) -------------------------------------------------------------- */
 int nbco_minmax(nbco_ctx *c, const float *p, long long n, float *minmax6_dev);           /* reductions.cuh:67 minmaxReduce2 */
 int nbco_mean_relerr(nbco_ctx *c, const float *x, const float *ref, long long n, float *out_host);  /* reductions.cuh:99 relerrReduce2 (intent) */
@@ -499,6 +535,17 @@ int nbco_2d_integrate(nbco_ctx *c, int scheme, int kind, double *buf, long long 
 /* `steps` calls of nbco_2d_integrate, bit for bit (main.cu:855-893 loop body) */
 int nbco_2d_integrate_steps(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt,
                             double scale, int elastic, int steps);
+/* The helix drift in 2-D (see nbco_drift_b; the field points out of the plane, omega is a scalar): fp64 state, double matrices from
+ * nbco_2d_helix_matrices, x'[c] = fma(A[c][1], vy, fma(A[c][0], vx, x[c])), v'[c] = fma(R[c][1], vy, R[c][0] * vx), both from the
+ * old v.  The integrators are nbco_2d_integrate / nbco_2d_integrate_steps with the drift replaced; omega = 0 exactly: the call is the
+ * counterpart.  NBCO_ERR_ARG before any launch: a non-finite omega (or s) and everything the counterparts refuse.  Unlike nbco_drift_b
+ * these drifts leave the context's "moved since the last kd-tree evaluation" mark alone, as the drift of nbco_2d_integrate does:
+ * the mark belongs to the 3-D kd-tree (nbco_kd_probe reads it) and no 2-D call reads it. */
+int nbco_2d_drift_b(nbco_ctx *c, double *x, double *v, long long n, double omega, double s);
+int nbco_2d_integrate_b(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                        int elastic, double omega);
+int nbco_2d_integrate_steps_b(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt,
+                              double scale, int elastic, int steps, double omega);
 /* reductions.cuh:99 relerrReduce2: mean over particles of sqrt(|x_i - ref_i|^2 / (|ref_i|^2 + 1e-18)) (rel_diff1, :37-42;
  * main.cu:172 test_accuracy); syncs */
 int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host);
