@@ -5,6 +5,7 @@
 // 16-byte vectors sized to fill 256 CUs.
 #include "nbco_internal.hpp"
 #include "helix.hpp"
+#include "bath.hpp"
 #include <type_traits>
 
 namespace {
@@ -188,6 +189,31 @@ __global__ __launch_bounds__(kBlock) void helix_vec(float4 *__restrict__ x, floa
 	}
 }
 
+// the Langevin bath step O(s) of nbco_bath_apply (bath.hpp): velocities only, a lane owns whole particles.  The noise is keyed by the
+// particle's row, so the vector form (four particles per thread, three 16-byte accesses) and the scalar form give the same bits.
+__global__ __launch_bounds__(kBlock) void bath_scalar(float *__restrict__ v, Bath3 b, long long beg, long long n)
+{
+	for (long long i = beg + (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
+	{
+		float vi[3] = {v[3 * i], v[3 * i + 1], v[3 * i + 2]};
+		bath_kick(b, i, vi);
+#pragma unroll
+		for (int c = 0; c < 3; ++c) v[3 * i + c] = vi[c];
+	}
+}
+
+__global__ __launch_bounds__(kBlock) void bath_vec(float4 *__restrict__ v, Bath3 b, long long ngroups)
+{
+	for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < ngroups; g += (long long)gridDim.x * kBlock)
+	{
+		float vp[4][3];
+		unpack4(v[3 * g], v[3 * g + 1], v[3 * g + 2], vp);
+#pragma unroll
+		for (int u = 0; u < 4; ++u) bath_kick(b, 4 * g + u, vp[u]);
+		pack4(vp, v + 3 * g);
+	}
+}
+
 // fused tail of a force evaluation + kick: a = a*param[0] - k o x (rescale + add_elastic), v += a*ks
 // (v_in != v: the evaluator left the tree-ordered velocities in a scratch buffer and this kick brings them home)
 __global__ __launch_bounds__(kBlock) void finish_kick_kernel(const float *__restrict__ x, const float *v_in, float *v, float *__restrict__ a,
@@ -309,6 +335,18 @@ static int launch_helix(nbco_ctx *c, float *x, float *v, const float *a, float k
 int launch_drift_b(nbco_ctx *c, float *x, float *v, const Helix3 &h, long long n) { return launch_helix(c, x, v, nullptr, 0.f, h, n); }
 
 int launch_kick_drift_b(nbco_ctx *c, float *x, float *v, const float *a, float ks, const Helix3 &h, long long n) { return launch_helix(c, x, v, a, ks, h, n); }
+
+// O(s) of the Langevin bath on the velocities of n particles, rows 0 .. n - 1 (nbco_bath_apply)
+int launch_bath(nbco_ctx *c, float *v, const Bath3 &b, long long n)
+{
+	if (n <= 0) return NBCO_OK;
+	const long long groups = aligned16(v) ? n / 4 : 0;
+	if (groups > 0) hipLaunchKernelGGL(bath_vec, dim3(stream_grid(groups)), dim3(kBlock), 0, c->stream, (float4 *)v, b, groups);
+	const long long done = 4 * groups;
+	if (done < n) hipLaunchKernelGGL(bath_scalar, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, v, b, done, n);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
 
 int launch_finish_kick(nbco_ctx *c, const float *x, const float *v_in, float *v, float *a, const float *param, float ks, long long n, bool elastic)
 {

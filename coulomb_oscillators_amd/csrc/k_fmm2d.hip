@@ -26,6 +26,7 @@
 #include "host_util.hpp"
 #include "integ_compose.hpp"
 #include "helix.hpp"
+#include "bath.hpp"
 #include <algorithm>
 #include <string>
 #include <cmath>
@@ -69,6 +70,18 @@ __global__ __launch_bounds__(kB) void f2d_drift_b_kernel(double2 *__restrict__ x
 		p.y = fma(h.A[3], u.y, fma(h.A[2], u.x, p.y));
 		x[i] = p;
 		v[i] = make_double2(fma(h.R[1], u.y, h.R[0] * u.x), fma(h.R[3], u.y, h.R[2] * u.x));
+	}
+}
+
+// the Langevin bath step O(s) on the velocities (include/nbco.h, nbco_2d_bath_apply; bath.hpp), one particle per lane
+__global__ __launch_bounds__(kB) void f2d_bath_kernel(double2 *__restrict__ v, Bath2 b, long long n)
+{
+	for (long long i = (long long)blockIdx.x * kB + threadIdx.x; i < n; i += (long long)gridDim.x * kB)
+	{
+		const double2 u = v[i];
+		double w[2] = {u.x, u.y};
+		bath_kick(b, i, w);
+		v[i] = make_double2(w[0], w[1]);
 	}
 }
 
@@ -856,6 +869,20 @@ static int f2d_drift_b(nbco_ctx *c, double *x, double *v, double omega, long dou
 	return NBCO_OK;
 }
 
+// O(s) of the bath on n velocities; false from the coefficients: gamma, kT or s is not finite or negative
+static int f2d_bath(nbco_ctx *c, double *v, const nbco_bath *bath, double s, int half, unsigned long long tick, long long n)
+{
+	Bath2 b;
+	if (bath_coeffs_dim(bath, s, b.c1, b.c2, 2) != NBCO_OK) return c->fail(NBCO_ERR_ARG, "nbco_2d_bath_apply: gamma, kT and s must be finite and not negative");
+	b.key[0] = (uint32_t)bath->seed; b.key[1] = (uint32_t)(bath->seed >> 32);
+	b.tick[0] = (uint32_t)tick; b.tick[1] = (uint32_t)(tick >> 32);
+	b.half = half;
+	if (n <= 0) return NBCO_OK;
+	hipLaunchKernelGGL(f2d_bath_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, c->stream, (double2 *)v, b, n);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
 static int f2d_eval(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)
 {
 	double *a = buf + 4 * n;
@@ -929,9 +956,10 @@ int nbco_2d_force(nbco_ctx *c, int kind, double *buf, long long n, const double 
 	return f2d_done(c);
 }
 
-// omega = 0: the straight drift of the reference; otherwise the helix drift replaces it (nbco_2d_integrate_b)
+// omega = 0: the straight drift of the reference; otherwise the helix drift replaces it (nbco_2d_integrate_b).  bath: null, or the
+// Langevin bath whose two half steps wrap the scheme (nbco_2d_integrate_t); with every gamma 0 it is no bath.
 static int f2d_integrate(nbco_ctx *c, const char *who, int scheme, int kind, double *buf, long long n, const double *param, double dt_, double scale_,
-                         int elastic, double omega)
+                         int elastic, double omega, const nbco_bath *bath = nullptr, unsigned long long tick = 0)
 {
 	if (!c) return NBCO_ERR_ARG;
 	const std::string w(who);
@@ -939,25 +967,35 @@ static int f2d_integrate(nbco_ctx *c, const char *who, int scheme, int kind, dou
 	if (kind < NBCO_2D_EVAL_DIRECT || kind > NBCO_2D_EVAL_FMM) return c->fail(NBCO_ERR_ARG, w + ": unknown evaluator kind");
 	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, w + ": unknown scheme");
 	if (omega != 0.0 && (!std::isfinite(omega) || !std::isfinite(omega * dt_))) return c->fail(NBCO_ERR_ARG, w + ": omega must be finite");
+	if (bath)
+	{
+		if (!bath_valid(bath, 2)) return c->fail(NBCO_ERR_ARG, w + ": gamma and kT must be finite and not negative");
+		if (bath_off(bath, 2)) bath = nullptr;
+		else if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n must be below 2^31 (the row is one counter word)");
+		else if (!std::isfinite(dt_) || dt_ < 0.0) return c->fail(NBCO_ERR_ARG, w + ": dt must be finite and not negative with a bath");
+	}
 	if (kind == NBCO_2D_EVAL_FMM) NBCO_TRY(f2d_fmm_check(c, n));
 	double *x = buf, *v = buf + 2 * n, *a = buf + 4 * n;
 	const long double dt = dt_, scale = scale_;
+	if (bath) NBCO_TRY(f2d_bath(c, v, bath, 0.5 * dt_, 0, tick, n));
 	auto K = [&](long double s) { return f2d_step(c, v, a, s, n); };
 	auto D = [&](long double s) { return omega == 0.0 ? f2d_step(c, x, v, s, n) : f2d_drift_b(c, x, v, omega, s, n); };
 	auto F = [&]() { return f2d_eval(c, kind, buf, n, param, elastic); };
 	NBCO_TRY(integ_compose(scheme, dt, scale, K, D, F));
+	if (bath) NBCO_TRY(f2d_bath(c, v, bath, 0.5 * dt_, 1, tick, n));
 	return f2d_done(c);
 }
 
 static int f2d_integrate_steps(nbco_ctx *c, const char *who, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
-                               int elastic, int steps, double omega)
+                               int elastic, int steps, double omega, const nbco_bath *bath = nullptr, unsigned long long tick0 = 0)
 {
 	if (!c) return NBCO_ERR_ARG;
 	if (steps < 0) return c->fail(NBCO_ERR_ARG, std::string(who) + ": steps < 0");
 	const int save = c->o.sync;
 	c->o.sync = 0;
 	int rc = NBCO_OK;
-	for (int s = 0; s < steps && rc == NBCO_OK; ++s) rc = f2d_integrate(c, who, scheme, kind, buf, n, param, dt, scale, elastic, omega);
+	for (int s = 0; s < steps && rc == NBCO_OK; ++s)
+		rc = f2d_integrate(c, who, scheme, kind, buf, n, param, dt, scale, elastic, omega, bath, tick0 + (unsigned long long)s);
 	c->o.sync = save;
 	if (rc != NBCO_OK) return rc;
 	return f2d_done(c);
@@ -992,6 +1030,33 @@ int nbco_2d_integrate_steps_b(nbco_ctx *c, int scheme, int kind, double *buf, lo
                               int elastic, int steps, double omega)
 {
 	return f2d_integrate_steps(c, "nbco_2d_integrate_steps_b", scheme, kind, buf, n, param, dt, scale, elastic, steps, omega);
+}
+
+// ---- Langevin bath, 2-D (include/nbco.h): the bath reads gamma[0..1], kT[0..1] ----------------------------------------------------------
+int nbco_2d_bath_apply(nbco_ctx *c, double *v, long long n, const nbco_bath *bath, double s, int half, unsigned long long tick)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!v || !bath || n < 0) return c->fail(NBCO_ERR_ARG, "nbco_2d_bath_apply: bad arguments");
+	if (half != 0 && half != 1) return c->fail(NBCO_ERR_ARG, "nbco_2d_bath_apply: half must be 0 or 1");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_2d_bath_apply: n must be below 2^31 (the row is one counter word)");
+	NBCO_TRY(f2d_bath(c, v, bath, s, half, tick, n));
+	return f2d_done(c);
+}
+
+int nbco_2d_integrate_t(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale, int elastic,
+                        double omega, const nbco_bath *bath_host, unsigned long long tick)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!bath_host) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate_t: bath_host is NULL");
+	return f2d_integrate(c, "nbco_2d_integrate_t", scheme, kind, buf, n, param, dt, scale, elastic, omega, bath_host, tick);
+}
+
+int nbco_2d_integrate_steps_t(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                              int elastic, int steps, double omega, const nbco_bath *bath_host, unsigned long long tick0)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!bath_host) return c->fail(NBCO_ERR_ARG, "nbco_2d_integrate_steps_t: bath_host is NULL");
+	return f2d_integrate_steps(c, "nbco_2d_integrate_steps_t", scheme, kind, buf, n, param, dt, scale, elastic, steps, omega, bath_host, tick0);
 }
 
 int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host)

@@ -33,6 +33,7 @@
 #include "kd_common.hpp"
 #include "host_util.hpp"
 #include "helix.hpp"
+#include "bath.hpp"
 #include <type_traits>
 #include <chrono>
 #include <cmath>
@@ -905,8 +906,10 @@ int kd_finish_pending_order(nbco_ctx *c, float *p, long long n, KdStepLink *link
 // nbco_integrate_steps, between the force evaluation of one leapfrog step and that of the next (kd_turnaround_kernel).  link->v_now:
 // where the velocities are (the caller's array or the scratch copy of the turnaround before), and where they are afterwards.
 // helix: null, or the matrices of the drift in a magnetic field, which then replaces x += v ds (nbco_integrate_steps_b).
+// bath_close: null, or the closing half of the Langevin bath of the step that ends here (half = 1, its tick); the opening half of the next
+// step follows it inside the pass (nbco_integrate_steps_t).
 int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6,
-                  const Helix3 *helix)
+                  const Helix3 *helix, const Bath3 *bath_close)
 {
 	const bool gather = link->order_pending;
 	link->order_pending = false;
@@ -934,7 +937,18 @@ int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds,
 	hipStream_t st = c->stream;
 #define NBCO_TURN_ARGS(drift) c->pos4.as<float4>(), c->unsort.as<int>(), x, v_in, v_out, (const float *)a, param, ks, drift, elastic ? 1 : 0, n, next_rebuild ? 1 : 0, \
 	c->sel_hist.as<uint32_t>(), words_a, c->sel_nodes.as<uint32_t>(), words_b, c->counters.as<int>() + 110, c->prep_state.as<unsigned>(), tv, root6
-	if (helix)
+	if (bath_close)
+	{
+		const Bath3 &b = *bath_close;
+		if (helix)
+		{
+			if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, Helix3, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix), b);
+			else hipLaunchKernelGGL((kd_turnaround_kernel<false, Helix3, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix), b);
+		}
+		else if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, float, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds), b);
+		else hipLaunchKernelGGL((kd_turnaround_kernel<false, float, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds), b);
+	}
+	else if (helix)
 	{
 		if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, Helix3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix));
 		else hipLaunchKernelGGL((kd_turnaround_kernel<false, Helix3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix));

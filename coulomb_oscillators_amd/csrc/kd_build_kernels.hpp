@@ -1,7 +1,8 @@
 // kd_build_kernels.hpp -- part of k_fmm_kd.hip (included there, in this place: one translation unit, one anonymous namespace)
 // tree geometry (rounded like the oracle), build prologue, the fused turnaround pass, per-level kernels of the sorting build, the in-LDS subtree build
 // (no include guard on purpose: this is a section of that file, not a header; it sits inside that file's anonymous namespace, so it
-// includes nothing itself: std::is_same and helix_drift come from <type_traits> and helix.hpp, which k_fmm_kd.hip includes at its top)
+// includes nothing itself: std::is_same, helix_drift and bath_kick come from <type_traits>, helix.hpp and bath.hpp, which k_fmm_kd.hip
+// includes at its top)
 // ---- tree geometry: every function below must round exactly like the oracle ---------------------
 #pragma clang fp contract(off)
 
@@ -102,14 +103,20 @@ __global__ __launch_bounds__(kPrepBlock) void kd_prep_kernel(const float *__rest
 // with the same roundings, in registers.  GATHER: the evaluation rebuilt the tree (velocities come through `unsort`, v_out
 // must not be v_in); PREP: 1 = the next evaluation rebuilds (full build prologue), 0 = it reuses the tree (positions packed only).
 // Drift = float: the straight drift x += v ds, as ever.  Drift = Helix3: nbco_integrate_steps_b, the drift of kick_drift_kernel<Helix3>.
-template <bool GATHER, class Drift = float>
+// Bath: empty (no bath, and no argument: the plain and Helix3 instantiations keep their argument lists), or Bath3, the closing half of
+// the Langevin bath of the step that ends here (nbco_integrate_steps_t): between the two half kicks the velocity of output row i -- the
+// tree-order row, which the step-by-step sequence sees after reorder_state -- goes through bath_kick(half 1, tick) and then
+// bath_kick(half 0, tick + 1), the opening half of the next step.
+template <class T> __device__ __forceinline__ const T &turn_bath(const T &b) { return b; }
+template <bool GATHER, class Drift = float, class... Bath>
 __global__ __launch_bounds__(kPrepBlock) void kd_turnaround_kernel(float4 *__restrict__ pos4, int *__restrict__ unsort, float *__restrict__ x3,
                                                                    const float *v_in, float *v_out, const float *__restrict__ a3,
                                                                    const float *__restrict__ param, float ks, Drift ds, int elastic, long long n, int prep,
                                                                    uint32_t *__restrict__ zero_a, long long words_a, uint32_t *__restrict__ zero_b,
                                                                    long long words_b, int *__restrict__ flag, unsigned *__restrict__ state, TreeView t,
-                                                                   const float *__restrict__ root6)
+                                                                   const float *__restrict__ root6, Bath... bath)
 {
+	static_assert(sizeof...(Bath) <= 1, "at most one bath");
 	float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
 	const long long stride = (long long)gridDim.x * kPrepBlock, tid = (long long)blockIdx.x * kPrepBlock + threadIdx.x;
 	const float k3[3] = {param[3], param[4], param[5]};
@@ -151,8 +158,18 @@ __global__ __launch_bounds__(kPrepBlock) void kd_turnaround_kernel(float4 *__res
 			{
 				float ai = a[u][c];                                        // finish_kick_kernel (no rescale: the evaluator did it)
 				if (elastic) ai = fmaf(-k3[c], x[u][c], ai);
-				float vi = fmaf(ks, ai, v[u][c]);
-				vi = fmaf(ks, ai, vi);                                     // kick_drift_kernel
+				a[u][c] = ai;
+				v[u][c] = fmaf(ks, ai, v[u][c]);
+			}
+			if constexpr (sizeof...(Bath) != 0)
+			{
+				bath_kick(turn_bath(bath...), i, v[u]);                    // O(dt/2, half 1) of this step, O(dt/2, half 0) of the next
+				bath_kick(bath_next_open(turn_bath(bath...)), i, v[u]);
+			}
+#pragma unroll
+			for (int c = 0; c < 3; ++c)
+			{
+				const float vi = fmaf(ks, a[u][c], v[u][c]);               // kick_drift_kernel
 				if constexpr (std::is_same<Drift, float>::value) x[u][c] = fmaf(ds, vi, x[u][c]);
 				v[u][c] = vi;
 			}

@@ -4,6 +4,7 @@
 #include "nbco_internal.hpp"
 #include "integ_compose.hpp"
 #include "helix.hpp"
+#include "bath.hpp"
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -151,6 +152,34 @@ static int closing_kick(nbco_ctx *c, KdStepLink &link, Run run, float *buf, long
 	return launch_finish_kick(c, x, v_in, v, a, param, ds, n, elastic);
 }
 
+// ---- Langevin bath: coefficients of the exact Ornstein-Uhlenbeck step over s for the first `dim` axes (include/nbco.h; declared in
+// nbco_internal.hpp: the 2-D calls of k_fmm2d.hip use them with dim = 2)
+bool bath_valid(const nbco_bath *b, int dim)
+{
+	for (int a = 0; a < dim; ++a)
+		if (!std::isfinite(b->gamma[a]) || b->gamma[a] < 0.0 || !std::isfinite(b->kT[a]) || b->kT[a] < 0.0) return false;
+	return true;
+}
+
+bool bath_off(const nbco_bath *b, int dim)
+{
+	for (int a = 0; a < dim; ++a)
+		if (b->gamma[a] != 0.0) return false;
+	return true;
+}
+
+int bath_coeffs_dim(const nbco_bath *b, double s, double *c1, double *c2, int dim)
+{
+	if (!b || !c1 || !c2 || !bath_valid(b, dim) || !std::isfinite(s) || s < 0.0) return NBCO_ERR_ARG;
+	for (int a = 0; a < dim; ++a)
+	{
+		const double gs = b->gamma[a] * s;
+		c1[a] = std::exp(-gs);
+		c2[a] = std::sqrt(b->kT[a] * (-std::expm1(-2.0 * gs)));
+	}
+	return NBCO_OK;
+}
+
 // ---- uniform magnetic field: the matrices of the helix drift (include/nbco.h) ---------------------------------------------------
 namespace {
 
@@ -190,9 +219,23 @@ bool helix3_make(const double *omega3, double s, Helix3 &h)
 
 bool omega3_finite(const double *o) { return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]); }
 
+// the kernel argument of the 3-D bath step: coefficients narrowed to float once, the seed and the tick as two words each
+bool bath3_make(const nbco_bath *b, double s, int half, unsigned long long tick, Bath3 &out)
+{
+	double c1[3], c2[3];
+	if (bath_coeffs_dim(b, s, c1, c2, 3) != NBCO_OK) return false;
+	for (int a = 0; a < 3; ++a) { out.c1[a] = (float)c1[a]; out.c2[a] = (float)c2[a]; }
+	out.key[0] = (uint32_t)b->seed; out.key[1] = (uint32_t)(b->seed >> 32);
+	out.tick[0] = (uint32_t)tick; out.tick[1] = (uint32_t)(tick >> 32);
+	out.half = half;
+	return true;
+}
+
 } // namespace
 
 extern "C" {
+
+int nbco_bath_coeffs(const nbco_bath *b, double s, double *c1, double *c2) { return bath_coeffs_dim(b, s, c1, c2, 3); }
 
 int nbco_helix_matrices(const double *o, double s, double *R, double *A)
 {
@@ -675,8 +718,13 @@ static int integrate_impl(nbco_ctx *c, int scheme, int kind, float *buf, long lo
 // between two force evaluations -- tree order for x and v, elastic term, the two half kicks, the drift and the next build's
 // prologue: four passes over the state -- into one (kd_turnaround); every particle sees the same operations with the same
 // roundings as in `steps` calls of nbco_integrate, and the final state is bit-identical to theirs.  Everything else loops.
+// bath: null, or the Langevin bath of nbco_integrate_steps_t (checked by the caller), step k at tick0 + k: every step is wrapped in the two
+// half bath steps; in the fused run those between two force evaluations are part of the turnaround pass.
+static int integrate_t_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
+                            const double *omega, const nbco_bath *bath, unsigned long long tick);
+
 static int integrate_steps_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt_, double scale_, int elastic,
-                                int steps, const double *omega)
+                                int steps, const double *omega, const nbco_bath *bath = nullptr, unsigned long long tick0 = 0)
 {
 	if (!c || !buf || !param || n <= 0 || steps < 0) return c ? c->fail(NBCO_ERR_ARG, "nbco_integrate_steps: bad arguments") : NBCO_ERR_ARG;
 	const bool fuse = scheme == NBCO_INTEG_LEAPFROG && kind == NBCO_EVAL_FMM_KDTREE && !c->o.unsort && !c->o.track_order && steps >= 2;
@@ -685,7 +733,9 @@ static int integrate_steps_impl(nbco_ctx *c, int scheme, int kind, float *buf, l
 		const int sync = c->o.sync;
 		c->o.sync = 0;
 		int rc = NBCO_OK;
-		for (int s = 0; s < steps && rc == NBCO_OK; ++s) rc = integrate_impl(c, scheme, kind, buf, n, param, dt_, scale_, elastic, omega);
+		for (int s = 0; s < steps && rc == NBCO_OK; ++s)
+			rc = bath ? integrate_t_impl(c, scheme, kind, buf, n, param, dt_, scale_, elastic, omega, bath, tick0 + (unsigned long long)s)
+			          : integrate_impl(c, scheme, kind, buf, n, param, dt_, scale_, elastic, omega);
 		c->o.sync = sync;
 		if (rc != NBCO_OK) return rc;
 		return maybe_sync(c);
@@ -697,8 +747,11 @@ static int integrate_steps_impl(nbco_ctx *c, int scheme, int kind, float *buf, l
 	Helix3 h;
 	if (omega && !helix3_make(omega, (double)dt, h)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_steps_b: Omega dt is not finite");
 	const Helix3 *helix = omega ? &h : nullptr;
+	Bath3 bt;
+	if (bath && !bath3_make(bath, 0.5 * dt_, 0, tick0, bt)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_steps_t: bad bath");
 	{
 		PhaseScope ph(c, NBCO_PH_AXPY);
+		if (bath) NBCO_TRY(launch_bath(c, v, bt, n));   // the opening half of the first step
 		if (helix) NBCO_TRY(launch_kick_drift_b(c, x, v, a, ds, h, n));
 		else NBCO_TRY(launch_kick_drift(c, x, v, a, ds, dtf, n3));
 	}
@@ -711,7 +764,11 @@ static int integrate_steps_impl(nbco_ctx *c, int scheme, int kind, float *buf, l
 	for (int s = 0; s < steps; ++s)
 	{
 		int rc = eval_kind(c, kind, x, a, n, param, &link);
-		if (rc == NBCO_OK && s + 1 < steps) rc = kd_turnaround(c, buf, param, ds, dtf, elastic != 0, n, &link, nullptr, helix);
+		if (rc == NBCO_OK && s + 1 < steps)
+		{
+			if (bath) bath3_make(bath, 0.5 * dt_, 1, tick0 + (unsigned long long)s, bt);
+			rc = kd_turnaround(c, buf, param, ds, dtf, elastic != 0, n, &link, nullptr, helix, bath ? &bt : nullptr);
+		}
 		if (rc != NBCO_OK)
 		{
 			home();
@@ -722,6 +779,13 @@ static int integrate_steps_impl(nbco_ctx *c, int scheme, int kind, float *buf, l
 	home();
 	// tail of the last step, as in nbco_integrate: tree order, then a -= k o x, v += a ds
 	NBCO_TRY(closing_kick(c, link, [&] { return kd_finish_pending_order(c, x, n, &link); }, buf, n, param, ds, elastic != 0));
+	if (bath)
+	{
+		// the closing half of the last step
+		PhaseScope ph(c, NBCO_PH_AXPY);
+		bath3_make(bath, 0.5 * dt_, 1, tick0 + (unsigned long long)(steps - 1), bt);
+		NBCO_TRY(launch_bath(c, v, bt, n));
+	}
 	return maybe_sync(c);
 }
 
@@ -777,6 +841,84 @@ int nbco_integrate_steps_b(nbco_ctx *c, int scheme, int kind, float *buf, long l
 {
 	NBCO_TRY(integrate_b_args(c, "nbco_integrate_steps_b", scheme, kind, buf, n, param, dt, steps, omega3_host));
 	return integrate_steps_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, steps, omega3_host);
+}
+
+// ---- Langevin bath (include/nbco.h) ---------------------------------------------------------------------------------------------
+// O(dt/2, half 0) S(dt) O(dt/2, half 1); the arguments were checked by integrate_t_args
+static int integrate_t_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
+                            const double *omega, const nbco_bath *bath, unsigned long long tick)
+{
+	float *v = buf + 3 * n;
+	Bath3 b;
+	if (!bath3_make(bath, 0.5 * dt, 0, tick, b)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_t: bad bath");
+	{
+		PhaseScope ph(c, NBCO_PH_AXPY);
+		NBCO_TRY(launch_bath(c, v, b, n));
+	}
+	const int sync = c->o.sync;
+	c->o.sync = 0;
+	const int rc = integrate_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega);
+	c->o.sync = sync;
+	if (rc != NBCO_OK) return rc;
+	b.half = 1;
+	{
+		PhaseScope ph(c, NBCO_PH_AXPY);
+		NBCO_TRY(launch_bath(c, v, b, n));
+	}
+	return maybe_sync(c);
+}
+
+int nbco_bath_apply(nbco_ctx *c, float *v, long long n, const nbco_bath *bath, double s, int half, unsigned long long tick)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!v || !bath || n < 0) return c->fail(NBCO_ERR_ARG, "nbco_bath_apply: bad arguments");
+	if (half != 0 && half != 1) return c->fail(NBCO_ERR_ARG, "nbco_bath_apply: half must be 0 or 1");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_bath_apply: n must be below 2^31 (the row is one counter word)");
+	Bath3 b;
+	if (!bath3_make(bath, s, half, tick, b)) return c->fail(NBCO_ERR_ARG, "nbco_bath_apply: gamma, kT and s must be finite and not negative");
+	{
+		PhaseScope ph(c, NBCO_PH_AXPY);
+		NBCO_TRY(launch_bath(c, v, b, n));
+	}
+	return maybe_sync(c);
+}
+
+// what nbco_integrate_t and nbco_integrate_steps_t refuse before any launch.  All gamma = 0: `bath` comes back null; Omega null or 0:
+// `omega` comes back null (the call is its counterpart)
+static int integrate_t_args(nbco_ctx *c, const char *who, int scheme, int kind, const float *buf, long long n, const float *param, double dt, int steps,
+                            const double *&omega, const nbco_bath *&bath)
+{
+	if (!c) return NBCO_ERR_ARG;
+	const std::string w(who);
+	if (!buf || !param || n <= 0 || steps < 0) return c->fail(NBCO_ERR_ARG, w + ": bad arguments");
+	if (!bath) return c->fail(NBCO_ERR_ARG, w + ": bath_host is NULL");
+	if (!bath_valid(bath, 3)) return c->fail(NBCO_ERR_ARG, w + ": gamma and kT must be finite and not negative");
+	if (omega) NBCO_TRY(integrate_b_args(c, who, scheme, kind, buf, n, param, dt, steps, omega));
+	else
+	{
+		if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, w + ": unknown integrator scheme");
+		if (kind < NBCO_EVAL_DIRECT || kind > NBCO_EVAL_FMM_SYMMETRIC) return c->fail(NBCO_ERR_ARG, w + ": unknown evaluator kind");
+		if (kind == NBCO_EVAL_FMM_KDTREE && n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit tree indices");
+	}
+	if (bath_off(bath, 3)) { bath = nullptr; return NBCO_OK; }
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n must be below 2^31 (the row is one counter word)");
+	if (!std::isfinite(dt) || dt < 0.0) return c->fail(NBCO_ERR_ARG, w + ": dt must be finite and not negative with a bath");
+	return NBCO_OK;
+}
+
+int nbco_integrate_t(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
+                     const double *omega3_host, const nbco_bath *bath_host, unsigned long long tick)
+{
+	NBCO_TRY(integrate_t_args(c, "nbco_integrate_t", scheme, kind, buf, n, param, dt, 0, omega3_host, bath_host));
+	if (!bath_host) return integrate_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega3_host);
+	return integrate_t_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega3_host, bath_host, tick);
+}
+
+int nbco_integrate_steps_t(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
+                           int steps, const double *omega3_host, const nbco_bath *bath_host, unsigned long long tick0)
+{
+	NBCO_TRY(integrate_t_args(c, "nbco_integrate_steps_t", scheme, kind, buf, n, param, dt, steps, omega3_host, bath_host));
+	return integrate_steps_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, steps, omega3_host, bath_host, tick0);
 }
 
 // ---- reductions --------------------------------------------------------------------------------

@@ -366,6 +366,13 @@ int launch_finish_kick(nbco_ctx *c, const float *x, const float *v_in, float *v,
 struct Helix3;
 int launch_drift_b(nbco_ctx *c, float *x, float *v, const Helix3 &h, long long n);
 int launch_kick_drift_b(nbco_ctx *c, float *x, float *v, const float *a, float ks, const Helix3 &h, long long n);
+// the Langevin bath step on the velocities (bath.hpp)
+struct Bath3;
+int launch_bath(nbco_ctx *c, float *v, const Bath3 &b, long long n);
+// nbco_api.hip: the bath's checks and coefficients over the first `dim` axes
+bool bath_valid(const nbco_bath *b, int dim);                                               // gamma, kT finite and not negative
+bool bath_off(const nbco_bath *b, int dim);                                                 // every gamma exactly 0
+int bath_coeffs_dim(const nbco_bath *b, double s, double *c1, double *c2, int dim);
 // k_direct.hip
 int launch_direct(nbco_ctx *c, const float *p, float *a, long long n, const float *param, bool kahan);
 // k_reduce.hip
@@ -423,7 +430,7 @@ int dpart_begin(nbco_ctx *c, float *state_local, long long n_global, int world, 
 int dpart_next(nbco_ctx *c, nbco_dist_step *out);
 int kd_finish_pending_order(nbco_ctx *c, float *p, long long n, KdStepLink *link);
 int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds, bool elastic, long long n, KdStepLink *link, const float *root6 = nullptr,
-                  const Helix3 *helix = nullptr);
+                  const Helix3 *helix = nullptr, const Bath3 *bath_close = nullptr);
 int kd_dist_turnaround(nbco_ctx *c, float *buf_local, long long n_local, const float *param, float ks, float ds, bool elastic);
 int kd_dist_let_select(nbco_ctx *c, const void *csz_all, long long *counts);
 int kd_dist_let_pack(nbco_ctx *c, const long long *counts_all, void *pos_send, void *mpole_send);

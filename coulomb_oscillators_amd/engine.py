@@ -93,6 +93,13 @@ class Aperture(C.Structure):
 
 
 AP_ELLIPSOID, AP_BOX = 0, 1   # NBCO_AP_*
+
+
+class Bath(C.Structure):
+    """nbco_bath: per-axis friction rates and temperatures of the Langevin bath and the 64-bit seed of its noise"""
+    _fields_ = [("gamma", C.c_double * 3), ("kT", C.c_double * 3), ("seed", C.c_ulonglong)]
+
+
 ERR_CAPACITY = 3              # NBCO_ERR_CAPACITY
 
 COLL_DONE, COLL_ALLREDUCE_MIN_I32, COLL_ALLREDUCE_SUM_I32, COLL_ALLGATHER, COLL_ALLTOALL = range(5)
@@ -123,7 +130,7 @@ def _load():
         raise EngineError("libnbco_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                           "there is no CPU fallback")
     L = C.CDLL(_LIB)
-    P, LL, I, F, D = C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_double
+    P, LL, I, F, D, ULL = C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_ulonglong
     sig = {
         "nbco_opts_default": [C.POINTER(Opts)],
         "nbco_create": [C.POINTER(P), C.POINTER(Opts)],
@@ -155,6 +162,13 @@ def _load():
         "nbco_2d_drift_b": [P, P, P, LL, D, D],
         "nbco_2d_integrate_b": [P, I, I, P, LL, P, D, D, I, D],
         "nbco_2d_integrate_steps_b": [P, I, I, P, LL, P, D, D, I, I, D],
+        "nbco_bath_coeffs": [C.POINTER(Bath), D, C.POINTER(D), C.POINTER(D)],
+        "nbco_bath_apply": [P, P, LL, C.POINTER(Bath), D, I, ULL],
+        "nbco_integrate_t": [P, I, I, P, LL, P, D, D, I, C.POINTER(D), C.POINTER(Bath), ULL],
+        "nbco_integrate_steps_t": [P, I, I, P, LL, P, D, D, I, I, C.POINTER(D), C.POINTER(Bath), ULL],
+        "nbco_2d_bath_apply": [P, P, LL, C.POINTER(Bath), D, I, ULL],
+        "nbco_2d_integrate_t": [P, I, I, P, LL, P, D, D, I, D, C.POINTER(Bath), ULL],
+        "nbco_2d_integrate_steps_t": [P, I, I, P, LL, P, D, D, I, I, D, C.POINTER(Bath), ULL],
         "nbco_minmax": [P, P, LL, P],
         "nbco_mean_relerr": [P, P, P, LL, C.POINTER(F)],
         "nbco_pow_sum": [P, P, I, LL, C.POINTER(D)],
@@ -292,6 +306,25 @@ def helix_matrices_2d(omega, s):
     if rc != 0:
         raise EngineError("nbco_2d_helix_matrices failed with status %d" % rc, status=rc)
     return np.array(R[:], dtype=np.float64).reshape(2, 2), np.array(A[:], dtype=np.float64).reshape(2, 2)
+
+
+def _bath(gamma, kT, seed):
+    """nbco_bath from per-axis rates and temperatures (two or three values each; a scalar serves every axis) and a 64-bit seed"""
+    def three(q):
+        q = [float(q)] * 3 if not hasattr(q, "__len__") else [float(t) for t in q]
+        return q + [0.0] * (3 - len(q))
+    return Bath((C.c_double * 3)(*three(gamma)), (C.c_double * 3)(*three(kT)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def bath_coeffs(gamma, kT, s):
+    """(c1, c2), float64[3]: the coefficients of the exact Langevin bath step over s, v' = c1 v + c2 xi with c1 = exp(-gamma s) and
+    c2 = sqrt(kT (1 - exp(-2 gamma s))) (nbco_bath_coeffs, include/nbco.h).  Host only, needs no GPU; the one place they are formed."""
+    import numpy as np
+    c1, c2 = (C.c_double * 3)(), (C.c_double * 3)()
+    rc = _load().nbco_bath_coeffs(C.byref(_bath(gamma, kT, 0)), float(s), c1, c2)
+    if rc != 0:
+        raise EngineError("nbco_bath_coeffs failed with status %d" % rc, status=rc)
+    return np.array(c1[:], dtype=np.float64), np.array(c2[:], dtype=np.float64)
 
 
 def default_opts(**kw):
@@ -437,6 +470,37 @@ class Engine:
 
     def integrate_steps_b_2d(self, scheme, kind, buf, n, param, dt, steps, omega, scale=1.0, elastic=True):
         self._chk(self.lib.nbco_2d_integrate_steps_b(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps), float(omega)))
+
+    # ---- Langevin bath: the exact friction-and-noise step of the velocities (include/nbco.h) ------------------------------------
+    bath_coeffs = staticmethod(bath_coeffs)
+
+    def bath_apply(self, v, n, gamma, kT, s, half, tick, seed=REF_SEED):
+        """O(s) alone on the float32 velocities v of n particles (nbco_bath_apply): v' = c1 v + c2 xi per row and axis, the noise keyed by
+        (seed, tick, half, row, axis); gamma and kT per axis"""
+        self._chk(self.lib.nbco_bath_apply(self.ctx, _ptr(v), n, C.byref(_bath(gamma, kT, seed)), float(s), int(half), int(tick)))
+
+    def integrate_t(self, scheme, kind, buf, n, param, dt, gamma, kT, tick, seed=REF_SEED, omega=None, scale=1.0, elastic=True):
+        """integrate() or integrate_b() (omega given) wrapped in the two half bath steps O(dt/2) (nbco_integrate_t); every gamma 0 is the
+        counterpart itself"""
+        self._chk(self.lib.nbco_integrate_t(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), _omega3(omega),
+                                            C.byref(_bath(gamma, kT, seed)), int(tick)))
+
+    def integrate_steps_t(self, scheme, kind, buf, n, param, dt, steps, gamma, kT, tick0, seed=REF_SEED, omega=None, scale=1.0, elastic=True):
+        """`steps` steps in one call, step k at tick0 + k (nbco_integrate_steps_t): same final state as `steps` calls of integrate_t()"""
+        self._chk(self.lib.nbco_integrate_steps_t(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps), _omega3(omega),
+                                                  C.byref(_bath(gamma, kT, seed)), int(tick0)))
+
+    def bath_apply_2d(self, v, n, gamma, kT, s, half, tick, seed=REF_SEED):
+        """the 2-D form: float64 xy pairs, gamma and kT two values each (nbco_2d_bath_apply)"""
+        self._chk(self.lib.nbco_2d_bath_apply(self.ctx, _ptr(v), n, C.byref(_bath(gamma, kT, seed)), float(s), int(half), int(tick)))
+
+    def integrate_t_2d(self, scheme, kind, buf, n, param, dt, gamma, kT, tick, seed=REF_SEED, omega=0.0, scale=1.0, elastic=True):
+        self._chk(self.lib.nbco_2d_integrate_t(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), float(omega),
+                                               C.byref(_bath(gamma, kT, seed)), int(tick)))
+
+    def integrate_steps_t_2d(self, scheme, kind, buf, n, param, dt, steps, gamma, kT, tick0, seed=REF_SEED, omega=0.0, scale=1.0, elastic=True):
+        self._chk(self.lib.nbco_2d_integrate_steps_t(self.ctx, scheme, kind, _ptr(buf), n, _ptr(param), dt, scale, int(elastic), int(steps), float(omega),
+                                                     C.byref(_bath(gamma, kT, seed)), int(tick0)))
 
     # ---- 2-D fp64 evaluators (main.cu): float64 tensors, xy pairs, param = {xi/N, 0, kx, ky} -------------------------------
     def direct_2d(self, p, a, n, param=None):

@@ -79,6 +79,10 @@ const char *kHelp =
     "  -B <w>            uniform magnetic field out of the plane, Omega = (q/m) B in radians per unit of -ds: the force\n"
     "                    (vy, -vx) w, integrated exactly -- the drift of every scheme becomes a rotation\n"
     "                    (nbco_2d_integrate_b); 0 is the run without the flag; no effect with -test\n"
+    "  -bath <gx> <gy> <Tx> <Ty>   Langevin bath: friction rates per unit of -ds and temperatures (units of v^2) per\n"
+    "                    axis; every step is wrapped in two exact half steps of friction and noise\n"
+    "                    (nbco_2d_integrate_t), the iteration number is the tick; rates 0 0 are the run without the\n"
+    "                    flag; -bath-seed <u64> seeds the noise; works with -B; no effect with -test\n"
     "  -ga               Gaussian initial state instead of KV\n"
     "  -xi <v>           perveance\n"
     "  -omega0 <x> <y>   trap phase advances\n"
@@ -106,6 +110,7 @@ int main(const int argc, const char **argv)
 	int nBodies = 30001, nIters = 30001, nSteps = 200, integ = NBCO_INTEG_LEAPFROG;
 	int fmm_order = 5, tree_radius = 1;
 	double dt = 5.e-4, EPS2 = 1e-18, dens_inhom = 1, omega_b = 0;
+	nbco_bath bath{{0, 0, 0}, {0, 0, 0}, NBCO_REF_SEED};
 	std::string strout("out"), strin, strprobes;
 	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false, moments = false;
 	bool aperture = false;
@@ -209,6 +214,26 @@ int main(const int argc, const char **argv)
 			if (need(i, 1, a)) return missing();
 			omega_b = std::atof(argv[i + 1]);
 			if (!std::isfinite(omega_b)) return invalid(argv[i + 1], " (should be finite)");
+			++i;
+		}
+		else if (is(a, "bath"))
+		{
+			if (need(i, 4, a)) return missing();
+			for (int k = 0; k < 2; ++k)
+			{
+				bath.gamma[k] = std::atof(argv[i + 1 + k]);
+				bath.kT[k] = std::atof(argv[i + 3 + k]);
+				if (!std::isfinite(bath.gamma[k]) || bath.gamma[k] < 0) return invalid(argv[i + 1 + k], " (rates should be finite and not negative)");
+				if (!std::isfinite(bath.kT[k]) || bath.kT[k] < 0) return invalid(argv[i + 3 + k], " (temperatures should be finite and not negative)");
+			}
+			i += 4;
+		}
+		else if (is(a, "bath-seed"))
+		{
+			if (need(i, 1, a)) return missing();
+			char *end = nullptr;
+			bath.seed = std::strtoull(argv[i + 1], &end, 10);
+			if (end == argv[i + 1] || *end != 0 || argv[i + 1][0] == '-') return invalid(argv[i + 1], " (should be an unsigned 64-bit integer)");
 			++i;
 		}
 		else if (is(a, "ncoll")) coll = false;
@@ -435,7 +460,7 @@ int main(const int argc, const char **argv)
 	if (!lib_ok(nbco_2d_force(ctx, NBCO_2D_EVAL_FMM, d_buf, n, d_par, 1))) return finish(-1);
 	for (int iter = 0; iter < nIters; ++iter)
 	{
-		if (!lib_ok(nbco_2d_integrate_b(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1, omega_b))) return finish(-1);
+		if (!lib_ok(nbco_2d_integrate_t(ctx, integ, NBCO_2D_EVAL_FMM, d_buf, n, d_par, dt, 1.0, 1, omega_b, &bath, (unsigned long long)iter))) return finish(-1);
 		if (iter % nSteps == 0)
 		{
 			std::cout << iter << ' ' << std::flush;

@@ -97,6 +97,12 @@ const char *kHelp =
     "  -B <wx> <wy> <wz> Uniform magnetic field Omega = (q/m) B in radians per unit of -ds: the force v x Omega, integrated exactly -- the\n"
     "                    drift of every scheme becomes the motion along a helix (nbco_integrate_steps_b; with -cpu the same matrices and\n"
     "                    arithmetic on the host).  0 0 0 is the run without the flag.  No effect with -test, -test2 or -accuracy.\n"
+    "  -bath <gx> <gy> <gz> <Tx> <Ty> <Tz>   Langevin bath: friction rates per unit of -ds and temperatures (units of v^2) per axis; every step is\n"
+    "                    wrapped in two exact half steps v <- c1 v + c2 xi of friction and noise (nbco_integrate_steps_t; with -cpu the same\n"
+    "                    arithmetic and noise on the host).  A rate of 0 leaves its axis alone, a temperature of 0 is pure cooling; all rates 0\n"
+    "                    is the run without the flag.  The step number of an iteration is its tick.  Works with -B, -aperture and -cpu; no\n"
+    "                    effect with -test, -test2 or -accuracy.\n"
+    "  -bath-seed <u64>  Seed of the bath's noise (default 5351550349027530206, the seed of the reference's initial state).\n"
     "  -cpu              Run the simulation on the host: compensated direct sum O(N^2) over C++20 threads (small N; the test and\n"
     "                    tuning modes need the GPU).  -cpu-threads <n> sets the number of threads (default 8); -cacheline <n> is\n"
     "                    accepted and ignored.\n";
@@ -359,7 +365,7 @@ struct Session
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
 	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture, const SlicesOpt &slices,
-	             const double *omega)
+	             const double *omega, const nbco_bath *bath)
 	{
 		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
@@ -404,7 +410,8 @@ struct Session
 				if (iter == kSteadyFrom) { check(nbco_sync(ctx()), "sync"); steady_t0 = std::chrono::steady_clock::now(); steady_first = iter; }
 				else if (iter < kSteadyFrom) run = std::min(run, kSteadyFrom - iter);   // (K steps in one call == the same steps in two calls, bit for bit)
 			}
-			if (omega) check(nbco_integrate_steps_b(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega), "integrate_b");
+			if (bath) check(nbco_integrate_steps_t(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega, bath, (unsigned long long)iter), "integrate_t");
+			else if (omega) check(nbco_integrate_steps_b(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega), "integrate_b");
 			else check(nbco_integrate_steps(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run), "integrate");
 			iter += run;
 			if ((iter - 1) % nSteps != 0) continue;
@@ -556,6 +563,8 @@ int main(int argc, const char **argv)
 	SlicesOpt slices;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false, bfield = false;
 	double omega_b[3]{0, 0, 0};
+	nbco_bath bath{{0, 0, 0}, {0, 0, 0}, NBCO_REF_SEED};
+	bool bath_on = false;
 	SCAL accuracy = (SCAL)0.001;
 	int scheme = NBCO_INTEG_LEAPFROG;   // main3.cu:238
 	SCAL xi = (SCAL)2.e-6;
@@ -738,6 +747,32 @@ int main(int argc, const char **argv)
 			bfield = omega_b[0] != 0 || omega_b[1] != 0 || omega_b[2] != 0;   // (0 0 0 IS the run without the flag, on the host path too)
 			i += 3;
 		}
+		else if (a == "-bath")
+		{
+			if (!need(i, 6, "-bath")) return -1;
+			bool ok = true;
+			for (int k = 0; k < 3; ++k)
+			{
+				bath.gamma[k] = atof(argv[i + 1 + k]);
+				bath.kT[k] = atof(argv[i + 4 + k]);
+				ok = ok && std::isfinite(bath.gamma[k]) && bath.gamma[k] >= 0 && std::isfinite(bath.kT[k]) && bath.kT[k] >= 0;
+			}
+			if (!ok)
+			{
+				std::cerr << "Error: invalid argument(s) to '-bath' (three rates and three temperatures, finite and not negative)\n";
+				return -1;
+			}
+			bath_on = bath.gamma[0] != 0 || bath.gamma[1] != 0 || bath.gamma[2] != 0;   // (all rates 0 IS the run without the flag, on the host path too)
+			i += 6;
+		}
+		else if (a == "-bath-seed")
+		{
+			if (!need(i, 1, "-bath-seed")) return -1;
+			char *end = nullptr;
+			bath.seed = strtoull(argv[i + 1], &end, 10);
+			if (end == argv[i + 1] || *end != 0 || argv[i + 1][0] == '-') { std::cerr << "Error: invalid argument to '-bath-seed': " << argv[i + 1] << " (an unsigned 64-bit integer)\n"; return -1; }
+			i += 1;
+		}
 		else if (a == "-cpu-threads")
 		{
 			if (!need(i, 1, "-cpu-threads")) return -1;
@@ -852,7 +887,7 @@ int main(int argc, const char **argv)
 		std::vector<nbco_moments> slice_recs;
 		for (int iter = 0; iter < nIters; ++iter)
 		{
-			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr);
+			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr, bath_on ? &bath : nullptr, (unsigned long long)iter);
 			if (iter % nSteps != 0) continue;
 			std::cout << iter << ' ' << std::flush;
 			if (aperture.on)
@@ -922,7 +957,8 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr);
+		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
+		                     bath_on && !b_accuracy ? &bath : nullptr);
 	}
 	return rc;
 }

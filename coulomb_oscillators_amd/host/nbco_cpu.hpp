@@ -9,6 +9,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <thread>
 #include <vector>
 #include "../../include/nbco.h"
@@ -282,10 +283,66 @@ inline void drift_b(V3 *x, V3 *v, const double *omega, double s, int n)
 	});
 }
 
+// The Langevin bath of `nbco3 -cpu -bath` (include/nbco.h, nbco_bath_apply), the device's rule restated: Philox4x32-10 over
+// key = the seed's two words and counter = (row, axis + 4 half, the tick's two words), the four words summed as an integer, centred and
+// scaled by sqrt(3) 2^-32 in double, narrowed to float; v' = (c1 v) + (c2 xi) with the coefficients of nbco_bath_coeffs narrowed to float
+// and each product and the sum rounded once (the program is compiled with -ffp-contract=off).  An axis with c1 = 1 and c2 = 0 is left alone.
+inline void philox4x32_10(const uint32_t (&ctr)[4], const uint32_t (&key)[2], uint32_t (&out)[4])
+{
+	uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+	for (int r = 0; r < 10; ++r)
+	{
+		const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+		const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+		c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+		k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+	}
+	out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+inline double bath_xi(unsigned long long seed, unsigned long long tick, int half, uint32_t row, int axis)
+{
+	const uint32_t ctr[4]{row, (uint32_t)(axis + 4 * half), (uint32_t)tick, (uint32_t)(tick >> 32)}, key[2]{(uint32_t)seed, (uint32_t)(seed >> 32)};
+	uint32_t w[4];
+	philox4x32_10(ctr, key, w);
+	const long long S = (long long)w[0] + (long long)w[1] + (long long)w[2] + (long long)w[3];
+	return (double)(S - 0x1FFFFFFFELL) * 0x1.bb67ae8584caap-32;
+}
+
+inline void bath_apply(V3 *v, int n, const nbco_bath &bath, double s, int half, unsigned long long tick)
+{
+	double c1d[3], c2d[3];
+	if (nbco_bath_coeffs(&bath, s, c1d, c2d) != NBCO_OK) return;
+	const float c1[3]{(float)c1d[0], (float)c1d[1], (float)c1d[2]}, c2[3]{(float)c2d[0], (float)c2d[1], (float)c2d[2]};
+	const unsigned long long seed = bath.seed;
+	for_ranges(n, [=](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			float *q = &v[i].x;
+			for (int a = 0; a < 3; ++a)
+			{
+				if (c1[a] == 1.f && c2[a] == 0.f) continue;
+				const float xi = (float)bath_xi(seed, tick, half, (uint32_t)i, a);
+				const float p = c1[a] * q[a], r = c2[a] * xi;
+				q[a] = p + r;
+			}
+		}
+	});
+}
+
 // one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call); omega: null, or
-// the uniform magnetic field whose helix drift replaces x += v c
+// the uniform magnetic field whose helix drift replaces x += v c; bath: null, or the Langevin bath whose two half steps O(dt/2) wrap the
+// scheme, at the step number `tick`
 enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
-inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega = nullptr)
+inline void integrate_scheme(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega);
+inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega = nullptr, const nbco_bath *bath = nullptr,
+                      unsigned long long tick = 0)
+{
+	if (bath) bath_apply(buf + n, n, *bath, 0.5 * (double)dt, 0, tick);
+	integrate_scheme(s, buf, n, par, eps2, dt, omega);
+	if (bath) bath_apply(buf + n, n, *bath, 0.5 * (double)dt, 1, tick);
+}
+inline void integrate_scheme(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega)
 {
 	V3 *x = buf, *v = buf + n, *a = buf + 2 * (size_t)n;
 	auto K = [&](long double c) { step(v, a, (float)c, n); };

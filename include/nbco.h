@@ -192,6 +192,60 @@ int nbco_integrate_b(nbco_ctx *c, int scheme, int kind, float *buf, long long n,
 int nbco_integrate_steps_b(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
                            double dt, double scale, int elastic, int steps, const double *omega3_host);
 
+/* ---- Langevin bath: the exact friction-and-noise step ------------------------------------------------------------------------
+ * Friction -gamma v plus noise at the temperature kT (laser or buffer-gas cooling) depends on v like the magnetic force, and no kick
+ * expresses it.  The flow of dv = -gamma v dt + sqrt(2 gamma kT) dW alone, the Ornstein-Uhlenbeck process, is known in closed form,
+ * and one step of any of the five schemes S(dt) becomes
+ *
+ *   O(dt/2, half = 0) . S(dt) . O(dt/2, half = 1)        (the form of Bussi and Parrinello, Phys. Rev. E 75, 056707)
+ *
+ * K, D (straight or helix) and F are as they are.  gamma[a] >= 0 is the friction rate of axis a per unit of dt, kT[a] >= 0 the bath
+ * temperature of axis a in units of v^2 (mass 1).  The values are per axis on purpose: Doppler cooling acts along the beam; gamma[a] = 0
+ * leaves axis a alone, kT[a] = 0 is pure cooling.  The 2-D calls read gamma[0..1] and kT[0..1] only.  HOST struct. */
+typedef struct nbco_bath { double gamma[3]; double kT[3]; unsigned long long seed; } nbco_bath;
+/* The coefficients of O(s), formed in double: c1 = exp(-gamma s), c2 = sqrt(kT * (-expm1(-2 gamma s))), so that a velocity of variance
+ * sigma^2 leaves with c1^2 sigma^2 + c2^2 and kT is the fixed point at any s: the O step is exact, whatever gamma dt.  gamma = 0 gives
+ * c1 = 1 and c2 = 0 exactly.  Host only, no GPU needed, and the one place they are formed: the device calls below, `nbco3 -cpu` and the
+ * tests take them from it (the 3-D calls narrow them to float once).  NBCO_ERR_ARG: a null pointer, a non-finite or negative gamma, kT
+ * or s. */
+int nbco_bath_coeffs(const nbco_bath *bath, double s, double c1[3], double c2[3]);
+/* O(s) alone on the velocities of n particles (xyz triplets, fp32), on the context's stream; returns as the evaluators do.  Per particle
+ * row r and axis a, the whole numerical contract:
+ *
+ *   v' = (c1[a] * v) + (c2[a] * xi)      each product and the sum rounded once, in this order, no fused multiply-add
+ *
+ * so that numpy float32 arithmetic reproduces it bit for bit.  An axis whose narrowed coefficients are c1 = 1 and c2 = 0 (gamma = 0) is
+ * not touched: its bytes stay whatever they are, and no noise is drawn for it.
+ * The noise xi is counter-based and stateless, from Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85; ten rounds): key = (seed low word, seed high word), counter = (r, a + 4 half, tick low word, tick high word), with r the
+ * particle's row in the state at the moment O is applied (after an evaluation's re-ordering) and tick the 64-bit step number.  The four
+ * output words are summed as an integer, S = w0 + w1 + w2 + w3, and
+ *   xi = (double) (int64) (S - 0x1FFFFFFFE) * 0x1.bb67ae8584caap-32      (sqrt(3) 2^-32; one rounding; in 3-D then narrowed to float)
+ * That is a centred sum of four uniforms: mean 0, variance 1, kurtosis 2.7, and NOT a Gaussian: |xi| <= 3.47, there is no tail beyond.
+ * Only the first two moments enter the stationary variance, so <v^2> -> kT holds exactly; a run that depends on rare large kicks
+ * (escape over a barrier many kT high) needs another noise.
+ * Consequences: a row's new v depends on (seed, tick, half, row, its old v) and on nothing else -- not on n, the launch shape or the
+ * other rows; a second call with the same arguments draws the same noise; a run is reproducible and restartable from (state, tick).
+ * An aperture that compacts the rows re-keys the noise, which is harmless: any independent stream serves.
+ * The call does not move positions: it leaves the "moved since the last kd-tree evaluation" mark, the trees, the schedule and the
+ * diagnostics' validity alone (nbco_kd_probe is still accepted after it).  Refused before any launch: NBCO_ERR_ARG for a null pointer,
+ * n < 0, half not 0 or 1, a non-finite or negative gamma, kT or s; NBCO_ERR_UNSUPPORTED for n >= 2^31 (the row is one counter word). */
+int nbco_bath_apply(nbco_ctx *c, float *v, long long n, const nbco_bath *bath_host, double s, int half, unsigned long long tick);
+/* nbco_integrate(_b) and nbco_integrate_steps(_b) wrapped in the two half bath steps; omega3_host NULL: no magnetic field.  Step k of
+ * nbco_integrate_steps_t uses tick0 + k.  Every gamma exactly 0 (any kT): the call IS nbco_integrate(_steps)(_b), byte for byte.
+ * nbco_integrate_t is bit for bit the sequence nbco_bath_apply(dt/2, 0, tick), nbco_integrate(_b), nbco_bath_apply(dt/2, 1, tick), and
+ * nbco_integrate_steps_t is bit for bit `steps` calls of nbco_integrate_t: leapfrog over the kd-tree evaluator fuses as in
+ * nbco_integrate_steps, and the closing half of step k and the opening half of step k + 1 are part of the one pass between two force
+ * evaluations (on the tree-order row); the opening half of the first step and the closing half of the last are passes of their own.
+ * Refused before any launch, the state untouched: NBCO_ERR_ARG for a null bath_host, a non-finite or negative gamma or kT, a negative or
+ * non-finite dt (with a bath), and everything the counterparts refuse; NBCO_ERR_UNSUPPORTED for n >= 2^31.
+ * Not offered: the nbco_dist_* path, per-particle or position-dependent rates, a conserved "effective energy" bookkeeping. */
+int nbco_integrate_t(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
+                     double dt, double scale, int elastic, const double *omega3_host, const nbco_bath *bath_host, unsigned long long tick);
+int nbco_integrate_steps_t(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
+                           double dt, double scale, int elastic, int steps, const double *omega3_host, const nbco_bath *bath_host,
+                           unsigned long long tick0);
+
 /* ---- reductions (reductions.cuh) -------------------------------------------------------------- */
 int nbco_minmax(nbco_ctx *c, const float *p, long long n, float *minmax6_dev);           /* reductions.cuh:67 minmaxReduce2 */
 int nbco_mean_relerr(nbco_ctx *c, const float *x, const float *ref, long long n, float *out_host);  /* reductions.cuh:99 relerrReduce2 (intent) */
@@ -546,6 +600,15 @@ int nbco_2d_integrate_b(nbco_ctx *c, int scheme, int kind, double *buf, long lon
                         int elastic, double omega);
 int nbco_2d_integrate_steps_b(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt,
                               double scale, int elastic, int steps, double omega);
+/* The Langevin bath in 2-D (see nbco_bath_apply): fp64 state of xy pairs, gamma[0..1] and kT[0..1] of the bath, the coefficients of
+ * nbco_bath_coeffs in double, v' = (c1[a] * v) + (c2[a] * xi) with each product and the sum rounded once and xi in double (not narrowed),
+ * the same noise rule with a = 0, 1; numpy float64 arithmetic reproduces it bit for bit.  The integrators are nbco_2d_integrate(_steps)(_b)
+ * wrapped in the two half steps (omega = 0: no field); gamma[0] = gamma[1] = 0 exactly: the call is its counterpart.  Refusals as in 3-D. */
+int nbco_2d_bath_apply(nbco_ctx *c, double *v, long long n, const nbco_bath *bath_host, double s, int half, unsigned long long tick);
+int nbco_2d_integrate_t(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt, double scale,
+                        int elastic, double omega, const nbco_bath *bath_host, unsigned long long tick);
+int nbco_2d_integrate_steps_t(nbco_ctx *c, int scheme, int kind, double *buf, long long n, const double *param, double dt,
+                              double scale, int elastic, int steps, double omega, const nbco_bath *bath_host, unsigned long long tick0);
 /* reductions.cuh:99 relerrReduce2: mean over particles of sqrt(|x_i - ref_i|^2 / (|ref_i|^2 + 1e-18)) (rel_diff1, :37-42;
  * main.cu:172 test_accuracy); syncs */
 int nbco_2d_mean_relerr(nbco_ctx *c, const double *x, const double *ref, long long n, double *out_host);
