@@ -1,5 +1,5 @@
 // dispatch.hpp -- the switches that turn a run-time choice into a template argument: the expansion order, the element type of the
-// far-field tuples, the output set of a probe call.  A launch function calls them around its hipLaunchKernelGGL: the only place
+// far-field tuples, the output set of a probe call, the variant of the pass between two leapfrog steps.  A launch function calls them around its hipLaunchKernelGGL: the only place
 // where that kernel's variant is chosen.  Nothing here needs rocPRIM, so the kernel translation units include it directly.
 #pragma once
 #include "nbco_internal.hpp"
@@ -40,4 +40,28 @@ static void with_outputs(const double *a, const double *psi, F &&f)
 	if (a && psi) f(std::true_type{}, std::true_type{});
 	else if (a) f(std::true_type{}, std::false_type{});
 	else f(std::false_type{}, std::true_type{});
+}
+
+// f(std::bool_constant<ON>) for a run-time flag
+template <class F>
+static void with_flag(bool on, F &&f)
+{
+	if (on) f(std::true_type{});
+	else f(std::false_type{});
+}
+
+// f(drift) for the drift of a leapfrog step: the matrices of the helix drift (Helix3) where a magnetic field is given, the step length (float) otherwise
+template <class H, class F>
+static void with_drift(float ds, const H *helix, F &&f)
+{
+	if (helix) f(*helix);
+	else f(ds);
+}
+
+// f(bath...) with the pack empty (no bath: the kernel has no such argument) or the one Bath3
+template <class B, class F>
+static void with_bath(const B *bath, F &&f)
+{
+	if (bath) f(*bath);
+	else f();
 }

@@ -1,7 +1,14 @@
 // integ_compose.hpp -- the five symplectic compositions of the reference (integrator.cuh:32-167), once for the 3-D and the 2-D
-// library: which kick, drift and force evaluation follow each other, and with which coefficients.
+// library and the host programs' CPU path: which kick, drift and force evaluation follow each other, and with which coefficients.
+// Needs the ABI header alone, so that a host compiler without HIP can include it.
 #pragma once
-#include "nbco_internal.hpp"
+#include "../../include/nbco.h"
+
+#define INTEG_TRY(call)                  \
+	do {                                 \
+		int rc_ = (call);                \
+		if (rc_ != NBCO_OK) return rc_;  \
+	} while (0)
 
 // One step of `scheme` over K(s): v += a s, D(s): x += v s and F(): a = f(x), each returning a status; the first that fails ends the
 // step.  The coefficients are formed in long double and handed to K and D as such: narrowing them to the state's type is theirs, as
@@ -14,36 +21,38 @@ static int integ_compose(int scheme, long double dt, long double scale, Kick &&K
 	switch (scheme)
 	{
 	case NBCO_INTEG_EULER:        // integrator.cuh:32
-		NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt)); NBCO_TRY(F());
+		INTEG_TRY(K(dt * scale)); INTEG_TRY(D(dt)); INTEG_TRY(F());
 		return NBCO_OK;
 	case NBCO_INTEG_PRE_EULER:    // :50
-		NBCO_TRY(F()); NBCO_TRY(K(dt * scale)); NBCO_TRY(D(dt));
+		INTEG_TRY(F()); INTEG_TRY(K(dt * scale)); INTEG_TRY(D(dt));
 		return NBCO_OK;
 	case NBCO_INTEG_LEAPFROG:     // :68
 	{
 		const long double ds = dt * scale * 0.5L;
-		NBCO_TRY(K(ds)); NBCO_TRY(D(dt)); NBCO_TRY(F()); NBCO_TRY(K(ds));
+		INTEG_TRY(K(ds)); INTEG_TRY(D(dt)); INTEG_TRY(F()); INTEG_TRY(K(ds));
 		return NBCO_OK;
 	}
 	case NBCO_INTEG_FORESTRUTH:   // :100
 	{
 		const long double ds = dt * scale;
-		NBCO_TRY(D(dt * th / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * th))); NBCO_TRY(D(dt * (1 - th) / 2)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * th)); NBCO_TRY(D(dt * th / 2));
+		INTEG_TRY(D(dt * th / 2)); INTEG_TRY(F());
+		INTEG_TRY(K(ds * th)); INTEG_TRY(D(dt * (1 - th) / 2)); INTEG_TRY(F());
+		INTEG_TRY(K(ds * (1 - 2 * th))); INTEG_TRY(D(dt * (1 - th) / 2)); INTEG_TRY(F());
+		INTEG_TRY(K(ds * th)); INTEG_TRY(D(dt * th / 2));
 		return NBCO_OK;
 	}
 	case NBCO_INTEG_PEFRL:        // :134
 	{
 		const long double ds = dt * scale;
-		NBCO_TRY(D(dt * xi)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * (1 - 2 * (ch + xi)))); NBCO_TRY(F());
-		NBCO_TRY(K(ds * la)); NBCO_TRY(D(dt * ch)); NBCO_TRY(F());
-		NBCO_TRY(K(ds * (1 - 2 * la) / 2)); NBCO_TRY(D(dt * xi));
+		INTEG_TRY(D(dt * xi)); INTEG_TRY(F());
+		INTEG_TRY(K(ds * (1 - 2 * la) / 2)); INTEG_TRY(D(dt * ch)); INTEG_TRY(F());
+		INTEG_TRY(K(ds * la)); INTEG_TRY(D(dt * (1 - 2 * (ch + xi)))); INTEG_TRY(F());
+		INTEG_TRY(K(ds * la)); INTEG_TRY(D(dt * ch)); INTEG_TRY(F());
+		INTEG_TRY(K(ds * (1 - 2 * la) / 2)); INTEG_TRY(D(dt * xi));
 		return NBCO_OK;
 	}
 	default: return NBCO_ERR_ARG;
 	}
 }
+
+#undef INTEG_TRY

@@ -6,7 +6,6 @@
 #include "nbco_internal.hpp"
 #include "helix.hpp"
 #include "bath.hpp"
-#include <type_traits>
 
 namespace {
 
@@ -109,43 +108,32 @@ __global__ __launch_bounds__(kBlock) void pack4_kernel(float4 *__restrict__ dst,
 		dst[i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0.f);
 }
 
-// fused K(ks) D(ds): v += a*ks; x += v*ds  (the first two step() calls of leapfrog, integrator.cuh:85-89).  Drift = float: the
-// straight drift over the flat view of n3 floats, as ever.  Drift = Helix3: the drift in a uniform magnetic field (helix.hpp), one
-// whole particle per lane -- the tail and the unaligned case of launch_kick_drift_b.
-template <class Drift>
+// fused K(ks) D(ds): v += a*ks; x += v*ds over the flat view of n3 floats (the first two step() calls of leapfrog, integrator.cuh:85-89)
 __global__ __launch_bounds__(kBlock) void kick_drift_kernel(float *__restrict__ x, float *__restrict__ v, const float *__restrict__ a,
-                                                            float ks, Drift ds, long long n3)
+                                                            float ks, float ds, long long n3)
 {
-	if constexpr (std::is_same<Drift, float>::value)
+	for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n3; i += (long long)gridDim.x * kBlock)
 	{
-		for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n3; i += (long long)gridDim.x * kBlock)
-		{
-			float vi = fmaf(ks, a[i], v[i]);
-			v[i] = vi;
-			x[i] = fmaf(ds, vi, x[i]);
-		}
-	}
-	else
-	{
-		const long long n = n3 / 3;
-		for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
-		{
-			float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]}, vi[3];
-#pragma unroll
-			for (int c = 0; c < 3; ++c) vi[c] = fmaf(ks, a[3 * i + c], v[3 * i + c]);
-			helix_drift(ds, xi, vi);
-#pragma unroll
-			for (int c = 0; c < 3; ++c) { x[3 * i + c] = xi[c]; v[3 * i + c] = vi[c]; }
-		}
+		float vi = fmaf(ks, a[i], v[i]);
+		v[i] = vi;
+		x[i] = fmaf(ds, vi, x[i]);
 	}
 }
 
-// the helix drift alone over the particles [beg, n), one per lane (tails and unaligned arrays)
-__global__ __launch_bounds__(kBlock) void drift_b_scalar(float *__restrict__ x, float *__restrict__ v, Helix3 h, long long beg, long long n)
+// the drift in a uniform magnetic field (helix.hpp) over the particles [beg, n), one per lane; KICK: v += a*ks first.  The tail and
+// the unaligned case of helix_vec<KICK>.
+template <bool KICK>
+__global__ __launch_bounds__(kBlock) void helix_scalar(float *__restrict__ x, float *__restrict__ v, const float *__restrict__ a, float ks, Helix3 h,
+                                                       long long beg, long long n)
 {
 	for (long long i = beg + (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
 	{
 		float xi[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]}, vi[3] = {v[3 * i], v[3 * i + 1], v[3 * i + 2]};
+		if constexpr (KICK)
+		{
+#pragma unroll
+			for (int c = 0; c < 3; ++c) vi[c] = fmaf(ks, a[3 * i + c], vi[c]);
+		}
 		helix_drift(h, xi, vi);
 #pragma unroll
 		for (int c = 0; c < 3; ++c) { x[3 * i + c] = xi[c]; v[3 * i + c] = vi[c]; }
@@ -307,7 +295,7 @@ int launch_pack4(nbco_ctx *c, float4 *dst, const float *src3, long long n)
 int launch_kick_drift(nbco_ctx *c, float *x, float *v, const float *a, float ks, float ds, long long n3)
 {
 	if (n3 <= 0) return NBCO_OK;
-	hipLaunchKernelGGL(kick_drift_kernel<float>, dim3(stream_grid(n3)), dim3(kBlock), 0, c->stream, x, v, a, ks, ds, n3);
+	hipLaunchKernelGGL(kick_drift_kernel, dim3(stream_grid(n3)), dim3(kBlock), 0, c->stream, x, v, a, ks, ds, n3);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }
@@ -325,8 +313,8 @@ static int launch_helix(nbco_ctx *c, float *x, float *v, const float *a, float k
 	const long long done = 4 * groups;
 	if (done < n)
 	{
-		if (a) hipLaunchKernelGGL(kick_drift_kernel<Helix3>, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, x + 3 * done, v + 3 * done, a + 3 * done, ks, h, 3 * (n - done));
-		else hipLaunchKernelGGL(drift_b_scalar, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, x, v, h, done, n);
+		if (a) hipLaunchKernelGGL(helix_scalar<true>, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, x, v, a, ks, h, done, n);
+		else hipLaunchKernelGGL(helix_scalar<false>, dim3(stream_grid(n - done)), dim3(kBlock), 0, c->stream, x, v, (const float *)nullptr, 0.f, h, done, n);
 	}
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;

@@ -886,18 +886,16 @@ static int f2d_bath(nbco_ctx *c, double *v, const nbco_bath *bath, double s, int
 static int f2d_eval(nbco_ctx *c, int kind, double *buf, long long n, const double *param, int elastic)
 {
 	double *a = buf + 4 * n;
-	const int save = c->o.sync;
-	c->o.sync = 0;
-	int rc;
-	switch (kind)
 	{
-	case NBCO_2D_EVAL_DIRECT: rc = f2d_direct(c, buf, a, n, param, false); break;
-	case NBCO_2D_EVAL_DIRECT_KAHAN: rc = f2d_direct(c, buf, a, n, param, true); break;
-	case NBCO_2D_EVAL_FMM: rc = f2d_fmm(c, buf, a, n, param); break;
-	default: rc = c->fail(NBCO_ERR_ARG, "nbco_2d: unknown evaluator kind");
+		SyncOff quiet(c);
+		switch (kind)
+		{
+		case NBCO_2D_EVAL_DIRECT: NBCO_TRY(f2d_direct(c, buf, a, n, param, false)); break;
+		case NBCO_2D_EVAL_DIRECT_KAHAN: NBCO_TRY(f2d_direct(c, buf, a, n, param, true)); break;
+		case NBCO_2D_EVAL_FMM: NBCO_TRY(f2d_fmm(c, buf, a, n, param)); break;
+		default: return c->fail(NBCO_ERR_ARG, "nbco_2d: unknown evaluator kind");
+		}
 	}
-	c->o.sync = save;
-	if (rc != NBCO_OK) return rc;
 	if (elastic)   // main.cu:85-89: a -= k o x, k = param + 2
 	{
 		hipLaunchKernelGGL(f2d_elastic_kernel, dim3(grid_blocks(n, kB, kGridCap)), dim3(kB), 0, c->stream, (const double2 *)buf, (double2 *)a, n, param + 2);
@@ -991,13 +989,11 @@ static int f2d_integrate_steps(nbco_ctx *c, const char *who, int scheme, int kin
 {
 	if (!c) return NBCO_ERR_ARG;
 	if (steps < 0) return c->fail(NBCO_ERR_ARG, std::string(who) + ": steps < 0");
-	const int save = c->o.sync;
-	c->o.sync = 0;
-	int rc = NBCO_OK;
-	for (int s = 0; s < steps && rc == NBCO_OK; ++s)
-		rc = f2d_integrate(c, who, scheme, kind, buf, n, param, dt, scale, elastic, omega, bath, tick0 + (unsigned long long)s);
-	c->o.sync = save;
-	if (rc != NBCO_OK) return rc;
+	{
+		SyncOff quiet(c);
+		for (int s = 0; s < steps; ++s)
+			NBCO_TRY(f2d_integrate(c, who, scheme, kind, buf, n, param, dt, scale, elastic, omega, bath, tick0 + (unsigned long long)s));
+	}
 	return f2d_done(c);
 }
 

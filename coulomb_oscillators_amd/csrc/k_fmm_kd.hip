@@ -935,27 +935,17 @@ int kd_turnaround(nbco_ctx *c, float *p, const float *param, float ks, float ds,
 	PhaseScope ph(c, NBCO_PH_AXPY);
 	TreeView tv = view_of(c->kd);
 	hipStream_t st = c->stream;
-#define NBCO_TURN_ARGS(drift) c->pos4.as<float4>(), c->unsort.as<int>(), x, v_in, v_out, (const float *)a, param, ks, drift, elastic ? 1 : 0, n, next_rebuild ? 1 : 0, \
-	c->sel_hist.as<uint32_t>(), words_a, c->sel_nodes.as<uint32_t>(), words_b, c->counters.as<int>() + 110, c->prep_state.as<unsigned>(), tv, root6
-	if (bath_close)
-	{
-		const Bath3 &b = *bath_close;
-		if (helix)
-		{
-			if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, Helix3, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix), b);
-			else hipLaunchKernelGGL((kd_turnaround_kernel<false, Helix3, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix), b);
-		}
-		else if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, float, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds), b);
-		else hipLaunchKernelGGL((kd_turnaround_kernel<false, float, Bath3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds), b);
-	}
-	else if (helix)
-	{
-		if (gather) hipLaunchKernelGGL((kd_turnaround_kernel<true, Helix3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix));
-		else hipLaunchKernelGGL((kd_turnaround_kernel<false, Helix3>), dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(*helix));
-	}
-	else if (gather) hipLaunchKernelGGL(kd_turnaround_kernel<true>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds));
-	else hipLaunchKernelGGL(kd_turnaround_kernel<false>, dim3(kPrepGrid), dim3(kPrepBlock), 0, st, NBCO_TURN_ARGS(ds));
-#undef NBCO_TURN_ARGS
+	// (bath outermost, gather innermost: the order in which the eight instantiations have always been laid out in the code object)
+	with_bath(bath_close, [&](const auto &...bath) {
+		with_drift(ds, helix, [&](const auto &drift) {
+			with_flag(gather, [&](auto g) {
+				hipLaunchKernelGGL((kd_turnaround_kernel<decltype(g)::value, std::decay_t<decltype(drift)>, std::decay_t<decltype(bath)>...>), dim3(kPrepGrid),
+				                   dim3(kPrepBlock), 0, st, c->pos4.as<float4>(), c->unsort.as<int>(), x, v_in, v_out, (const float *)a, param, ks, drift,
+				                   elastic ? 1 : 0, n, next_rebuild ? 1 : 0, c->sel_hist.as<uint32_t>(), words_a, c->sel_nodes.as<uint32_t>(), words_b,
+				                   c->counters.as<int>() + 110, c->prep_state.as<unsigned>(), tv, root6, bath...);
+			});
+		});
+	});
 	NBCO_HIP(hipGetLastError());
 	link->prep_done = next_rebuild ? 1 : 2;
 	c->order_n = -1;

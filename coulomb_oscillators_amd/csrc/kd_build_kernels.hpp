@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kPrepBlock) void kd_prep_kernel(const float *__rest
 // cleared selection state (kd_prep_kernel).  Here every particle goes through exactly those operations, in that order and
 // with the same roundings, in registers.  GATHER: the evaluation rebuilt the tree (velocities come through `unsort`, v_out
 // must not be v_in); PREP: 1 = the next evaluation rebuilds (full build prologue), 0 = it reuses the tree (positions packed only).
-// Drift = float: the straight drift x += v ds, as ever.  Drift = Helix3: nbco_integrate_steps_b, the drift of kick_drift_kernel<Helix3>.
+// Drift = float: the straight drift x += v ds, as ever.  Drift = Helix3: nbco_integrate_steps_b, the drift of helix_vec / helix_scalar (k_axpy.hip).
 // Bath: empty (no bath, and no argument: the plain and Helix3 instantiations keep their argument lists), or Bath3, the closing half of
 // the Langevin bath of the step that ends here (nbco_integrate_steps_t): between the two half kicks the velocity of output row i -- the
 // tree-order row, which the step-by-step sequence sees after reorder_state -- goes through bath_kick(half 1, tick) and then

@@ -1,10 +1,7 @@
 // nbco_api.hip -- the C ABI of include/nbco.h: context, option handling, the evaluator dispatch
-// of compute_force (integrator.cuh:22-28 over main3.cu:47-69) and the symplectic integrators
-// (integrator.cuh:32-167).
+// of compute_force (integrator.cuh:22-28 over main3.cu:47-69) and thin wrappers over the launchers.
+// The symplectic integrators (integrator.cuh:32-167) are nbco_integrate.hip.
 #include "nbco_internal.hpp"
-#include "integ_compose.hpp"
-#include "helix.hpp"
-#include "bath.hpp"
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -132,157 +129,27 @@ static int check_opts(nbco_ctx *c, const nbco_opts *o)
 	return NBCO_OK;
 }
 
-// F K(ds) at the end of a leapfrog step.  `run` is what comes before the kick -- the force evaluation, or the re-ordering the last
-// evaluation of a fused run has left.  The elastic term and the kick share one pass over x, v, a, and when `run` has just
-// re-ordered the particles, the kick reads the tree-ordered velocities straight from the scratch copy.
-template <class Run>
-static int closing_kick(nbco_ctx *c, KdStepLink &link, Run run, float *buf, long long n, const float *param, float ds, bool elastic)
+int maybe_sync(nbco_ctx *c)
 {
-	float *x = buf, *v = buf + 3 * n, *a = buf + 6 * n;
-	link.defer_v_copy = true;
-	link.v_now = nullptr;
-	const int rc = run();
-	const float *v_in = link.v_now ? link.v_now : v;
-	if (rc != NBCO_OK)
-	{
-		if (v_in != v) hipMemcpyAsync(v, v_in, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream);   // leave a whole state behind
-		return rc;
-	}
-	PhaseScope ph(c, NBCO_PH_AXPY);
-	return launch_finish_kick(c, x, v_in, v, a, param, ds, n, elastic);
-}
-
-// ---- Langevin bath: coefficients of the exact Ornstein-Uhlenbeck step over s for the first `dim` axes (include/nbco.h; declared in
-// nbco_internal.hpp: the 2-D calls of k_fmm2d.hip use them with dim = 2)
-bool bath_valid(const nbco_bath *b, int dim)
-{
-	for (int a = 0; a < dim; ++a)
-		if (!std::isfinite(b->gamma[a]) || b->gamma[a] < 0.0 || !std::isfinite(b->kT[a]) || b->kT[a] < 0.0) return false;
-	return true;
-}
-
-bool bath_off(const nbco_bath *b, int dim)
-{
-	for (int a = 0; a < dim; ++a)
-		if (b->gamma[a] != 0.0) return false;
-	return true;
-}
-
-int bath_coeffs_dim(const nbco_bath *b, double s, double *c1, double *c2, int dim)
-{
-	if (!b || !c1 || !c2 || !bath_valid(b, dim) || !std::isfinite(s) || s < 0.0) return NBCO_ERR_ARG;
-	for (int a = 0; a < dim; ++a)
-	{
-		const double gs = b->gamma[a] * s;
-		c1[a] = std::exp(-gs);
-		c2[a] = std::sqrt(b->kT[a] * (-std::expm1(-2.0 * gs)));
-	}
+	if (c->o.sync) NBCO_HIP(hipStreamSynchronize(c->stream));
 	return NBCO_OK;
 }
 
-// ---- uniform magnetic field: the matrices of the helix drift (include/nbco.h) ---------------------------------------------------
-namespace {
-
-// sin(theta), 1 - cos(theta), (1 - cos(theta)) / w and (theta - sin(theta)) / w for theta = (w + dw) s.  theta = p + e with p the rounded
-// product and e what the rounding and dw leave: at theta = 100 one ulp of theta alone is tens of ulps of the sine.
-struct HelixCoef { double sn, vc, c1, c2; };
-constexpr double kHelixSeries = 0.5;   // |theta| below which theta - sin(theta) is summed as a series (the difference cancels there)
-
-HelixCoef helix_coef(double w, double dw, double s)
+// the evaluator dispatch of compute_force (nbco_force and the integrators of nbco_integrate.hip)
+int eval_kind(nbco_ctx *c, int kind, float *p, float *a, long long n, const float *param, KdStepLink *link)
 {
-	const double p = w * s, e = std::fma(w, s, -p) + dw * s, h = 0.5 * p;
-	const double sh = std::sin(h) + 0.5 * e * std::cos(h);   // sin(theta / 2)
-	HelixCoef k;
-	k.vc = 2.0 * sh * sh;
-	k.sn = std::sin(p) + e * std::cos(p);
-	double tms;
-	if (std::fabs(p) < kHelixSeries)
+	switch (kind)
 	{
-		// theta^3/3! - theta^5/5! + ..., nested; the first term left out is theta^17/17!: below 2^-60 of the sum
-		const double t = p + e, t2 = t * t;
-		tms = t * t2 / 6.0 * (1.0 - t2 / 20.0 * (1.0 - t2 / 42.0 * (1.0 - t2 / 72.0 * (1.0 - t2 / 110.0 * (1.0 - t2 / 156.0 * (1.0 - t2 / 210.0))))));
+	case NBCO_EVAL_DIRECT: return launch_direct(c, p, a, n, param, false);
+	case NBCO_EVAL_DIRECT_KAHAN: return launch_direct(c, p, a, n, param, true);
+	case NBCO_EVAL_FMM_KDTREE: return fmm_kdtree_eval(c, p, a, n, param, link);
+	case NBCO_EVAL_FMM_TRACELESS: return fmm_oct_traceless_eval(c, p, a, n, param, false);
+	case NBCO_EVAL_FMM_SYMMETRIC: return fmm_oct_traceless_eval(c, p, a, n, param, true);
+	default: return c->fail(NBCO_ERR_ARG, "unknown evaluator kind");
 	}
-	else tms = (p - std::sin(p)) + e * k.vc;
-	k.c1 = k.vc / w;
-	k.c2 = tms / w;
-	return k;
 }
-
-// float matrices of the 3-D device drift; false: Omega or s is not finite
-bool helix3_make(const double *omega3, double s, Helix3 &h)
-{
-	double R[9], A[9];
-	if (nbco_helix_matrices(omega3, s, R, A) != NBCO_OK) return false;
-	for (int i = 0; i < 9; ++i) { h.R[i] = (float)R[i]; h.A[i] = (float)A[i]; }
-	return true;
-}
-
-bool omega3_finite(const double *o) { return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]); }
-
-// the kernel argument of the 3-D bath step: coefficients narrowed to float once, the seed and the tick as two words each
-bool bath3_make(const nbco_bath *b, double s, int half, unsigned long long tick, Bath3 &out)
-{
-	double c1[3], c2[3];
-	if (bath_coeffs_dim(b, s, c1, c2, 3) != NBCO_OK) return false;
-	for (int a = 0; a < 3; ++a) { out.c1[a] = (float)c1[a]; out.c2[a] = (float)c2[a]; }
-	out.key[0] = (uint32_t)b->seed; out.key[1] = (uint32_t)(b->seed >> 32);
-	out.tick[0] = (uint32_t)tick; out.tick[1] = (uint32_t)(tick >> 32);
-	out.half = half;
-	return true;
-}
-
-} // namespace
 
 extern "C" {
-
-int nbco_bath_coeffs(const nbco_bath *b, double s, double *c1, double *c2) { return bath_coeffs_dim(b, s, c1, c2, 3); }
-
-int nbco_helix_matrices(const double *o, double s, double *R, double *A)
-{
-	if (!o || !R || !A || !omega3_finite(o) || !std::isfinite(s)) return NBCO_ERR_ARG;
-	for (int i = 0; i < 9; ++i) { R[i] = i % 4 == 0 ? 1.0 : 0.0; A[i] = i % 4 == 0 ? s : 0.0; }
-	const double m = std::fmax(std::fabs(o[0]), std::fmax(std::fabs(o[1]), std::fabs(o[2])));
-	if (m == 0.0) return NBCO_OK;
-	// u = Omega / 2^ex (exact), S = |u|^2 as hi + lo (two-products, two-sums), |u| = wu + dwu
-	int ex;
-	std::frexp(m, &ex);
-	double u[3], hi = 0.0, lo = 0.0;
-	for (int k = 0; k < 3; ++k)
-	{
-		u[k] = std::ldexp(o[k], -ex);
-		const double q = u[k] * u[k], qe = std::fma(u[k], u[k], -q), t = hi + q, bb = t - hi;
-		lo += ((hi - (t - bb)) + (q - bb)) + qe;
-		hi = t;
-	}
-	const double S = hi + lo, wu = std::sqrt(S), dwu = (std::fma(-wu, wu, hi) + lo) / (2.0 * wu);
-	const double w = std::ldexp(wu, ex), dw = std::ldexp(dwu, ex);
-	if (!std::isfinite(w) || !std::isfinite(w * s)) return NBCO_ERR_ARG;
-	const HelixCoef k = helix_coef(w, dw, s);
-	const double n[3] = {u[0] / wu, u[1] / wu, u[2] / wu};
-	const double N[9] = {0.0, -n[2], n[1], n[2], 0.0, -n[0], -n[1], n[0], 0.0};   // N v = n x v
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j)
-		{
-			const double d = i == j ? 1.0 : 0.0, n2 = u[i] * u[j] / S - d;         // N^2 = n n^T - I
-			R[3 * i + j] = d - k.sn * N[3 * i + j] + k.vc * n2;
-			A[3 * i + j] = s * d - k.c1 * N[3 * i + j] + k.c2 * n2;
-		}
-	return NBCO_OK;
-}
-
-// N = [[0, -1], [1, 0]], N^2 = -I: R = cos(theta) I - sin(theta) N, A = (sin(theta) / w) I - ((1 - cos(theta)) / w) N  (s - (theta - sin(theta)) / w
-// is sin(theta) / w; taken directly, nothing cancels and no series is needed)
-int nbco_2d_helix_matrices(double w, double s, double *R, double *A)
-{
-	if (!R || !A || !std::isfinite(w) || !std::isfinite(s) || !std::isfinite(w * s)) return NBCO_ERR_ARG;
-	R[0] = R[3] = 1.0; R[1] = R[2] = 0.0;
-	A[0] = A[3] = s; A[1] = A[2] = 0.0;
-	if (w == 0.0) return NBCO_OK;
-	const HelixCoef k = helix_coef(w, 0.0, s);
-	R[0] = R[3] = 1.0 - k.vc; R[1] = k.sn; R[2] = -k.sn;
-	A[0] = A[3] = k.sn / w; A[1] = k.c1; A[2] = -k.c1;
-	return NBCO_OK;
-}
 
 int nbco_opts_default(nbco_opts *o)
 {
@@ -388,12 +255,6 @@ int nbco_sync(nbco_ctx *c)
 {
 	if (!c) return NBCO_ERR_ARG;
 	NBCO_HIP(hipStreamSynchronize(c->stream));
-	return NBCO_OK;
-}
-
-static int maybe_sync(nbco_ctx *c)
-{
-	if (c->o.sync) NBCO_HIP(hipStreamSynchronize(c->stream));
 	return NBCO_OK;
 }
 
@@ -624,20 +485,6 @@ int nbco_dist_finish(nbco_ctx *c, const void *nodes_all, const void *pos_all, fl
 	return maybe_sync(c);
 }
 
-// link: the leapfrog drivers' hand-off with the kd-tree evaluator (KdStepLink); the other evaluators take no part in it
-static int eval_kind(nbco_ctx *c, int kind, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr)
-{
-	switch (kind)
-	{
-	case NBCO_EVAL_DIRECT: return launch_direct(c, p, a, n, param, false);
-	case NBCO_EVAL_DIRECT_KAHAN: return launch_direct(c, p, a, n, param, true);
-	case NBCO_EVAL_FMM_KDTREE: return fmm_kdtree_eval(c, p, a, n, param, link);
-	case NBCO_EVAL_FMM_TRACELESS: return fmm_oct_traceless_eval(c, p, a, n, param, false);
-	case NBCO_EVAL_FMM_SYMMETRIC: return fmm_oct_traceless_eval(c, p, a, n, param, true);
-	default: return c->fail(NBCO_ERR_ARG, "unknown evaluator kind");
-	}
-}
-
 // the uniform-octree evaluators on `world` GPUs: every rank holds the whole state and builds the whole tree, and evaluates the
 // accelerations of its slab of the cell order only (k_fmm_oct.hip, oct_slab_kernel)
 int nbco_fmm_oct_shard(nbco_ctx *c, float *p, float *a, long long n, const float *param, int symmetric, int world, int rank, long long *bounds_host)
@@ -658,267 +505,6 @@ int nbco_force(nbco_ctx *c, int kind, float *buf, long long n, const float *para
 		NBCO_TRY(launch_add_elastic(c, x, a, n, param + 3, false));
 	}
 	return maybe_sync(c);
-}
-
-// integrator.cuh:32-167.  K(s): v += a*s, D(s): x += v*s, F: a = f(x) (+ elastic term).  The step
-// coefficients are formed in long double and narrowed to float at the step call, as the
-// reference does at its step_func call sites.  omega: null, or the uniform magnetic field whose helix drift replaces D
-// (nbco_integrate_b; checked by the caller).
-static int integrate_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt_, double scale_,
-                          int elastic, const double *omega)
-{
-	if (!c || !buf || !param || n <= 0) return c ? c->fail(NBCO_ERR_ARG, "nbco_integrate: bad arguments") : NBCO_ERR_ARG;
-	struct HostTimer
-	{
-		nbco_ctx *c;
-		std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-		~HostTimer() { c->host_call_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); ++c->host_calls; }
-	} host_timer{c};
-	float *x = buf, *v = buf + 3 * n, *a = buf + 6 * n;
-	const long long n3 = 3 * n;
-	const long double dt = dt_, scale = scale_;
-	auto K = [&](long double s) { PhaseScope ph(c, NBCO_PH_AXPY); return launch_step(c, v, a, (float)s, n3); };
-	auto D = [&](long double s) {
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		c->drifted = true;
-		if (!omega) return launch_step(c, x, v, (float)s, n3);
-		Helix3 h;
-		if (!helix3_make(omega, (double)s, h)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_b: Omega dt is not finite");
-		return launch_drift_b(c, x, v, h, n);
-	};
-	auto F = [&]() {
-		NBCO_TRY(eval_kind(c, kind, x, a, n, param));
-		if (elastic)
-		{
-			PhaseScope ph(c, NBCO_PH_AXPY);
-			NBCO_TRY(launch_add_elastic(c, x, a, n, param + 3, false));
-		}
-		return (int)NBCO_OK;
-	};
-	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, "unknown integrator scheme");
-	if (scheme == NBCO_INTEG_LEAPFROG)
-	{
-		const long double ds = dt * scale * 0.5L;
-		Helix3 h;
-		if (omega && !helix3_make(omega, (double)dt, h)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_b: Omega dt is not finite");
-		{
-			// K(ds) D(dt) fused into one pass over x, v, a
-			PhaseScope ph(c, NBCO_PH_AXPY);
-			if (omega) NBCO_TRY(launch_kick_drift_b(c, x, v, a, (float)ds, h, n));
-			else NBCO_TRY(launch_kick_drift(c, x, v, a, (float)ds, (float)dt, n3));
-		}
-		KdStepLink link;
-		NBCO_TRY(closing_kick(c, link, [&] { return eval_kind(c, kind, x, a, n, param, &link); }, buf, n, param, (float)ds, elastic != 0));
-	}
-	else NBCO_TRY(integ_compose(scheme, dt, scale, K, D, F));
-	return maybe_sync(c);
-}
-
-// `steps` steps of the scheme in one call.  Leapfrog over the kd-tree evaluator (tree order kept, opts.unsort = 0) fuses what lies
-// between two force evaluations -- tree order for x and v, elastic term, the two half kicks, the drift and the next build's
-// prologue: four passes over the state -- into one (kd_turnaround); every particle sees the same operations with the same
-// roundings as in `steps` calls of nbco_integrate, and the final state is bit-identical to theirs.  Everything else loops.
-// bath: null, or the Langevin bath of nbco_integrate_steps_t (checked by the caller), step k at tick0 + k: every step is wrapped in the two
-// half bath steps; in the fused run those between two force evaluations are part of the turnaround pass.
-static int integrate_t_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                            const double *omega, const nbco_bath *bath, unsigned long long tick);
-
-static int integrate_steps_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt_, double scale_, int elastic,
-                                int steps, const double *omega, const nbco_bath *bath = nullptr, unsigned long long tick0 = 0)
-{
-	if (!c || !buf || !param || n <= 0 || steps < 0) return c ? c->fail(NBCO_ERR_ARG, "nbco_integrate_steps: bad arguments") : NBCO_ERR_ARG;
-	const bool fuse = scheme == NBCO_INTEG_LEAPFROG && kind == NBCO_EVAL_FMM_KDTREE && !c->o.unsort && !c->o.track_order && steps >= 2;
-	if (!fuse)
-	{
-		const int sync = c->o.sync;
-		c->o.sync = 0;
-		int rc = NBCO_OK;
-		for (int s = 0; s < steps && rc == NBCO_OK; ++s)
-			rc = bath ? integrate_t_impl(c, scheme, kind, buf, n, param, dt_, scale_, elastic, omega, bath, tick0 + (unsigned long long)s)
-			          : integrate_impl(c, scheme, kind, buf, n, param, dt_, scale_, elastic, omega);
-		c->o.sync = sync;
-		if (rc != NBCO_OK) return rc;
-		return maybe_sync(c);
-	}
-	float *x = buf, *v = buf + 3 * n, *a = buf + 6 * n;
-	const long long n3 = 3 * n;
-	const long double dt = dt_, scale = scale_;
-	const float ds = (float)(dt * scale * 0.5L), dtf = (float)dt;
-	Helix3 h;
-	if (omega && !helix3_make(omega, (double)dt, h)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_steps_b: Omega dt is not finite");
-	const Helix3 *helix = omega ? &h : nullptr;
-	Bath3 bt;
-	if (bath && !bath3_make(bath, 0.5 * dt_, 0, tick0, bt)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_steps_t: bad bath");
-	{
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		if (bath) NBCO_TRY(launch_bath(c, v, bt, n));   // the opening half of the first step
-		if (helix) NBCO_TRY(launch_kick_drift_b(c, x, v, a, ds, h, n));
-		else NBCO_TRY(launch_kick_drift(c, x, v, a, ds, dtf, n3));
-	}
-	KdStepLink link;
-	auto home = [&]() {   // the velocities back into the caller's array
-		if (link.v_now) hipMemcpyAsync(v, link.v_now, sizeof(float) * (size_t)n3, hipMemcpyDeviceToDevice, c->stream);
-		link.v_now = nullptr;
-	};
-	link.defer_order = true;
-	for (int s = 0; s < steps; ++s)
-	{
-		int rc = eval_kind(c, kind, x, a, n, param, &link);
-		if (rc == NBCO_OK && s + 1 < steps)
-		{
-			if (bath) bath3_make(bath, 0.5 * dt_, 1, tick0 + (unsigned long long)s, bt);
-			rc = kd_turnaround(c, buf, param, ds, dtf, elastic != 0, n, &link, nullptr, helix, bath ? &bt : nullptr);
-		}
-		if (rc != NBCO_OK)
-		{
-			home();
-			kd_finish_pending_order(c, x, n, &link);   // leave a whole state behind
-			return rc;
-		}
-	}
-	home();
-	// tail of the last step, as in nbco_integrate: tree order, then a -= k o x, v += a ds
-	NBCO_TRY(closing_kick(c, link, [&] { return kd_finish_pending_order(c, x, n, &link); }, buf, n, param, ds, elastic != 0));
-	if (bath)
-	{
-		// the closing half of the last step
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		bath3_make(bath, 0.5 * dt_, 1, tick0 + (unsigned long long)(steps - 1), bt);
-		NBCO_TRY(launch_bath(c, v, bt, n));
-	}
-	return maybe_sync(c);
-}
-
-int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic)
-{
-	return integrate_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, nullptr);
-}
-
-int nbco_integrate_steps(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                         int steps)
-{
-	return integrate_steps_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, steps, nullptr);
-}
-
-// ---- uniform magnetic field (include/nbco.h) ------------------------------------------------------------------------------------
-int nbco_drift_b(nbco_ctx *c, float *x, float *v, long long n, const double *omega3_host, double s)
-{
-	if (!c || !x || !v || !omega3_host || n < 0) return c ? c->fail(NBCO_ERR_ARG, "nbco_drift_b: bad arguments") : NBCO_ERR_ARG;
-	Helix3 h;
-	if (!helix3_make(omega3_host, s, h)) return c->fail(NBCO_ERR_ARG, "nbco_drift_b: Omega and s must be finite");
-	PhaseScope ph(c, NBCO_PH_AXPY);
-	c->drifted = true;
-	return launch_drift_b(c, x, v, h, n);
-}
-
-// what nbco_integrate_b and nbco_integrate_steps_b refuse before any launch; Omega = 0: `omega` comes back null (the call is its counterpart)
-static int integrate_b_args(nbco_ctx *c, const char *who, int scheme, int kind, const float *buf, long long n, const float *param, double dt, int steps,
-                            const double *&omega)
-{
-	if (!c) return NBCO_ERR_ARG;
-	const std::string w(who);
-	if (!buf || !param || n <= 0 || steps < 0) return c->fail(NBCO_ERR_ARG, w + ": bad arguments");
-	if (!omega) return c->fail(NBCO_ERR_ARG, w + ": omega3_host is NULL");
-	if (!omega3_finite(omega)) return c->fail(NBCO_ERR_ARG, w + ": Omega must be finite");
-	if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, w + ": unknown integrator scheme");
-	if (kind < NBCO_EVAL_DIRECT || kind > NBCO_EVAL_FMM_SYMMETRIC) return c->fail(NBCO_ERR_ARG, w + ": unknown evaluator kind");
-	if (kind == NBCO_EVAL_FMM_KDTREE && n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit tree indices");
-	if (omega[0] == 0.0 && omega[1] == 0.0 && omega[2] == 0.0) { omega = nullptr; return NBCO_OK; }
-	Helix3 h;
-	if (!helix3_make(omega, dt, h)) return c->fail(NBCO_ERR_ARG, w + ": Omega dt is not finite");
-	return NBCO_OK;
-}
-
-int nbco_integrate_b(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                     const double *omega3_host)
-{
-	NBCO_TRY(integrate_b_args(c, "nbco_integrate_b", scheme, kind, buf, n, param, dt, 0, omega3_host));
-	return integrate_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega3_host);
-}
-
-int nbco_integrate_steps_b(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                           int steps, const double *omega3_host)
-{
-	NBCO_TRY(integrate_b_args(c, "nbco_integrate_steps_b", scheme, kind, buf, n, param, dt, steps, omega3_host));
-	return integrate_steps_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, steps, omega3_host);
-}
-
-// ---- Langevin bath (include/nbco.h) ---------------------------------------------------------------------------------------------
-// O(dt/2, half 0) S(dt) O(dt/2, half 1); the arguments were checked by integrate_t_args
-static int integrate_t_impl(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                            const double *omega, const nbco_bath *bath, unsigned long long tick)
-{
-	float *v = buf + 3 * n;
-	Bath3 b;
-	if (!bath3_make(bath, 0.5 * dt, 0, tick, b)) return c->fail(NBCO_ERR_ARG, "nbco_integrate_t: bad bath");
-	{
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		NBCO_TRY(launch_bath(c, v, b, n));
-	}
-	const int sync = c->o.sync;
-	c->o.sync = 0;
-	const int rc = integrate_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega);
-	c->o.sync = sync;
-	if (rc != NBCO_OK) return rc;
-	b.half = 1;
-	{
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		NBCO_TRY(launch_bath(c, v, b, n));
-	}
-	return maybe_sync(c);
-}
-
-int nbco_bath_apply(nbco_ctx *c, float *v, long long n, const nbco_bath *bath, double s, int half, unsigned long long tick)
-{
-	if (!c) return NBCO_ERR_ARG;
-	if (!v || !bath || n < 0) return c->fail(NBCO_ERR_ARG, "nbco_bath_apply: bad arguments");
-	if (half != 0 && half != 1) return c->fail(NBCO_ERR_ARG, "nbco_bath_apply: half must be 0 or 1");
-	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_bath_apply: n must be below 2^31 (the row is one counter word)");
-	Bath3 b;
-	if (!bath3_make(bath, s, half, tick, b)) return c->fail(NBCO_ERR_ARG, "nbco_bath_apply: gamma, kT and s must be finite and not negative");
-	{
-		PhaseScope ph(c, NBCO_PH_AXPY);
-		NBCO_TRY(launch_bath(c, v, b, n));
-	}
-	return maybe_sync(c);
-}
-
-// what nbco_integrate_t and nbco_integrate_steps_t refuse before any launch.  All gamma = 0: `bath` comes back null; Omega null or 0:
-// `omega` comes back null (the call is its counterpart)
-static int integrate_t_args(nbco_ctx *c, const char *who, int scheme, int kind, const float *buf, long long n, const float *param, double dt, int steps,
-                            const double *&omega, const nbco_bath *&bath)
-{
-	if (!c) return NBCO_ERR_ARG;
-	const std::string w(who);
-	if (!buf || !param || n <= 0 || steps < 0) return c->fail(NBCO_ERR_ARG, w + ": bad arguments");
-	if (!bath) return c->fail(NBCO_ERR_ARG, w + ": bath_host is NULL");
-	if (!bath_valid(bath, 3)) return c->fail(NBCO_ERR_ARG, w + ": gamma and kT must be finite and not negative");
-	if (omega) NBCO_TRY(integrate_b_args(c, who, scheme, kind, buf, n, param, dt, steps, omega));
-	else
-	{
-		if (scheme < NBCO_INTEG_EULER || scheme > NBCO_INTEG_PEFRL) return c->fail(NBCO_ERR_ARG, w + ": unknown integrator scheme");
-		if (kind < NBCO_EVAL_DIRECT || kind > NBCO_EVAL_FMM_SYMMETRIC) return c->fail(NBCO_ERR_ARG, w + ": unknown evaluator kind");
-		if (kind == NBCO_EVAL_FMM_KDTREE && n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit tree indices");
-	}
-	if (bath_off(bath, 3)) { bath = nullptr; return NBCO_OK; }
-	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n must be below 2^31 (the row is one counter word)");
-	if (!std::isfinite(dt) || dt < 0.0) return c->fail(NBCO_ERR_ARG, w + ": dt must be finite and not negative with a bath");
-	return NBCO_OK;
-}
-
-int nbco_integrate_t(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                     const double *omega3_host, const nbco_bath *bath_host, unsigned long long tick)
-{
-	NBCO_TRY(integrate_t_args(c, "nbco_integrate_t", scheme, kind, buf, n, param, dt, 0, omega3_host, bath_host));
-	if (!bath_host) return integrate_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega3_host);
-	return integrate_t_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, omega3_host, bath_host, tick);
-}
-
-int nbco_integrate_steps_t(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param, double dt, double scale, int elastic,
-                           int steps, const double *omega3_host, const nbco_bath *bath_host, unsigned long long tick0)
-{
-	NBCO_TRY(integrate_t_args(c, "nbco_integrate_steps_t", scheme, kind, buf, n, param, dt, steps, omega3_host, bath_host));
-	return integrate_steps_impl(c, scheme, kind, buf, n, param, dt, scale, elastic, steps, omega3_host, bath_host, tick0);
 }
 
 // ---- reductions --------------------------------------------------------------------------------

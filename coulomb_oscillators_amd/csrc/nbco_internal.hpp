@@ -349,6 +349,16 @@ struct PhaseScope
 	~PhaseScope() { c->phase_end(ph); }
 };
 
+// opts.sync off for the lifetime of the scope: the calls a driver makes inside it do not drain the stream one by one, and what the
+// driver does once the scope has ended (maybe_sync, f2d_done) sees the caller's setting again
+struct SyncOff
+{
+	nbco_ctx *c;
+	int saved;
+	explicit SyncOff(nbco_ctx *c_) : c(c_), saved(c_->o.sync) { c->o.sync = 0; }
+	~SyncOff() { c->o.sync = saved; }
+};
+
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- launchers implemented in the kernel translation units -------------------------------------
@@ -369,10 +379,14 @@ int launch_kick_drift_b(nbco_ctx *c, float *x, float *v, const float *a, float k
 // the Langevin bath step on the velocities (bath.hpp)
 struct Bath3;
 int launch_bath(nbco_ctx *c, float *v, const Bath3 &b, long long n);
-// nbco_api.hip: the bath's checks and coefficients over the first `dim` axes
+// nbco_integrate.hip: the bath's checks and coefficients over the first `dim` axes
 bool bath_valid(const nbco_bath *b, int dim);                                               // gamma, kT finite and not negative
 bool bath_off(const nbco_bath *b, int dim);                                                 // every gamma exactly 0
 int bath_coeffs_dim(const nbco_bath *b, double s, double *c1, double *c2, int dim);
+// nbco_api.hip
+// link: the leapfrog drivers' hand-off with the kd-tree evaluator (KdStepLink); the other evaluators take no part in it
+int eval_kind(nbco_ctx *c, int kind, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);
+int maybe_sync(nbco_ctx *c);   // drains the stream with opts.sync
 // k_direct.hip
 int launch_direct(nbco_ctx *c, const float *p, float *a, long long n, const float *param, bool kahan);
 // k_reduce.hip

@@ -365,7 +365,7 @@ struct Session
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
 	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture, const SlicesOpt &slices,
-	             const double *omega, const nbco_bath *bath)
+	             const double *omega, const nbco_bath &bath)
 	{
 		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
@@ -410,9 +410,8 @@ struct Session
 				if (iter == kSteadyFrom) { check(nbco_sync(ctx()), "sync"); steady_t0 = std::chrono::steady_clock::now(); steady_first = iter; }
 				else if (iter < kSteadyFrom) run = std::min(run, kSteadyFrom - iter);   // (K steps in one call == the same steps in two calls, bit for bit)
 			}
-			if (bath) check(nbco_integrate_steps_t(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega, bath, (unsigned long long)iter), "integrate_t");
-			else if (omega) check(nbco_integrate_steps_b(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega), "integrate_b");
-			else check(nbco_integrate_steps(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run), "integrate");
+			// (omega null and all rates zero: the library makes this the plain nbco_integrate_steps call)
+			check(nbco_integrate_steps_t(ctx(), scheme, NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, (double)dt, 1.0, 1, run, omega, &bath, (unsigned long long)iter), "integrate");
 			iter += run;
 			if ((iter - 1) % nSteps != 0) continue;
 			const int snap = iter - 1;
@@ -873,8 +872,6 @@ int main(int argc, const char **argv)
 		if (input_order) { std::cerr << "Error: '-snapshot-order input' is what '-cpu' writes anyway (the direct sum never permutes the state)\n"; return -1; }
 		std::vector<nbco_cpu::V3> st(3 * (size_t)nBodies);
 		std::memcpy(st.data(), host.data(), state_bytes);
-		const nbco_cpu::Scheme sch = scheme == NBCO_INTEG_EULER ? nbco_cpu::Euler : scheme == NBCO_INTEG_FORESTRUTH ? nbco_cpu::ForestRuth
-		                             : scheme == NBCO_INTEG_PEFRL ? nbco_cpu::Pefrl : nbco_cpu::Leapfrog;
 		nbco_cpu::force(st.data(), nBodies, par, o.eps2);
 		EnergyLog elog(energy, strout);
 		MomentsLog mlog(moments, strout);
@@ -887,7 +884,7 @@ int main(int argc, const char **argv)
 		std::vector<nbco_moments> slice_recs;
 		for (int iter = 0; iter < nIters; ++iter)
 		{
-			nbco_cpu::integrate(sch, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr, bath_on ? &bath : nullptr, (unsigned long long)iter);
+			nbco_cpu::integrate(scheme, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr, bath_on ? &bath : nullptr, (unsigned long long)iter);
 			if (iter % nSteps != 0) continue;
 			std::cout << iter << ' ' << std::flush;
 			if (aperture.on)
@@ -958,7 +955,7 @@ int main(int argc, const char **argv)
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
 		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
-		                     bath_on && !b_accuracy ? &bath : nullptr);
+		                     b_accuracy ? nbco_bath{} : bath);
 	}
 	return rc;
 }

@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/nbco.h"
+#include "../csrc/integ_compose.hpp"
 
 namespace nbco_cpu {
 
@@ -330,42 +331,23 @@ inline void bath_apply(V3 *v, int n, const nbco_bath &bath, double s, int half, 
 	});
 }
 
-// one step of the symplectic schemes of integrator.cuh:32-167 (coefficients in long double, narrowed at the step call); omega: null, or
-// the uniform magnetic field whose helix drift replaces x += v c; bath: null, or the Langevin bath whose two half steps O(dt/2) wrap the
-// scheme, at the step number `tick`
-enum Scheme { Euler, Leapfrog, ForestRuth, Pefrl };
-inline void integrate_scheme(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega);
-inline void integrate(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega = nullptr, const nbco_bath *bath = nullptr,
+// one step of a scheme (NBCO_INTEG_*), composed by integ_compose as in the library (coefficients in long double, narrowed at the step call);
+// omega: null, or the uniform magnetic field whose helix drift replaces x += v c; bath: null, or the Langevin bath whose two half steps
+// O(dt/2) wrap the scheme, at the step number `tick`
+inline void integrate_scheme(int scheme, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega)
+{
+	V3 *x = buf, *v = buf + n, *a = buf + 2 * (size_t)n;
+	auto K = [&](long double c) { step(v, a, (float)c, n); return NBCO_OK; };
+	auto D = [&](long double c) { if (omega) drift_b(x, v, omega, (double)c, n); else step(x, v, (float)c, n); return NBCO_OK; };
+	auto F = [&] { force(buf, n, par, eps2); return NBCO_OK; };
+	integ_compose(scheme, dt, 1.0L, K, D, F);
+}
+inline void integrate(int scheme, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega = nullptr, const nbco_bath *bath = nullptr,
                       unsigned long long tick = 0)
 {
 	if (bath) bath_apply(buf + n, n, *bath, 0.5 * (double)dt, 0, tick);
-	integrate_scheme(s, buf, n, par, eps2, dt, omega);
+	integrate_scheme(scheme, buf, n, par, eps2, dt, omega);
 	if (bath) bath_apply(buf + n, n, *bath, 0.5 * (double)dt, 1, tick);
-}
-inline void integrate_scheme(Scheme s, V3 *buf, int n, const float *par, float eps2, long double dt, const double *omega)
-{
-	V3 *x = buf, *v = buf + n, *a = buf + 2 * (size_t)n;
-	auto K = [&](long double c) { step(v, a, (float)c, n); };
-	auto D = [&](long double c) { if (omega) drift_b(x, v, omega, (double)c, n); else step(x, v, (float)c, n); };
-	auto F = [&] { force(buf, n, par, eps2); };
-	switch (s)
-	{
-	case Euler: K(dt); D(dt); F(); break;
-	case Leapfrog: K(dt * 0.5L); D(dt); F(); K(dt * 0.5L); break;
-	case ForestRuth:
-	{
-		constexpr long double th = 1.3512071919596576340476878089715L;
-		D(dt * th / 2); F(); K(dt * th); D(dt * (1 - th) / 2); F(); K(dt * (1 - 2 * th)); D(dt * (1 - th) / 2); F(); K(dt * th); D(dt * th / 2);
-		break;
-	}
-	case Pefrl:
-	{
-		constexpr long double xi = +0.1786178958448091E+00L, la = -0.2123418310626054E+00L, ch = -0.6626458266981849E-01L;
-		D(dt * xi); F(); K(dt * (1 - 2 * la) / 2); D(dt * ch); F(); K(dt * la); D(dt * (1 - 2 * (ch + xi))); F(); K(dt * la); D(dt * ch); F();
-		K(dt * (1 - 2 * la) / 2); D(dt * xi);
-		break;
-	}
-	}
 }
 
 } // namespace nbco_cpu

@@ -146,13 +146,16 @@ int nbco_fmm_symmetric(nbco_ctx *c, float *p, float *a, long long n, const float
 int nbco_force(nbco_ctx *c, int kind, float *buf, long long n, const float *param, int elastic);
 
 /* one step of integrator `scheme` with evaluator `kind` (+ elastic term), integrator.cuh:32-167.
- * dt and scale are the reference's long double arguments narrowed to double. */
+ * dt and scale are the reference's long double arguments narrowed to double.  Refused before any launch, the state untouched:
+ * NBCO_ERR_ARG for a null pointer, n <= 0, an unknown scheme or kind; NBCO_ERR_UNSUPPORTED for the kd-tree evaluator with
+ * n > 0x7fffffff / 4. */
 int nbco_integrate(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
                    double dt, double scale, int elastic);
 /* `steps` steps in one call: the loop body of main3.cu:840-870 between two snapshots.  The final state is bit-identical to
  * `steps` calls of nbco_integrate; leapfrog over the kd-tree evaluator (opts.unsort = 0, no order tracking) runs what lies
  * between two force evaluations -- tree order of x and v, elastic term, both half kicks, the drift, the next build's
- * prologue -- as ONE pass over the state instead of four.  Intermediate states are not observable. */
+ * prologue -- as ONE pass over the state instead of four.  Intermediate states are not observable.  Refused before any launch,
+ * the state untouched, also with steps = 0: steps < 0 and everything nbco_integrate refuses. */
 int nbco_integrate_steps(nbco_ctx *c, int scheme, int kind, float *buf, long long n, const float *param,
                          double dt, double scale, int elastic, int steps);
 

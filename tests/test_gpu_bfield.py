@@ -110,7 +110,7 @@ def test_schemes_elastic_only_against_model(engine, oracle32, scheme, scale):
 @pytest.mark.parametrize("scheme", ig.SCHEMES, ids=[ig.NAMES[s] for s in ig.SCHEMES])
 def test_schemes_elastic_only_odd_n_against_model(engine, oracle32, scheme):
     """the same comparison at n = 257: v = buf + 3 n and a = buf + 6 n are off the 16-byte grid, so leapfrog's fused kick and drift is
-    kick_drift_kernel<Helix3> (one particle per lane) and every drift the one-particle kernel; integrate_steps_b gives the same bits"""
+    helix_scalar<true> (one particle per lane) and every drift the one-particle kernel; integrate_steps_b gives the same bits"""
     import torch
     from coulomb_oscillators_amd import EVAL_DIRECT_KAHAN
     n = 257
@@ -163,7 +163,7 @@ def _state(oracle32, n):
 def test_fused_leapfrog_equals_step_by_step(oracle32, n, p, tree_steps, steps):
     """kd_turnaround_kernel<., Helix3> against the separate passes; afterwards one integrate_b and two more fused steps carry on identically
     (the pattern of test_gpu_integrate_steps.py).  The opening kick and drift of every call is helix_vec<kick> where n % 4 == 0 and
-    kick_drift_kernel<Helix3> at n = 20003 and 5001, where v and a are off the 16-byte grid."""
+    helix_scalar<true> at n = 20003 and 5001, where v and a are off the 16-byte grid."""
     import torch
     from coulomb_oscillators_amd import Engine, EVAL_FMM_KDTREE, INTEG_LEAPFROG
     dt, om = 5e-4, (300.0, -200.0, 700.0)      # |Omega| dt = 0.39: the field turns the velocities visibly within a step

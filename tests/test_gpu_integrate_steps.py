@@ -118,3 +118,53 @@ def test_refused_evaluation_inside_a_fused_run_leaves_the_context_sound(oracle32
         assert torch.equal(states[live][part], states[twin][part]), name + " differ"
     live.close()
     twin.close()
+
+
+def test_plain_calls_refuse_before_any_launch(oracle32):
+    """nbco_integrate and nbco_integrate_steps refuse an unknown scheme or kind (also with steps = 0) and a kd-tree call over the 32-bit
+    index limit before their first launch, as their _b and _t forms do: the state keeps its bytes, and the refused context goes on bit for
+    bit like a twin that was never refused anything"""
+    import ctypes as C
+    import torch
+    from coulomb_oscillators_amd import Engine, EngineError, EVAL_FMM_KDTREE, INTEG_LEAPFROG
+    n, dt = 5000, 5e-4
+    live, twin = Engine(fmm_order=4, unsort=0), Engine(fmm_order=4, unsort=0)
+    d, prm = _state(oracle32, n)
+    d2 = d.clone()
+    for e, s in ((live, d), (twin, d2)):
+        e.compute_force(EVAL_FMM_KDTREE, s, n, prm)
+        e.integrate_steps(INTEG_LEAPFROG, EVAL_FMM_KDTREE, s, n, prm, dt, 2)
+    torch.cuda.synchronize()
+    assert torch.equal(d.view(torch.int32), d2.view(torch.int32))
+    before = d.clone()
+    for case in (dict(scheme=7), dict(scheme=-1), dict(kind=9), dict(kind=-1)):
+        a = dict(scheme=INTEG_LEAPFROG, kind=EVAL_FMM_KDTREE)
+        a.update(case)
+        for steps in (None, 3, 0):
+            with pytest.raises(EngineError) as ei:
+                if steps is None:
+                    live.integrate(a["scheme"], a["kind"], d, n, prm, dt)
+                else:
+                    live.integrate_steps(a["scheme"], a["kind"], d, n, prm, dt, steps)
+            assert ei.value.status == 2, (case, steps)                             # NBCO_ERR_ARG
+            torch.cuda.synchronize()
+            assert torch.equal(d.view(torch.int32), before.view(torch.int32)), (case, steps)
+    L, ptr, pp = live.lib, C.c_void_p(d.data_ptr()), C.c_void_p(prm.data_ptr())
+    big = 0x7fffffff // 4 + 1                                                      # refused before the buffer is read
+    assert L.nbco_integrate(live.ctx, INTEG_LEAPFROG, EVAL_FMM_KDTREE, ptr, big, pp, dt, 1.0, 1) == 4                 # NBCO_ERR_UNSUPPORTED
+    assert L.nbco_integrate_steps(live.ctx, INTEG_LEAPFROG, EVAL_FMM_KDTREE, ptr, big, pp, dt, 1.0, 1, 3) == 4
+    torch.cuda.synchronize()
+    assert torch.equal(d.view(torch.int32), before.view(torch.int32))
+    probes = before[0][:16].clone()
+    res = []
+    for e, s in ((live, d), (twin, d2)):
+        a_out = torch.zeros(16, 3, dtype=torch.float64, device="cuda")
+        en = e.energy_fmm(s, n, prm)
+        e.probe_kd(probes, 16, prm, a=a_out)
+        e.integrate_steps(INTEG_LEAPFROG, EVAL_FMM_KDTREE, s, n, prm, dt, 2)
+        torch.cuda.synchronize()
+        res.append((en, a_out, s.clone()))
+    assert res[0][0] == res[1][0] and torch.equal(res[0][1], res[1][1])
+    assert torch.equal(res[0][2].view(torch.int32), res[1][2].view(torch.int32))
+    live.close()
+    twin.close()
