@@ -745,13 +745,16 @@ def test_capped_let_attempt_with_a_flagged_build_is_repeated(oracle32):
     assert redos[0] >= 1 and redos[1] == 0
 
 
-@pytest.mark.parametrize("tree_steps,recut", [(1, 0), (3, 0), (1, 4)])
-def test_sharded_turnaround_equals_step_kernels(oracle32, tree_steps, recut):
+@pytest.mark.parametrize("n,G,tree_steps,recut", [pytest.param(1 << 17, 4, 1, 0, id="1-0"), pytest.param(1 << 17, 4, 3, 0, id="3-0"), pytest.param(1 << 17, 4, 1, 4, id="1-4"),
+                                                  pytest.param(600000, 2, 1, 0, id="600000x2-1-0"), pytest.param(600000, 2, 3, 0, id="600000x2-3-0")])
+def test_sharded_turnaround_equals_step_kernels(oracle32, n, G, tree_steps, recut):
     """nbco_dist_turnaround (one pass between two force evaluations of a sharded leapfrog run: elastic term, both half kicks, drift,
     next build's prologue) against nbco_add_elastic + three nbco_step calls + the build's own prologue: same state bit for bit,
-    through tree reuse and through a re-cut of the domains in the middle (which discards the prologue)"""
+    through tree reuse and through a re-cut of the domains in the middle (which discards the prologue).  n_local = 32 768 fills a quarter
+    of slot 0 of kd_turnaround_kernel's first trip; n_local = 300 000 fills slots 0 and 1 and puts 37 856 rows into slot 2, and the box
+    of the prologue is the union with the domain's inherited one (tests/test_gpu_turnaround_shapes.py names the slots)"""
     import torch
-    n, G, p, steps, dt = 1 << 17, 4, 4, 7, 5e-4
+    p, steps, dt = 4, 7, 5e-4
     pos, vel = make_state(oracle32, n, "reference")
     par = torch.from_numpy(oracle32.params(n)).cuda()
     nl = n // G
