@@ -151,3 +151,19 @@ def drive_by_hand(eng, d, n, prm, dt, evals, force, on_eval=None):
             on_eval(k, x_in)
         if k:
             eng.step(d[1], d[2], dt / 2, n)
+
+
+def warm_engine(warm, **opts):
+    """an Engine whose kd-tree build uses the warm median select (k_kdselect.hip) or never does: NBCO_SEL_WARM is read when the
+    context is created, and is put back afterwards"""
+    import os
+    from coulomb_oscillators_amd import Engine
+    old = os.environ.get("NBCO_SEL_WARM")
+    os.environ["NBCO_SEL_WARM"] = "1" if warm else "0"
+    try:
+        return Engine(**opts)
+    finally:
+        if old is None:
+            del os.environ["NBCO_SEL_WARM"]
+        else:
+            os.environ["NBCO_SEL_WARM"] = old

@@ -5,11 +5,17 @@ the ball's particle count, velocities and length scale.  Pure numpy on top of Or
 CASES lists (evaluator, shape, n, p, what).  what = "forces": both oracles are finite on the input and agree on the tree, so the
 accelerations of a GPU evaluation are compared with them.  what = "lists": the reference's forces mean nothing on the input (fp32
 cancellation, lists that differ between fp32 and fp64, NaN in both precisions); only the tree / keys / lists are compared.
-test_shapes3d_host.py asserts, without a GPU, that every case is what this table says it is."""
+test_shapes3d_host.py asserts, without a GPU, that every case is what this table says it is.
+
+SELECT_CASES lists (shape, n, p, what) for the kd-tree at sizes whose top levels are built by selection (test_gpu_select_shapes.py),
+and select_nodes / mode_from_nodes / tie_orders restate on the oracle's tree what that build meets there."""
 import numpy as np
 
-SHAPES = ("gauss", "plane", "plane_off", "line", "lattice", "quant16", "dup2", "dup8", "dup16", "dup64", "late", "two_clumps", "offset")
-DRAWS = ("lattice", "dup2", "dup8", "dup16", "dup64")      # the shapes that take a permutation, in the order they draw it
+SHAPES = ("gauss", "plane", "plane_off", "line", "lattice", "quant16", "dup2", "dup8", "dup16", "dup64", "late", "two_clumps", "offset",
+          "dup128", "ejected", "zeros", "quant2048")
+# the shapes that take a permutation, in the order they draw it (new ones at the end only: the states of the others keep their bytes)
+DRAWS = ("lattice", "dup2", "dup8", "dup16", "dup64", "dup128")
+ZERO_BLOCK = 4                                              # "zeros": -0.0 on this many particles below the root median, +0.0 on as many above
 LATE_ROWS = np.array([[40.0, 0, 0], [0, -55.0, 0], [0, 0, 70.0]], dtype=np.float32)
 
 
@@ -40,13 +46,31 @@ def state(oracle32, name, n):
         m = lattice_side(n)
         g = np.indices((m, m, m)).reshape(3, -1).T.astype(f)
         pos[:] = (((g / f(m)) - f(0.5)) * R)[perm["lattice"]]
-    elif name == "quant16":
-        pos[:] = np.round(pos / R * f(16)) / f(16) * R
+    elif name.startswith("quant"):
+        # a grid of K cells per R: 16 puts hundreds of particles on every grid plane; 2048 a dozen, all at different points of it
+        K = f(int(name[5:]))
+        pos[:] = np.round(pos / R * K) / K * R
     elif name.startswith("dup"):
         K = int(name[3:])
         pos[:] = np.repeat(pos[:n // K], K, axis=0)[perm[name]]
     elif name == "late":
         pos[:3] = LATE_ROWS * R
+    elif name == "ejected":
+        # the late state a long run reaches (nbco.h, list_grow): a few particles thrown out to 1e6 times the ball's size
+        pos[:3] = f(25000) * LATE_ROWS * R
+    elif name == "zeros":
+        # The root cuts the axis of largest extent into the n // 2 smallest keys and the rest.  The axis is shifted (in fp32) so that
+        # exactly n // 2 coordinates are negative, then the ZERO_BLOCK negative ones nearest to zero become -0.0 and the ZERO_BLOCK
+        # positive ones nearest to zero +0.0: eight particles that compare equal as floats, that no linear bucket key separates, and
+        # that the reference's key (the ordered float bits) orders strictly -- the root pivot is -0.0, the right child begins at +0.0.
+        a = int(np.argmax(pos.max(axis=0) - pos.min(axis=0)))
+        x = np.sort(pos[:, a])
+        k = n // 2
+        pos[:, a] -= x[k - 1] + (x[k] - x[k - 1]) / f(2)
+        order = np.argsort(pos[:, a], kind="stable")
+        assert pos[order[k - 1], a] < 0 < pos[order[k], a], "the shift leaves no coordinate at zero and the median at the sign change"
+        pos[order[k - ZERO_BLOCK:k], a] = f(-0.0)
+        pos[order[k:k + ZERO_BLOCK], a] = f(0.0)
     elif name == "two_clumps":
         pos[:n // 2, 0] += f(1000) * R
     elif name == "offset":
@@ -92,6 +116,44 @@ def oct_cases():
 
 
 CASES = kd_cases() + oct_cases()
+
+# the shapes that only SELECT_CASES runs (added with it; CASES is pinned by test_the_table_covers_what_it_has_to)
+SELECT_ONLY = ("dup128", "ejected", "zeros", "quant2048")
+
+
+def select_cases():
+    """(shape, n, p, what) with the meanings of CASES, kd-tree only, at sizes whose top levels are built by SELECTION (k_kdselect.hip:
+    every level whose nodes hold more than 4096 particles).  20480 -> 10240 -> 5120: three selection levels, two with the 1024-thread
+    kernels and one with the 256-thread kernels; 65536: four.  The lattice needs a cube: 27^3 = 19683 -> 9841 / 9842 -> 4920 / 4921."""
+    F, T = "forces", "lists"
+    n = 20480
+    rows = [(s, n, 4, F) for s in ("gauss", "plane", "plane_off", "line", "dup2", "dup8", "dup16", "late", "ejected", "zeros")]
+    rows += [("lattice", 19683, 4, T), ("quant16", n, 4, T), ("dup64", n, 4, T), ("dup128", n, 4, T), ("two_clumps", n, 4, T), ("offset", n, 4, T),
+             ("quant2048", n, 4, T)]
+    rows += [("late", n, 6, F), ("dup8", n, 6, F)]
+    rows += [("late", 65536, 4, F), ("plane", 65536, 4, F), ("line", 65536, 4, F), ("ejected", 65536, 4, F)]
+    return rows
+
+
+SELECT_CASES = select_cases()
+SELECT_MIN = 4096          # kSubS: a node above it is split by selection, the rest of its subtree in one workgroup's LDS
+TIE_CAP = 64               # kTieCap of k_kdselect.hip: candidates the exact resolver orders
+# why a "lists" row of SELECT_CASES is one (the vocabulary of LISTS_WHY below)
+SELECT_LISTS_WHY = {
+    ("lattice", 19683, 4): "lists_differ", ("quant16", 20480, 4): "nonfinite", ("dup64", 20480, 4): "nonfinite",
+    ("dup128", 20480, 4): "nonfinite", ("two_clumps", 20480, 4): "lists_differ", ("offset", 20480, 4): "lists_differ",
+    ("quant2048", 20480, 4): "lists_differ",
+}
+
+
+def kd_of(row):
+    """a SELECT_CASES row as a case of evaluate()"""
+    return ("kd",) + tuple(row)
+
+
+def select_id(row):
+    return "%s-%d-p%d-%s" % tuple(row)
+
 
 # octree "forces" cases on which the fp32 oracle overflows (a stretched tree: few occupied cells far apart, r^-(p+1) (2p-1)!! out
 # of the fp32 range) while the fp64 oracle is finite.  There the GPU runs with far_fp64 = 1 and is compared with the fp64 oracle
@@ -234,3 +296,128 @@ def alive_columns(w32, w64):
     and nothing can be asked of a third evaluation.  (Where both oracles have an exact zero the column stays alive, and the GPU has
     to have an exact zero too.)"""
     return column_errs(np.asarray(w32, dtype=np.float64), w64) < 1e-2
+
+
+# ---- the selection levels of a kd-tree (k_kdselect.hip), restated on the oracle's tree -----------------------------------------
+def ordered_key(x):
+    """the reference's sort key of a float32: its bits, ordered (-0.0 strictly before +0.0)"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(u >> 31, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def lin_bucket(x, lo, hi, bits=22):
+    """lin_window / lin_key of k_kdselect.hip in float32 numpy, every subtraction, division and multiplication rounded to fp32:
+    the top `bits` bits of the box-linear key of the coordinates x in a node whose box is [lo, hi] along the split axis"""
+    f = np.float32
+    top = f(4294967040.0)
+    span = f(hi) - f(lo)
+    scale = top / span if span > 0 else f(0)
+    v = (np.asarray(x, dtype=f) - f(lo)) * f(scale)
+    assert v.dtype == f
+    return np.minimum(np.maximum(v, f(0)), top).astype(np.uint32) >> np.uint32(32 - bits)
+
+
+def warm_bits(n, level):
+    """bits of the warm select's bucket key at a level of a tree over n particles (kd_select_level, before any miss has coarsened
+    it): about 1 / 64 element per bucket, between 16 and 22 bits"""
+    node = n >> level
+    lg = 0
+    while (1 << lg) < node:
+        lg += 1
+    return max(12, min(22, max(16, lg + 6)))
+
+
+def select_nodes(tree, pos_tree_order):
+    """One row per node that the build splits by selection (more than SELECT_MIN particles), from a tree dict of the oracle and the
+    positions in that tree's order: (node, ties, bucket, ties_left, near, warm).
+      ties       particles of the node whose key along the split axis equals the pivot's (the largest key of the left child)
+      bucket     particles of the node in the pivot's 22-bit bucket of the box-linear key (lin_bucket) over the node's own box
+      ties_left  how many of the ties are in the left child: ties_left == ties means that the cut falls BEHIND the tied run
+      near       particles in the pivot's bucket or one of its two neighbours
+      warm       particles in the pivot's bucket of the WARM select, which cuts the same key into warm_bits(level) bits"""
+    pos = np.asarray(pos_tree_order, dtype=np.float32)
+    rows = []
+    for v in np.flatnonzero(np.asarray(tree["mult"]) > SELECT_MIN):
+        if 2 * v + 2 >= tree["ntot"]:
+            continue
+        a, i, m = int(tree["splitdim"][v]), int(tree["index"][v]), int(tree["mult"][v])
+        ml = int(tree["mult"][2 * v + 1])
+        assert int(tree["index"][2 * v + 1]) == i
+        x = pos[i:i + m, a]
+        key = ordered_key(x)
+        pivot = int(np.argmax(key[:ml]))
+        assert key[:ml].max() <= key[ml:].min(), "the oracle's children are the ml smallest keys and the rest"
+        tie = key == key[pivot]
+        b = lin_bucket(x, tree["lbound"][v, a], tree["rbound"][v, a]).astype(np.int64)
+        w = b >> (22 - warm_bits(int(tree["mult"][0]), int(v + 1).bit_length() - 1))
+        rows.append((int(v), int(tie.sum()), int((b == b[pivot]).sum()), int(tie[:ml].sum()), int((np.abs(b - b[pivot]) <= 1).sum()),
+                     int((w == w[pivot]).sum())))
+    return np.array(rows, dtype=np.int64).reshape(-1, 6)
+
+
+def mode_from_nodes(nodes):
+    """What nbco_kd_get_info's build_mode has to be after a first build, from select_nodes' rows; None where the figures do not decide.
+
+    The build starts with the two-pass select: every element of the pivot's 22-bit bucket is a candidate of the exact resolver,
+    which takes TIE_CAP of them.  A fuller bucket flags the build and it is repeated with three passes (mode 1), whose candidates
+    are the exact ties of the pivot -- and those only where the cut falls INSIDE the tied run (all_left in sel_partition_kernel: a run
+    that ends with the left child goes left as a whole and nobody resolves it).  More than TIE_CAP of them flag that build too and
+    the sorting build takes over (mode 2).
+      2     some node has more than TIE_CAP ties and the cut inside them
+      1     not 2, and some node's bucket certainly overflows: more than TIE_CAP ties (equal keys share a bucket however the key is
+            cut into digits), or more than 4 x TIE_CAP particles in the restated bucket
+      0     every restated bucket holds at most TIE_CAP / 2
+    The factors 4 and 1 / 2 keep the expectation independent of how the two radix passes cut the 22 bits and of the last bit of
+    this restatement."""
+    ties, bucket, left = nodes[:, 1], nodes[:, 2], nodes[:, 3]
+    if ((ties > TIE_CAP) & (left < ties)).any():
+        return 2
+    if (ties > TIE_CAP).any() or (bucket > 4 * TIE_CAP).any():
+        return 1
+    if (bucket <= TIE_CAP // 2).all():
+        return 0
+    return None
+
+
+def expected_mode(oracle32, oracle64, row):
+    """mode_from_nodes on the fp32 oracle's tree of a SELECT_CASES row, as a set of admissible modes (None: not asserted).
+    dup64: TIE_CAP copies of every point.  The rule is nt > kTieCap, so a bucket that holds exactly one point's copies still fits
+    the resolver (mode 0); one neighbour in it and the build goes to three passes, where every cut falls behind a tied run (mode 1).
+    Where the pivot's bucket AND its two neighbours hold nothing but the copies at every selection node, rounding cannot add
+    one: then it is mode 0."""
+    r = evaluate(oracle32, oracle64, kd_of(row))
+    nodes = select_nodes(r["t32"], r["buf"][0][r["t32"]["perm"]])
+    if row[0] == "dup64":
+        return {0} if (nodes[:, 4] == TIE_CAP).all() and (nodes[:, 1] == TIE_CAP).all() else {0, 1}
+    mode = mode_from_nodes(nodes)
+    return None if mode is None else {mode}
+
+
+def tie_orders(tree, pos_tree_order):
+    """The exact tie resolver's order, restated: inside node v the reference's stable-sort chain orders by (c[a1], c[a2], c[a3],
+    original index), a1 = splitdim(v), a2 and a3 the next distinct split axes of v's ancestors, nearest first (k_kdselect.hip, head).
+    One row per selection node whose cut falls inside a run of equal c[a1]: (node, chain, blind) -- chain: the tied particles that
+    the oracle's tree has in the left child are the first ones of that order; blind: they are ALSO the first ones of the order
+    without c[a2], so that a resolver that ignores its second key would not be seen at this node."""
+    pos = np.asarray(pos_tree_order, dtype=np.float32)
+    org = np.asarray(tree["perm"], dtype=np.int64)
+    rows = []
+    for v, ties, _, left, _, _ in select_nodes(tree, pos):
+        if left == ties:
+            continue
+        i, m, ml = int(tree["index"][v]), int(tree["mult"][v]), int(tree["mult"][2 * v + 1])
+        a1 = int(tree["splitdim"][v])
+        rest, u = [], int(v)
+        while u > 0 and len(rest) < 2:
+            u = (u - 1) // 2
+            a = int(tree["splitdim"][u])
+            if a != a1 and a not in rest:
+                rest.append(a)
+        key = ordered_key(pos[i:i + m, a1])
+        tied = np.flatnonzero(key == key[:ml].max())
+        k23 = [ordered_key(pos[i + tied, a]) if a is not None else np.zeros(len(tied), dtype=np.uint32) for a in (rest + [None, None])[:2]]
+        went_left = set(tied[tied < ml].tolist())
+        full = tied[np.lexsort((org[i + tied], k23[1], k23[0]))][:left]
+        blind = tied[np.lexsort((org[i + tied], k23[1]))][:left]
+        rows.append((int(v), set(full.tolist()) == went_left, set(blind.tolist()) == went_left))
+    return rows

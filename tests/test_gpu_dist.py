@@ -10,9 +10,14 @@ oracle."""
 import numpy as np
 import pytest
 
+import shapes3d as S
+
 pytestmark = pytest.mark.gpu
 
 MUTUAL = [0, 1]   # opts.p2p_mutual
+# flat, collinear, tied and late-run states (shapes3d): the domain cuts of k_dpart.hip and every domain's own selection level on them
+SHAPE_KINDS = [(32768, 4, 4, shape) for shape in ("plane", "line", "dup8", "late")]
+NAN_KINDS = ("dup64",)   # 64 copies of every point: NaN in the reference and here; positions and velocities are compared
 
 
 def same_acc(got, ref, mutual, n):
@@ -25,6 +30,9 @@ def same_acc(got, ref, mutual, n):
 
 
 def make_state(oracle, n, kind="reference"):
+    if kind in S.SHAPES:          # a degenerate shape of the 3-D shape tests (shapes3d.state)
+        buf = S.state(oracle, kind, n)
+        return np.ascontiguousarray(buf[0]), np.ascontiguousarray(buf[1])
     if kind == "reference":
         buf = oracle.init_reference(n)
         return np.ascontiguousarray(buf[0]), np.ascontiguousarray(buf[1])
@@ -141,7 +149,8 @@ def loopback(n, G, pos, vel, gather_partition=None, **opts):
 
 
 @pytest.mark.parametrize("n,G,p,kind", [(32768, 2, 6, "reference"), (32768, 4, 4, "reference"), (32768, 8, 6, "clumps"),
-                                        (40000, 8, 5, "uniform"), (24576, 2, 3, "clumps"), (1 << 20, 4, 6, "reference"), (32768, 4, 10, "uniform")])
+                                        (40000, 8, 5, "uniform"), (24576, 2, 3, "clumps"), (1 << 20, 4, 6, "reference"), (32768, 4, 10, "uniform")]
+                         + SHAPE_KINDS + [(32768, 4, 4, "dup64")])
 @pytest.mark.parametrize("mutual", MUTUAL)
 def test_sharded_equals_single_gpu(oracle32, n, G, p, kind, mutual):
     """(the exchange runs in its two-stage form: traversal records + positions first, multipoles behind the traversal)"""
@@ -159,8 +168,9 @@ def test_sharded_equals_single_gpu(oracle32, n, G, p, kind, mutual):
     got_acc = torch.cat([r.acc for r in world.runs])
     assert torch.equal(got_pos, ref[:3 * n]), "tree order of the positions differs"
     assert torch.equal(got_vel, ref[3 * n:6 * n]), "velocities were not carried along"
-    assert torch.isfinite(got_acc).all()
-    assert same_acc(got_acc, ref[6 * n:], mutual, n), "accelerations differ from the single-GPU evaluation"
+    if kind not in NAN_KINDS:
+        assert torch.isfinite(got_acc).all()
+        assert same_acc(got_acc, ref[6 * n:], mutual, n), "accelerations differ from the single-GPU evaluation"
     # every domain only pays for its own share of the interactions (+ the boundary)
     i1 = e1.kd_info()
     tot = sum(r.eng.kd_info().p2p_pairs for r in world.runs)
@@ -169,7 +179,8 @@ def test_sharded_equals_single_gpu(oracle32, n, G, p, kind, mutual):
 
 
 @pytest.mark.parametrize("n,G,p,kind", [(32768, 2, 6, "reference"), (32768, 4, 4, "reference"), (32768, 8, 6, "clumps"), (40000, 8, 5, "uniform"),
-                                        (24576, 2, 3, "clumps"), (1 << 20, 4, 6, "reference"), (1 << 20, 8, 6, "reference"), (32768, 4, 10, "uniform")])
+                                        (24576, 2, 3, "clumps"), (1 << 20, 4, 6, "reference"), (1 << 20, 8, 6, "reference"), (32768, 4, 10, "uniform"),
+                                        (32768, 4, 4, "plane"), (32768, 4, 4, "late")])
 @pytest.mark.parametrize("mutual", MUTUAL)
 def test_let_exchange_equals_single_gpu(oracle32, n, G, p, kind, mutual):
     """the locally-essential-tree exchange (nbco_dist_let_*): every rank receives only the sources its lists name, the result is

@@ -1,25 +1,12 @@
 """The warm median select (k_kdselect.hip: one histogram pass per level around the previous build's pivots).  Bar: the tree -- and
 with it every number downstream -- is the one the cold two-pass select builds, bit for bit; a window that misses the median costs
 a repeated evaluation, never a different result."""
-import os
-
 import numpy as np
 import pytest
 
+from nbutil import warm_engine as _engine
+
 pytestmark = pytest.mark.gpu
-
-
-def _engine(warm, **opts):
-    from coulomb_oscillators_amd import Engine
-    old = os.environ.get("NBCO_SEL_WARM")
-    os.environ["NBCO_SEL_WARM"] = "1" if warm else "0"
-    try:
-        return Engine(**opts)
-    finally:
-        if old is None:
-            del os.environ["NBCO_SEL_WARM"]
-        else:
-            os.environ["NBCO_SEL_WARM"] = old
 
 
 def _state(oracle32, n):

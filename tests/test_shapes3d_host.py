@@ -2,7 +2,10 @@
 
 test_gpu_shapes3d.py compares GPU evaluations of these inputs with the oracles under bounds taken from the oracles.  That is only a
 test where the oracles themselves are sound on the input, where the shape really is degenerate in the way its name says, and where
-the bound is tight enough to tell a wrong evaluation from a right one.  Every one of these is asserted here, per case."""
+the bound is tight enough to tell a wrong evaluation from a right one.  Every one of these is asserted here, per case.
+
+The last part does the same for shapes3d.SELECT_CASES and test_gpu_select_shapes.py: class and floor of every row, the ties and the
+bucket fill at every node that the GPU builds by selection, the build_mode that follows, and the order of cut ties."""
 import numpy as np
 import pytest
 
@@ -20,7 +23,9 @@ def test_the_table_covers_what_it_has_to():
     kd = [c for c in FORCES if c[0] == "kd"]
     oc = [c for c in FORCES if c[0] != "kd"]
     assert len(kd) >= 12 and len(oc) >= 10
-    need = set(S.SHAPES) - {"two_clumps", "offset", "dup64"}
+    # (the shapes added with SELECT_CASES run there only: test_the_select_table_covers_what_it_has_to)
+    need = set(S.SHAPES) - set(S.SELECT_ONLY) - {"two_clumps", "offset", "dup64"}
+    assert len(need) == 10
     assert need <= {c[1] for c in kd}
     assert need <= {c[1] for c in oc}
     assert {c[:4] for c in LISTS} == set(S.LISTS_WHY)
@@ -296,3 +301,133 @@ def test_dup64_lists_are_sound_and_the_forces_are_not(oracle32, oracle64):
         sz = (t["rbound"] - t["lbound"]) ** 2
         sz = np.maximum(sz[m2l[:, 0]].sum(axis=1), sz[m2l[:, 1]].sum(axis=1))
         assert d2.min() > 1e-6 and (d2 > 0.25 * sz).all()
+
+
+# ---- SELECT_CASES: the shapes at sizes whose top levels are built by selection ---------------------------------------------------
+# (max ties, max bucket) over the selection nodes of the fp32 oracle's tree, as select_nodes counts them; "lists" rows too.  quant16:
+# rounding to the grid leaves -0.0 and +0.0 behind, two keys of one coordinate -- 1127 + 1151 particles in the root pivot's bucket.
+SELECT_TIES = {
+    ("gauss", 20480, 4): (1, 1), ("plane", 20480, 4): (1, 1), ("plane_off", 20480, 4): (1, 1), ("line", 20480, 4): (1, 1),
+    ("dup2", 20480, 4): (2, 2), ("dup8", 20480, 4): (8, 8), ("dup16", 20480, 4): (16, 16), ("late", 20480, 4): (1, 6),
+    ("ejected", 20480, 4): (1, 12418), ("zeros", 20480, 4): (4, 8), ("lattice", 19683, 4): (729, 729), ("quant16", 20480, 4): (1979, 2278),
+    ("dup64", 20480, 4): (64, 64), ("dup128", 20480, 4): (128, 128), ("two_clumps", 20480, 4): (1, 1), ("offset", 20480, 4): (3, 3),
+    ("late", 20480, 6): (1, 6), ("dup8", 20480, 6): (8, 8), ("quant2048", 20480, 4): (18, 24),
+    ("late", 65536, 4): (1, 10), ("plane", 65536, 4): (1, 2), ("line", 65536, 4): (1, 1), ("ejected", 65536, 4): (1, 39348),
+}
+# build_mode of a first build (shapes3d.mode_from_nodes); None: the figures leave it open
+SELECT_MODES = {row[:3]: {0} for row in S.SELECT_CASES}
+SELECT_MODES.update({("ejected", 20480, 4): {1}, ("ejected", 65536, 4): {1}, ("dup128", 20480, 4): {1}, ("lattice", 19683, 4): {2},
+                     ("quant16", 20480, 4): {2}})
+
+
+def test_the_select_table_covers_what_it_has_to():
+    """every row has selection levels (three at about 20000 particles, four at 65536) and none of them is in CASES; every shape of
+    the module at p = 4; late and dup8 also at p = 6; late, plane, line at 65536; every "lists" row with a stated reason"""
+    rows = S.SELECT_CASES
+    assert len(set(rows)) == len(rows)
+    assert all(n > 2 * S.SELECT_MIN for _, n, _, _ in rows) and not {("kd",) + r for r in rows} & set(S.CASES)
+    assert {s for s, n, p, _ in rows if p == 4 and n in (20480, 19683)} == set(S.SHAPES)
+    assert all(n == (19683 if s == "lattice" else 20480) or n == 65536 for s, n, _, _ in rows) and 20480 % 128 == 0
+    assert {("late", 20480, 6), ("dup8", 20480, 6), ("late", 65536, 4), ("plane", 65536, 4), ("line", 65536, 4)} <= {r[:3] for r in rows}
+    assert {r[:3] for r in rows if r[3] == "lists"} == set(S.SELECT_LISTS_WHY)
+    assert set(S.SELECT_LISTS_WHY.values()) <= {"nonfinite32", "nonfinite", "lists_differ", "cancellation"}
+    assert set(SELECT_TIES) == set(SELECT_MODES) == {r[:3] for r in rows}
+    assert set(S.SELECT_ONLY) <= {r[0] for r in rows} and not set(S.SELECT_ONLY) & {c[1] for c in S.CASES}
+
+
+@pytest.mark.parametrize("row", S.SELECT_CASES, ids=S.select_id)
+def test_a_select_case_is_what_the_table_says(oracle32, oracle64, row):
+    """"forces": both oracles finite, same tree, permutation and lists, every ordered leaf pair served once, the floor at rounding
+    level (plane_off: 1.35e-5, the cancellation of a plane at z = 0.37 R).  "lists": for the reason SELECT_LISTS_WHY states.  Every
+    row: one selection level per halving above 4096 particles; the tie structure that the GPU module's build_mode expectation is
+    built on, pinned as measured (SELECT_TIES), and the expectation itself (SELECT_MODES)."""
+    shape, n, p, what = row
+    r = S.evaluate(oracle32, oracle64, S.kd_of(row))
+    t = r["t32"]
+    same = S.same_kd_tree(t, r["t64"]) and S.same_kd_lists(t, r["t64"])
+    cover = leaf_pair_cover(t)
+    assert cover.min() == 1 and cover.max() == 1
+    if what == "forces":
+        assert r["finite32"] and r["finite64"] and same
+        assert r["floor"] < (2e-5 if shape == "plane_off" else 3.75e-6)
+    else:
+        why = S.SELECT_LISTS_WHY[row[:3]]
+        if why == "nonfinite":
+            assert not r["finite32"] and not r["finite64"]
+            assert S.same_kd_tree(t, r["t64"])
+        else:
+            assert why == "lists_differ" and r["finite32"] and r["finite64"] and not same
+            assert r["floor"] > 5e-5
+    nodes = S.select_nodes(t, r["buf"][0][t["perm"]])
+    mode = S.expected_mode(oracle32, oracle64, row)
+    print("%s floor %.3e, expected build_mode %s; selection nodes (node, ties, bucket, ties in the left child, bucket +- 1, warm bucket):\n%s"
+          % (S.select_id(row), r["floor"], mode, nodes))
+    levels = 3 if n < 65536 else 4
+    np.testing.assert_array_equal(nodes[:, 0], np.arange((1 << levels) - 1))
+    assert (nodes[:, 1] <= nodes[:, 2]).all() and (nodes[:, 2] <= nodes[:, 4]).all() and (nodes[:, 2] <= nodes[:, 5]).all()
+    assert (1 <= nodes[:, 3]).all() and (nodes[:, 3] <= nodes[:, 1]).all()
+    assert (int(nodes[:, 1].max()), int(nodes[:, 2].max())) == SELECT_TIES[row[:3]]
+    assert mode == SELECT_MODES[row[:3]]
+    if shape in ("dup64", "dup128"):
+        # the two sides of kTieCap: 64 / 128 copies at EVERY selection node, alone in the pivot's bucket and its neighbours, and
+        # every cut behind the tied run (20480 / 2^l is a multiple of 128)
+        k = int(shape[3:])
+        assert (nodes[:, 1:] == k).all()
+    if shape == "ejected":
+        assert nodes[0, 2] == (12418 if n == 20480 else 39348)          # the ball is a few buckets of the root's box
+    if shape in ("dup2", "dup8", "dup16"):
+        assert (nodes[:, 1] == int(shape[3:])).all() and (nodes[:, 3] == nodes[:, 1]).all()
+    if shape == "lattice":
+        assert (nodes[:, 3] < nodes[:, 1]).all()          # every cut inside a tied plane
+
+
+@pytest.mark.parametrize("row", S.SELECT_CASES, ids=S.select_id)
+def test_cut_ties_follow_the_sort_chain(oracle32, oracle64, row):
+    """Wherever a cut of a selection node falls inside a run of equal keys, the tied particles of the oracle's left child are the
+    first ones by (c[a2], c[a3], original index) -- the order the GPU's exact resolver is written to.  quant2048 is the row on which
+    the SECOND key decides while the resolver is in charge (a dozen ties per node, build_mode 0): at two of its nodes the order
+    without c[a2] picks other particles.  The other rows with cut ties either tie in all keys but the index (offset) or end in the
+    sorting build (lattice, quant16)."""
+    r = S.evaluate(oracle32, oracle64, S.kd_of(row))
+    rows = S.tie_orders(r["t32"], r["buf"][0][r["t32"]["perm"]])
+    print(S.select_id(row), rows)
+    assert all(chain for _, chain, _ in rows)
+    assert bool(rows) == (row[0] in ("lattice", "quant16", "offset", "quant2048"))
+    if row[0] == "quant2048":
+        assert [v for v, _, blind in rows if not blind] == [4, 5]
+        assert S.expected_mode(oracle32, oracle64, row) == {0}
+
+
+def test_zeros_puts_the_root_cut_between_the_two_zeros(oracle32, oracle64):
+    """the root pivot is -0.0 and the right child begins at +0.0: the bounds of the root's children on the split axis are the two
+    zeros, told apart by their bits only; four particles on each, all eight in one bucket of the linear key"""
+    r = S.evaluate(oracle32, oracle64, S.kd_of(("zeros", 20480, 4, "forces")))
+    t = r["t32"]
+    a = int(t["splitdim"][0])
+    ext = r["buf"][0].max(axis=0) - r["buf"][0].min(axis=0)
+    assert a == int(np.argmax(ext))
+    assert t["rbound"][1].view(np.uint32)[a] == 0x80000000
+    assert t["lbound"][2].view(np.uint32)[a] == 0
+    x = r["buf"][0][:, a]
+    bits = x.view(np.uint32)
+    assert (bits == 0x80000000).sum() == S.ZERO_BLOCK and (bits == 0).sum() == S.ZERO_BLOCK
+    assert (x < 0).sum() == 20480 // 2 - S.ZERO_BLOCK and (x > 0).sum() == 20480 // 2 - S.ZERO_BLOCK
+    np.testing.assert_array_equal(S.select_nodes(t, r["buf"][0][t["perm"]])[0, 1:5], [S.ZERO_BLOCK, 2 * S.ZERO_BLOCK, S.ZERO_BLOCK, 2 * S.ZERO_BLOCK])
+    np.testing.assert_array_equal(r["buf"][1], oracle32.init_reference(20480)[1])
+
+
+def test_the_bucket_restatement_against_exact_arithmetic():
+    """lin_bucket rounds where k_kdselect.hip's lin_key rounds: against the same expression in exact rational arithmetic it is never
+    more than one bucket off, is monotone, and sends the box faces to the first and the last bucket"""
+    from fractions import Fraction
+    rng = np.random.default_rng(3)
+    lo, hi = np.float32(-0.731), np.float32(1.9)
+    x = np.sort(rng.uniform(lo, hi, 2000).astype(np.float32))
+    b = S.lin_bucket(x, lo, hi).astype(np.int64)
+    assert (np.diff(b) >= 0).all()
+    exact = np.array([int((Fraction(float(v)) - Fraction(float(lo))) / (Fraction(float(hi)) - Fraction(float(lo))) * 4294967040) >> 10 for v in x])
+    assert np.abs(b - exact).max() <= 1
+    assert S.lin_bucket(np.array([lo, hi]), lo, hi).tolist() == [0, 4294967040 >> 10]
+    assert S.lin_bucket(np.array([lo, hi]), lo, lo).tolist() == [0, 0]          # a box of zero extent: one bucket
+    np.testing.assert_array_equal(S.ordered_key(np.array([-1.0, -0.0, 0.0, 1.0], dtype=np.float32)),
+                                  np.array([0x407FFFFF, 0x7FFFFFFF, 0x80000000, 0xBF800000], dtype=np.uint32))
