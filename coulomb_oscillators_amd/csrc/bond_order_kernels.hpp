@@ -1,0 +1,248 @@
+// bond_order_kernels.hpp -- part of k_reduce.hip (the exact forms, with NBCO_BOND_EXACT defined) and of k_fmm_kd.hip (the tree walk,
+// with NBCO_BOND_WALK defined): included there behind pair_stat_kernels.hpp, inside that file's anonymous namespace
+// Bond-orientational order: per particle the number of neighbours and the Steinhardt q4, q6 (2-D: |psi4|, |psi6|), and a summary
+// (no include guard on purpose: this is a section of those files, not a header)
+// The neighbour rule of include/nbco.h is the pair rule of the pair statistics (pair_r2, contraction off) with 0 < r2 < R2; what a
+// bond contributes comes from bond_order.hpp.  A particle's sums stay in the registers of the lane that owns it from the first
+// neighbour to the last, in the order the kernel meets them: no atomics, and a second call adds in the same order.
+// The summary: every wave of 64 consecutive particles (of the caller's order in the exact forms, of the tree order in the walk) adds
+// its lanes' sums with a butterfly of fixed shape and writes one record of kBondRec slots; one workgroup then adds the records
+// (bond_reduce_kernel, compiled with the exact forms and launched for both by bond_summary_finish).
+
+__device__ inline double bond_wave_sum(double v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+__device__ inline long long bond_wave_sum(long long v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
+__device__ inline int bond_wave_max(int v) { for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o); v = t > v ? t : v; } return v; }
+
+// The end of a lane's particle: q from the sums, nb and q to row `dst` of the outputs that are given (dst < 0: the lane has no
+// particle, or no row to write to), and with SUM the wave's record (wave-uniform control flow; rec points at this wave's record).
+template <int D, bool SUM>
+__device__ inline void bond_finish(bool valid, long long dst, int nb, const double (&S)[D == 3 ? kBondSums3 : kBondSums2], int *__restrict__ nb_out,
+                                   double *__restrict__ q_out, double *__restrict__ rec)
+{
+	constexpr int NS = D == 3 ? kBondSums3 : kBondSums2;
+	double q[2];
+	bond_q<D>(S, nb, q);
+	if (valid && dst >= 0)
+	{
+		if (nb_out) nb_out[dst] = nb;
+		if (q_out) { q_out[2 * dst] = q[0]; q_out[2 * dst + 1] = q[1]; }
+	}
+	if (SUM)
+	{
+		const bool first = (threadIdx.x & 63) == 0;
+#pragma unroll
+		for (int m = 0; m < NS; ++m)
+		{
+			const double v = bond_wave_sum(valid ? S[m] : 0.0);
+			if (first) rec[m] = v;
+		}
+		if (first)
+			for (int m = NS; m < kBondRecQ; ++m) rec[m] = 0.0;
+#pragma unroll
+		for (int l = 0; l < 2; ++l)
+		{
+			const double v = bond_wave_sum(valid ? q[l] : 0.0);
+			if (first) rec[kBondRecQ + l] = v;
+		}
+		const long long bonds = bond_wave_sum(valid ? (long long)nb : 0ll), isolated = bond_wave_sum(valid && nb == 0 ? 1ll : 0ll);
+		const int top = bond_wave_max(valid ? nb : 0);
+		if (first)
+		{
+			rec[kBondRecBonds] = __longlong_as_double(bonds);
+			rec[kBondRecIsolated] = __longlong_as_double(isolated);
+			rec[kBondRecMax] = __longlong_as_double((long long)top);
+		}
+	}
+}
+
+#ifdef NBCO_BOND_EXACT
+// The records of all waves -> out[kBondRec], by one workgroup: thread (g, slot) adds the records of the g-th of kBondGroups contiguous
+// ranges in record order, then the first kBondRec threads add the groups in group order.  Slots below kBondRecBonds are doubles,
+// the others 64-bit integers (two sums and a maximum).
+constexpr int kBondGroups = 32, kBondSlots = 32;
+static_assert(kBondRec <= kBondSlots, "a slot per thread of a group");
+__global__ __launch_bounds__(kBondGroups * kBondSlots) void bond_reduce_kernel(const double *__restrict__ rec, long long records, double *__restrict__ out)
+{
+	__shared__ double sh[kBondGroups][kBondSlots];
+	const int slot = threadIdx.x % kBondSlots, g = threadIdx.x / kBondSlots;
+	const long long per = (records + kBondGroups - 1) / kBondGroups;
+	const long long lo = g * per < records ? g * per : records, hi = lo + per < records ? lo + per : records;
+	if (slot < kBondRecBonds)
+	{
+		double s = 0.0;
+		for (long long r = lo; r < hi; ++r) s += rec[r * kBondRec + slot];
+		sh[g][slot] = s;
+	}
+	else if (slot < kBondRec)
+	{
+		long long s = 0;
+		for (long long r = lo; r < hi; ++r)
+		{
+			const long long v = __double_as_longlong(rec[r * kBondRec + slot]);
+			s = slot == kBondRecMax ? (v > s ? v : s) : s + v;
+		}
+		sh[g][slot] = __longlong_as_double(s);
+	}
+	__syncthreads();
+	if (threadIdx.x >= kBondRec) return;
+	if (slot < kBondRecBonds)
+	{
+		double s = 0.0;
+		for (int k = 0; k < kBondGroups; ++k) s += sh[k][slot];
+		out[slot] = s;
+	}
+	else
+	{
+		long long s = 0;
+		for (int k = 0; k < kBondGroups; ++k)
+		{
+			const long long v = __double_as_longlong(sh[k][slot]);
+			s = slot == kBondRecMax ? (v > s ? v : s) : s + v;
+		}
+		out[slot] = __longlong_as_double(s);
+	}
+}
+
+// ---- exact form: all pairs ---------------------------------------------------------------------------------------------------------
+// The tiling of pair_hist_kernel with the full square instead of the triangle: a workgroup keeps the particles of tile I in
+// registers, one per thread, and takes EVERY source tile through LDS, widened once when it is staged, so that a target meets all its
+// neighbours itself, in index order, and nothing has to be handed to the other end of a pair.  The particle itself and a coincident
+// one fall out through r2 > 0.  A pair outside costs the subtractions, r2, two compares and the wave's branch on the ballot; the
+// harmonics are formed only where a lane of the wave has a neighbour.  One template covers T = float, D = 3 and T = double, D = 2.
+template <class T, int D, bool SUM>
+__global__ __launch_bounds__(kBlock) void bond_exact_kernel(const T *__restrict__ p, long long n, double R2, int *__restrict__ nb_out, double *__restrict__ q_out,
+                                                             double *__restrict__ rec)
+{
+	__shared__ double src[3][kBlock];
+	const int tid = threadIdx.x;
+	const long long nt = (n + kBlock - 1) / kBlock, i = (long long)blockIdx.x * kBlock + tid;
+	// a thread without a particle carries NaNs: nobody is its neighbour
+	double x0 = __longlong_as_double(0x7FF8000000000000ll), x1 = x0, x2 = x0;
+	if (i < n)
+	{
+		const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[i];
+		x0 = (double)q.v[0]; x1 = (double)q.v[1];
+		if (D == 3) x2 = (double)q.v[D - 1];
+	}
+	double S[D == 3 ? kBondSums3 : kBondSums2] = {};
+	int nb = 0;
+	for (long long J = 0; J < nt; ++J)
+	{
+		__syncthreads();
+		const long long j = J * kBlock + tid;
+		if (j < n)
+		{
+			const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[j];
+			src[0][tid] = (double)q.v[0]; src[1][tid] = (double)q.v[1];
+			if (D == 3) src[2][tid] = (double)q.v[D - 1];
+		}
+		__syncthreads();
+		const int cnt = (int)(n - J * kBlock < kBlock ? n - J * kBlock : kBlock);
+		for (int u = 0; u < cnt; ++u)
+		{
+			const double dx = src[0][u] - x0, dy = src[1][u] - x1, dz = D == 3 ? src[2][u] - x2 : 0.0;
+			const double r2 = D == 3 ? pair_r2(dx, dy, dz) : pair_r2(dx, dy);
+			const bool in = 0.0 < r2 && r2 < R2;
+			if (__ballot(in) == 0) continue;
+			if (in)
+			{
+				++nb;
+				bond_add<D>(dx, dy, dz, r2, S);
+			}
+		}
+	}
+	// (a wave whose first thread has no particle has none at all: it writes no record)
+	const long long first = i - (tid & 63);
+	if (SUM && first >= n) return;
+	bond_finish<D, SUM>(i < n, i < n ? i : -1, nb, S, nb_out, q_out, SUM ? rec + (first >> 6) * kBondRec : nullptr);
+}
+#endif   // NBCO_BOND_EXACT
+
+#ifdef NBCO_BOND_WALK
+// ---- tree form: the walk of kd_pair_walk_kernel with another visitor ------------------------------------------------------------------
+// The control flow is that kernel's, unchanged: a wave takes 64 consecutive particles of the tree order, goes through the implicit
+// tree without a stack, opens a node iff the box of the node is within R2 (1 + 1e-9) of a lane's particle, and stages a leaf's
+// particles in its LDS tile 64 at a time.  The tree decides only what is skipped: a lane meets exactly its neighbours, in the order
+// of the leaves.  The particle itself and a coincident one fall out through r2 > 0, so the tree position is not asked.  nb and q go
+// through the build's unsort map into the caller's order.  A workgroup is kPairWalkWaves waves of kPairWalkChunks chunks each.
+template <bool SUM>
+__global__ __launch_bounds__(64 * kPairWalkWaves) void kd_bond_walk_kernel(const float *__restrict__ lbound, const float *__restrict__ rbound,
+                                                                            const int *__restrict__ mult, const int *__restrict__ index,
+                                                                            const float4 *__restrict__ pos, const int *__restrict__ unsort, int ntot, long long n,
+                                                                            double R2, double R2m, int *__restrict__ nb_out, double *__restrict__ q_out,
+                                                                            double *__restrict__ rec)
+{
+	__shared__ double tile[kPairWalkWaves][3][64];
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	for (int q = 0; q < kPairWalkChunks; ++q)
+	{
+		const long long s0 = (((long long)blockIdx.x * kPairWalkWaves + w) * kPairWalkChunks + q) * 64;
+		if (s0 >= n) break;   // (the whole wave)
+		const long long s = s0 + lane;
+		const bool valid = s < n;
+		const float4 me = pos[valid ? s : n - 1];
+		const double X = (double)me.x, Y = (double)me.y, Z = (double)me.z;
+		double S[kBondSums3] = {};
+		int nb = 0;
+		int k = 0;
+		for (;;)
+		{
+			k = __builtin_amdgcn_readfirstlane(k);   // (uniform by construction: it moves on ballots only)
+			const double gx = fmax(fmax((double)lbound[3 * k] - X, 0.0), X - (double)rbound[3 * k]);
+			const double gy = fmax(fmax((double)lbound[3 * k + 1] - Y, 0.0), Y - (double)rbound[3 * k + 1]);
+			const double gz = fmax(fmax((double)lbound[3 * k + 2] - Z, 0.0), Z - (double)rbound[3 * k + 2]);
+			const bool need = valid && gx * gx + gy * gy + gz * gz <= R2m;
+			const bool any_need = __ballot(need) != 0;
+			const bool leaf = 2 * k + 1 >= ntot;
+			if (leaf && any_need)
+			{
+				// (a leaf's range lies inside [0, n) by the build; the clamp keeps a damaged tree from reading past the array, and the
+				// checked build counts what the clamp would have hidden)
+				const long long i0 = index[k];
+				long long ml = mult[k];
+				(void)NBCO_CHECKED_OK(i0 >= 0 && ml >= 0 && i0 + ml <= n, NBCO_CHK_WALK);
+				if (i0 < 0 || i0 >= n) ml = 0;
+				else if (ml > n - i0) ml = n - i0;
+				for (long long j0 = 0; j0 < ml; j0 += 64)
+				{
+					wave_lds_sync();
+					if (j0 + lane < ml)
+					{
+						const float4 v = pos[i0 + j0 + lane];
+						tile[w][0][lane] = (double)v.x; tile[w][1][lane] = (double)v.y; tile[w][2][lane] = (double)v.z;
+					}
+					wave_lds_sync();
+					const int cnt = (int)(ml - j0 < 64 ? ml - j0 : 64);
+					for (int u = 0; u < cnt; ++u)
+					{
+						const double dx = tile[w][0][u] - X, dy = tile[w][1][u] - Y, dz = tile[w][2][u] - Z;
+						const double r2 = pair_r2(dx, dy, dz);
+						const bool in = need && 0.0 < r2 && r2 < R2;
+						if (__ballot(in) == 0) continue;
+						if (in)
+						{
+							++nb;
+							bond_add<3>(dx, dy, dz, r2, S);
+						}
+					}
+				}
+			}
+			if (!leaf && any_need) k = 2 * k + 1;
+			else
+			{
+				while (k != 0 && (k & 1) == 0) k = (k - 1) >> 1;   // up while a right child
+				if (k == 0) break;
+				k = k + 1;   // the sibling of a left child
+			}
+		}
+		long long dst = -1;
+		if (valid)
+		{
+			dst = unsort[s];   // (a permutation of [0, n) by the build; the check keeps a damaged map from writing outside the outputs)
+			(void)NBCO_CHECKED_OK(dst >= 0 && dst < n, NBCO_CHK_WALK);
+			if (dst >= n) dst = -1;
+		}
+		bond_finish<3, SUM>(valid, dst, nb, S, nb_out, q_out, SUM ? rec + (s0 >> 6) * kBondRec : nullptr);
+	}
+}
+#endif   // NBCO_BOND_WALK

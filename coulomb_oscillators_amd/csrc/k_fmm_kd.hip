@@ -34,6 +34,7 @@
 #include "host_util.hpp"
 #include "helix.hpp"
 #include "bath.hpp"
+#include "bond_order.hpp"
 #include <type_traits>
 #include <chrono>
 #include <cmath>
@@ -691,6 +692,9 @@ static int kd_finish_order(nbco_ctx *c, float *p, long long n, KdStepLink *link)
 #define NBCO_PAIR_STAT_WALK
 #include "pair_stat_kernels.hpp"   // pair statistics: the pair rule, the range-limited walk, the count of the pairs outside
 #undef NBCO_PAIR_STAT_WALK
+#define NBCO_BOND_WALK
+#include "bond_order_kernels.hpp"   // bond-orientational order: the same walk with the harmonics of the bonds at the leaves, the wave records of the summary
+#undef NBCO_BOND_WALK
 } // namespace
 
 // sum over the own particles of phi_i / 2 (the caller multiplies by param[0] = xi / N)
@@ -820,14 +824,14 @@ int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long 
 	return kd_probe_walk(c, probe_src(c, c->kd, c->pos4.as<float4>(), n), t, m, param, a, psi);
 }
 
-// nbco_pair_hist_tree, on the private context: the tree over x[0..n) -- kd_build only: no upward pass, no traversal, no lists -- and
-// the range-limited walk over its boxes.  nn2 is written for every particle; the counts are cleared first and closed with the pairs outside.
-int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts, double *nn2)
+// The tree of nbco_pair_hist_tree and nbco_bond_order_tree, on the private context, over x[0..n) -- kd_build only: no upward pass, no
+// traversal, no lists.
+static int kd_build_for_walk(nbco_ctx *c, float *x, long long n)
 {
 	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
 	// The build finishes every leaf inside one workgroup's LDS slice of kSubS particles.  A tree_L that leaves more than that per
 	// leaf overruns the slice, and the unsort map that comes out of it is not a permutation: refused here, before anything is
-	// launched, because this walk scatters nn2 through that map.
+	// launched, because the walks scatter their results through that map.
 	if (((n + (1LL << L) - 1) >> L) > kSubS)
 		return c->fail(NBCO_ERR_UNSUPPORTED, "tree_L leaves more than " + std::to_string(kSubS) + " particles per leaf: the kd-tree build cannot hold them");
 	c->last_eval.valid = false;   // the lists of an earlier evaluation belong to another tree
@@ -836,6 +840,14 @@ int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, un
 	c->tree_valid = true;   // (the boxes in the tree arrays are this build's: the next build of the same shape may select around them)
 	c->tree_n = n;
 	c->tree_order = c->kd.order;
+	return NBCO_OK;
+}
+
+// nbco_pair_hist_tree: that tree and the range-limited walk over its boxes.  nn2 is written for every particle; the counts are cleared
+// first and closed with the pairs outside.
+int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts, double *nn2)
+{
+	NBCO_TRY(kd_build_for_walk(c, x, n));
 	if (counts) NBCO_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * ((size_t)pb.bins + 1), c->stream));
 	// the LDS histogram while its 32-bit counters cannot wrap (a workgroup bins fewer than kPairWgParticles * n pairs) and the bins fit
 	const bool lds = pb.bins <= kPairLdsBins && (unsigned long long)kPairWgParticles * (unsigned long long)n < (1ull << 32);
@@ -857,6 +869,30 @@ int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, un
 		hipLaunchKernelGGL(pair_outside_kernel, dim3(1), dim3(kBlock), 0, c->stream, counts, pb.bins, (unsigned long long)n * (unsigned long long)(n - 1) / 2ull);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
+}
+
+// nbco_bond_order_tree: that tree and the same walk with the bonds' harmonics at the leaves; nb and q are written for every particle,
+// the summary from one record per wave (the reduction scratch of the private context)
+int kd_bond_order_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb, double *q, nbco_bond_summary *sum_host)
+{
+	NBCO_TRY(kd_build_for_walk(c, x, n));
+	const long long records = (n + 63) / 64;
+	double *rec = nullptr;
+	if (sum_host)
+	{
+		NBCO_TRY(c->reserve(c->part, sizeof(double) * kBondRec * (size_t)records));
+		rec = c->part.as<double>();
+	}
+	const dim3 grid((unsigned)((n + kPairWgParticles - 1) / kPairWgParticles)), block(64 * kPairWalkWaves);
+	const KdTreeDev &k = c->kd;
+	const double R2m = R2 * (1.0 + 1e-9);
+	with_flag(sum_host != nullptr, [&](auto ws) {
+		hipLaunchKernelGGL((kd_bond_walk_kernel<decltype(ws)::value>), grid, block, 0, c->stream, (const float *)k.lbound, (const float *)k.rbound,
+		                   (const int *)k.mult, (const int *)k.index, (const float4 *)c->pos4.as<float4>(), (const int *)c->unsort.as<int>(), k.ntot, n, R2, R2m,
+		                   nb, q, rec);
+	});
+	NBCO_HIP(hipGetLastError());
+	return sum_host ? bond_summary_finish(c, rec, records, n, 3, sum_host) : NBCO_OK;
 }
 
 // kd_fields has returned `rc`: twice the room for the lists (the caller's arrays are untouched), or reaction records sized from the

@@ -5,6 +5,7 @@
 // one partial per block -> last stage in a single block (deterministic, no float atomics).
 #include "nbco_internal.hpp"
 #include "host_util.hpp"
+#include "bond_order.hpp"
 #include <algorithm>
 #include <cfloat>
 
@@ -181,6 +182,9 @@ static int grid_for(long long n)
 #define NBCO_PAIR_STAT_EXACT
 #include "pair_stat_kernels.hpp"   // pair statistics: the pair rule, the all-pairs kernel, the count of the pairs outside
 #undef NBCO_PAIR_STAT_EXACT
+#define NBCO_BOND_EXACT
+#include "bond_order_kernels.hpp"   // bond-orientational order: the all-pairs kernel, the wave records of the summary and their sum
+#undef NBCO_BOND_EXACT
 
 } // namespace
 
@@ -474,6 +478,48 @@ int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const Pai
 		hipLaunchKernelGGL(pair_outside_kernel, dim3(1), dim3(kBlock), 0, c->stream, counts, pb.bins, (unsigned long long)n * (unsigned long long)(n - 1) / 2ull);
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
+}
+
+// ---- bond-orientational order, exact forms (bond_order_kernels.hpp) ---------------------------------
+// the summary of a call from the wave records in `rec`: one workgroup adds them into c->small (doubles from kBondOut on), the host
+// derives the means and the global Q.  Synchronises.
+constexpr int kBondOut = 256;
+int bond_summary_finish(nbco_ctx *c, const double *rec, long long records, long long n, int dim, nbco_bond_summary *sum_host)
+{
+	double *out = c->small.as<double>() + kBondOut;
+	hipLaunchKernelGGL(bond_reduce_kernel, dim3(1), dim3(kBondGroups * kBondSlots), 0, c->stream, rec, records, out);
+	NBCO_HIP(hipGetLastError());
+	double h[kBondRec];
+	NBCO_HIP(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	double S[kBondSums3], qsum[2] = {h[kBondRecQ], h[kBondRecQ + 1]};
+	long long ints[3];
+	memcpy(S, h, sizeof S);
+	memcpy(ints, h + kBondRecBonds, sizeof ints);
+	nbco_bond_summary s;
+	memset(&s, 0, sizeof s);
+	bond_summary_fill(S, qsum, ints[0], ints[1], ints[2], n, dim, s);
+	*sum_host = s;
+	return NBCO_OK;
+}
+
+int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R2, int *nb, double *q, nbco_bond_summary *sum_host)
+{
+	const long long nt = (n + kBlock - 1) / kBlock, records = (n + 63) / 64;
+	double *rec = nullptr;
+	if (sum_host)
+	{
+		NBCO_TRY(c->reserve(c->part, sizeof(double) * kBondRec * (size_t)records));
+		rec = c->part.as<double>();
+	}
+	const dim3 grid((unsigned)nt), block(kBlock);
+	with_flag(sum_host != nullptr, [&](auto ws) {
+		constexpr bool SUM = decltype(ws)::value;
+		if (dim == 3) hipLaunchKernelGGL((bond_exact_kernel<float, 3, SUM>), grid, block, 0, c->stream, (const float *)p, n, R2, nb, q, rec);
+		else hipLaunchKernelGGL((bond_exact_kernel<double, 2, SUM>), grid, block, 0, c->stream, (const double *)p, n, R2, nb, q, rec);
+	});
+	NBCO_HIP(hipGetLastError());
+	return sum_host ? bond_summary_finish(c, rec, records, n, dim, sum_host) : NBCO_OK;
 }
 
 // ---- aperture (aperture_kernels.hpp) -------------------------------------------------------------

@@ -2,9 +2,11 @@
 // of compute_force (integrator.cuh:22-28 over main3.cu:47-69) and thin wrappers over the launchers.
 // The symplectic integrators (integrator.cuh:32-167) are nbco_integrate.hip.
 #include "nbco_internal.hpp"
+#include "bond_order.hpp"
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <cmath>
 #include <new>
 #include <random>
@@ -750,6 +752,62 @@ int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, doub
 	};
 	const int rc = pass();
 	if (rc != NBCO_OK) return c->fail(rc, "nbco_pair_hist_tree: " + k->err);
+	return maybe_sync(c);
+}
+
+// ---- bond-orientational order ------------------------------------------------------------------
+int nbco_bond_harmonics(const double *u3, double *y4, double *y6)
+{
+	if (!u3 || !y4 || !y6) return NBCO_ERR_ARG;
+	if (!std::isfinite(u3[0]) || !std::isfinite(u3[1]) || !std::isfinite(u3[2])) return NBCO_ERR_ARG;
+	double a[9], b[13];
+	bond_harmonics(u3[0], u3[1], u3[2], a, b);
+	memcpy(y4, a, sizeof a);
+	memcpy(y6, b, sizeof b);
+	return NBCO_OK;
+}
+
+// what all three calls refuse before any launch
+static int bond_args(nbco_ctx *c, const char *who, bool tree, const void *p, long long n, double rmax, const void *nb_dev, const void *q_dev, const void *sum_host)
+{
+	if (!c) return NBCO_ERR_ARG;
+	const std::string w(who);
+	if (!p) return c->fail(NBCO_ERR_ARG, w + ": null pointer");
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, w + ": n must be positive");
+	if (!nb_dev && !q_dev && !sum_host) return c->fail(NBCO_ERR_ARG, w + ": all outputs are NULL");
+	if (!std::isfinite(rmax) || !(rmax > 0.0)) return c->fail(NBCO_ERR_ARG, w + ": rmax must be finite and positive");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit particle indices");
+	if (tree && n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit tree indices");
+	return NBCO_OK;
+}
+
+int nbco_bond_order(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host)
+{
+	NBCO_TRY(bond_args(c, "nbco_bond_order", false, p, n, rmax, nb_dev, q_dev, sum_host));
+	NBCO_TRY(launch_bond_order(c, p, 3, n, rmax * rmax, nb_dev, q_dev, sum_host));
+	return maybe_sync(c);
+}
+
+int nbco_2d_bond_order(nbco_ctx *c, const double *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host)
+{
+	NBCO_TRY(bond_args(c, "nbco_2d_bond_order", false, p, n, rmax, nb_dev, q_dev, sum_host));
+	NBCO_TRY(launch_bond_order(c, p, 2, n, rmax * rmax, nb_dev, q_dev, sum_host));
+	return maybe_sync(c);
+}
+
+int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host)
+{
+	NBCO_TRY(bond_args(c, "nbco_bond_order_tree", true, p, n, rmax, nb_dev, q_dev, sum_host));
+	nbco_ctx *k;
+	NBCO_TRY(private_child(c, "nbco_bond_order_tree", k));
+	auto pass = [&]() -> int {
+		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
+		float *x = k->pot_xa.as<float>();
+		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
+		return kd_bond_order_tree(k, x, n, rmax * rmax, nb_dev, q_dev, sum_host);
+	};
+	const int rc = pass();
+	if (rc != NBCO_OK) return c->fail(rc, "nbco_bond_order_tree: " + k->err);
 	return maybe_sync(c);
 }
 

@@ -407,6 +407,10 @@ struct PairBins
 	double R2, width, inv_width;   // R2 = rmax * rmax, width = rmax / bins; inv_width only seeds the bin search
 };
 int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
+// bond-orientational order (bond_order_kernels.hpp), exact forms; R2 = rmax * rmax.  With sum_host the call synchronises.
+int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R2, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
+// the wave records of a bond-order call (`records` of them, on the device) -> *sum_host.  Synchronises.
+int bond_summary_finish(nbco_ctx *c, const double *rec, long long records, long long n, int dim, nbco_bond_summary *sum_host);
 // aperture (aperture_kernels.hpp): the rule of a call, formed once on the host by include/nbco.h: w[a] = 1.0 / half[a]
 struct ApRule
 {
@@ -421,6 +425,7 @@ int launch_aperture_compact(nbco_ctx *c, void *buf, int dim, long long n, long l
                             const int *order_in, int *order_out);
 // k_fmm_kd.hip
 int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
+int kd_bond_order_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);
 int kd_copy_out(nbco_ctx *c, int which, void *host_dst, long long host_bytes);
 int kd_count_pairs(nbco_ctx *c, long long *out);

@@ -100,6 +100,12 @@ class Bath(C.Structure):
     _fields_ = [("gamma", C.c_double * 3), ("kT", C.c_double * 3), ("seed", C.c_ulonglong)]
 
 
+class BondSummary(C.Structure):
+    """nbco_bond_summary (include/nbco.h)"""
+    _fields_ = [("n", C.c_longlong), ("bonds", C.c_longlong), ("isolated", C.c_longlong), ("nb_max", C.c_int), ("dim", C.c_int),
+                ("q_mean", C.c_double * 2), ("Q", C.c_double * 2)]
+
+
 ERR_CAPACITY = 3              # NBCO_ERR_CAPACITY
 
 COLL_DONE, COLL_ALLREDUCE_MIN_I32, COLL_ALLREDUCE_SUM_I32, COLL_ALLGATHER, COLL_ALLTOALL = range(5)
@@ -232,6 +238,10 @@ def _load():
         "nbco_pair_hist": [P, P, LL, I, D, P, P],
         "nbco_pair_hist_tree": [P, P, LL, I, D, P, P],
         "nbco_2d_pair_hist": [P, P, LL, I, D, P, P],
+        "nbco_bond_harmonics": [C.POINTER(D), C.POINTER(D), C.POINTER(D)],
+        "nbco_bond_order": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
+        "nbco_bond_order_tree": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
+        "nbco_2d_bond_order": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
         "nbco_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
         "nbco_aperture_apply": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL), P, P, LL],
         "nbco_2d_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
@@ -325,6 +335,19 @@ def bath_coeffs(gamma, kT, s):
     if rc != 0:
         raise EngineError("nbco_bath_coeffs failed with status %d" % rc, status=rc)
     return np.array(c1[:], dtype=np.float64), np.array(c2[:], dtype=np.float64)
+
+
+def bond_harmonics(u):
+    """(y4, y6), float64[9] and float64[13]: the orthonormal real spherical harmonics of degree 4 and 6 at the unit vector u, as the
+    bond-order kernels form them (nbco_bond_harmonics, include/nbco.h): entry 0 is m = 0, 2m - 1 and 2m the cosine and sine parts
+    of m.  u is taken as it is.  Host only, needs no GPU; the one place they are formed."""
+    import numpy as np
+    u3 = (C.c_double * 3)(*[float(t) for t in u])
+    y4, y6 = (C.c_double * 9)(), (C.c_double * 13)()
+    rc = _load().nbco_bond_harmonics(u3, y4, y6)
+    if rc != 0:
+        raise EngineError("nbco_bond_harmonics failed with status %d" % rc, status=rc)
+    return np.array(y4[:], dtype=np.float64), np.array(y6[:], dtype=np.float64)
 
 
 def default_opts(**kw):
@@ -692,6 +715,40 @@ class Engine:
     def pair_hist_2d(self, p, n, bins, rmax, counts=None, nn2=None):
         """the exact form for the 2-D fp64 positions (xy pairs; nbco_2d_pair_hist)"""
         return self._pair_hist(self.lib.nbco_2d_pair_hist, p, n, bins, rmax, counts, nn2)
+
+    # ---- bond-orientational order -----------------------------------------------------------------
+    def _bond_order(self, fn, p, n, rmax, nb, q, summary):
+        room = max(int(n), 0)   # (the library refuses a bad n; nothing is sized by it)
+        if nb is None:
+            nb = self.torch.empty(room, dtype=self.torch.int32, device=p.device)
+        elif nb is False:
+            nb = None
+        if q is None:
+            q = self.torch.empty((room, 2), dtype=self.torch.float64, device=p.device)
+        elif q is False:
+            q = None
+        out = BondSummary() if summary else None
+        self._chk(fn(self.ctx, _ptr(p), n, float(rmax), _ptr(nb), _ptr(q), C.byref(out) if summary else None))
+        return nb, q, out
+
+    def bond_order(self, p, n, rmax, nb=None, q=None, summary=True):
+        """bond-orientational order of the n positions p (float32 xyz triplets; the head of a state works), all pairs, exact
+        (nbco_bond_order).  j is a neighbour of i iff 0 < r2 < rmax^2 in fp64 over the widened coordinates.  Returns (nb, q, summary):
+        nb an int32 device tensor of n neighbour counts, q a float64 device tensor (n, 2) of the Steinhardt q4 and q6 (0 where
+        nb = 0), both in the caller's order, summary a BondSummary (bonds, isolated, nb_max, the means of q over the particles with
+        neighbours and the global Q4, Q6).  nb and q are allocated if None and overwritten if given; False asks for none of that
+        output, summary=False for no summary (the call then does not synchronise).  p is not modified."""
+        return self._bond_order(self.lib.nbco_bond_order, p, n, rmax, nb, q, summary)
+
+    def bond_order_tree(self, p, n, rmax, nb=None, q=None, summary=True):
+        """the same from a range-limited walk over a kd-tree of its own on a private context (nbco_bond_order_tree): the cost follows the
+        number of bonds, not n^2.  nb is equal integer for integer, q and the summary to rounding (the neighbours are met in another
+        order).  Valid in any state of this engine, which it leaves untouched."""
+        return self._bond_order(self.lib.nbco_bond_order_tree, p, n, rmax, nb, q, summary)
+
+    def bond_order_2d(self, p, n, rmax, nb=None, q=None, summary=True):
+        """the exact form for the 2-D fp64 positions (xy pairs; nbco_2d_bond_order): q holds |psi4| and |psi6|, the hexatic order"""
+        return self._bond_order(self.lib.nbco_2d_bond_order, p, n, rmax, nb, q, summary)
 
     # ---- aperture ---------------------------------------------------------------------------------
     @staticmethod

@@ -85,12 +85,18 @@ const char *kHelp =
     "                    neighbour below rmax (inf where there is none).  From a range-limited kd-tree walk of its own\n"
     "                    (nbco_pair_hist_tree; with -cpu: all pairs on the host, the same rule, the same bytes).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -bonds <rmax>     At every snapshot write the bond-orientational order of the positions to <output>/bonds<iter>_<ds>.bin: n int32 -- per\n"
+    "                    particle, in the snapshot's order, the number of neighbours nb closer than rmax -- then n x 2 doubles: the Steinhardt\n"
+    "                    order parameters q4 and q6 of the particle's bonds (0 where nb = 0), and append 'iter bonds isolated nb_max q4_mean\n"
+    "                    q6_mean Q4 Q6' to <output>/bonds.txt.  From a range-limited kd-tree walk of its own (nbco_bond_order_tree; with -cpu:\n"
+    "                    all pairs on the host, the same neighbour rule and harmonics: the same nb, q to rounding).\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -aperture <ellipsoid|box> <hx> <hy> <hz>   At every snapshot iteration, after the step and before the snapshot, drop the particles\n"
     "                    outside the aperture with these half axes ('inf' opens an axis: pipes, slabs) from the run: they are lost and no\n"
     "                    longer simulated (nbco_aperture_apply; with -cpu the same rule on the host).  Per snapshot\n"
     "                    <output>/lost<iter>_<ds>.bin receives k int32 rows (the rows the lost particles had in the state; with\n"
     "                    -snapshot-order input their particle numbers), then k x 6 floats x y z vx vy vz -- empty when nobody was lost --\n"
-    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs\n"
+    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs, -bonds\n"
     "                    describe the survivors; the snapshot files shrink with n.  A run that loses everybody ends with an error.\n"
     "                    Refused with -test, -test2 and -accuracy.\n"
     "  -aperture-centre <cx> <cy> <cz>   Centre of the aperture (default 0 0 0).\n"
@@ -190,6 +196,30 @@ bool write_pairs(const std::string &folder, int iter, SCAL dt, const std::vector
 	if (!f) std::cerr << "Error: cannot write the pair file of iteration " << iter << " into \"" << folder << "\"" << std::endl;
 	return (bool)f;
 }
+
+// -bonds <rmax> (rmax = 0: the flag was not given).  <folder>/bonds<iter>_<dt>.bin: n int32 of nb, then n x 2 doubles {q4, q6};
+// <folder>/bonds.txt (emptied when the run starts): 'iter bonds isolated nb_max q4_mean q6_mean Q4 Q6' per snapshot
+struct BondsLog
+{
+	double rmax;
+	std::string folder;
+	std::ofstream out;
+	BondsLog(double rmax_, const std::string &folder_) : rmax(rmax_), folder(folder_)
+	{
+		if (rmax > 0) out.open(folder + "/bonds.txt", std::ios::out | std::ios::trunc);
+	}
+	bool record(int iter, SCAL dt, const std::vector<int> &nb, const std::vector<double> &q, const nbco_bond_summary &s)
+	{
+		std::ofstream f(folder + "/bonds" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+		if (f) f.write(reinterpret_cast<const char *>(nb.data()), (std::streamsize)(nb.size() * sizeof(int)));
+		if (f) f.write(reinterpret_cast<const char *>(q.data()), (std::streamsize)(q.size() * sizeof(double)));
+		char buf[256];
+		std::snprintf(buf, sizeof buf, "%d %lld %lld %d %.17g %.17g %.17g %.17g\n", iter, s.bonds, s.isolated, s.nb_max, s.q_mean[0], s.q_mean[1], s.Q[0], s.Q[1]);
+		out << buf << std::flush;
+		if (!f || !out) std::cerr << "Error: cannot write the bond files of iteration " << iter << " into \"" << folder << "\"" << std::endl;
+		return f && out;
+	}
+};
 
 // -aperture <shape> <hx> <hy> <hz> and -aperture-centre <cx> <cy> <cz>
 struct ApertureOpt
@@ -364,8 +394,8 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, const ApertureOpt &aperture, const SlicesOpt &slices,
-	             const double *omega, const nbco_bath &bath)
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const ApertureOpt &aperture,
+	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath)
 	{
 		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
@@ -382,6 +412,13 @@ struct Session
 		DeviceArray<double> pairs_nn2(pair_n);
 		std::vector<unsigned long long> pairs_counts_host(pair_c);
 		std::vector<double> pairs_nn2_host(pair_n), pairs_rows(input_order ? pair_n : 0);
+		// -bonds: nb and {q4, q6} on the device, and the host copies that go into the files
+		const size_t bond_n = bonds_rmax > 0 ? (size_t)n : 0;
+		DeviceArray<int> bonds_nb(bond_n);
+		DeviceArray<double> bonds_q(2 * bond_n);
+		std::vector<int> bonds_nb_host(bond_n), bonds_nb_rows(input_order ? bond_n : 0);
+		std::vector<double> bonds_q_host(2 * bond_n), bonds_q_rows(input_order ? 2 * bond_n : 0);
+		BondsLog blog(bonds_rmax, folder);
 		EnergyLog elog(energy, folder);
 		MomentsLog mlog(moments, folder);
 		// -probes: the points and their results [field m x 3 | potential m] on the device, and the host copy that goes into the files
@@ -531,6 +568,29 @@ struct Session
 				}
 				else if (!write_pairs(folder, snap, dt, pairs_counts_host, pairs_nn2_host)) return -1;
 			}
+			if (bonds_rmax > 0)
+			{
+				// the same private context and the same walk, with the harmonics of the bonds at the leaves; the summary synchronises
+				nbco_bond_summary bsum;
+				check(nbco_bond_order_tree(ctx(), state.ptr, n, bonds_rmax, bonds_nb.ptr, bonds_q.ptr, &bsum), "bond_order_tree");
+				bonds_nb_host.resize((size_t)n);
+				bonds_q_host.resize(2 * (size_t)n);
+				HIPCHK(hipMemcpy(bonds_nb_host.data(), bonds_nb.ptr, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(bonds_q_host.data(), bonds_q.ptr, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+				if (input_order)
+				{
+					bonds_nb_rows.resize((size_t)n);
+					bonds_q_rows.resize(2 * (size_t)n);
+					for (size_t r = 0; r < (size_t)n; ++r)   // (the rows of the snapshot file)
+					{
+						bonds_nb_rows[r] = bonds_nb_host[(size_t)rank[r]];
+						bonds_q_rows[2 * r] = bonds_q_host[2 * (size_t)rank[r]];
+						bonds_q_rows[2 * r + 1] = bonds_q_host[2 * (size_t)rank[r] + 1];
+					}
+					if (!blog.record(snap, dt, bonds_nb_rows, bonds_q_rows, bsum)) return -1;
+				}
+				else if (!blog.record(snap, dt, bonds_nb_host, bonds_q_host, bsum)) return -1;
+			}
 			if (snap == 0) { loop_t0 = std::chrono::steady_clock::now(); loop_first = 1; }   // the timer below starts behind the first snapshot
 		}
 		check(nbco_sync(ctx()), "sync");
@@ -558,6 +618,7 @@ int main(int argc, const char **argv)
 	std::string strout("out"), strin, strprobes;
 	std::vector<float> probes;
 	PairsOpt pairs;
+	double bonds_rmax = 0;
 	ApertureOpt aperture;
 	SlicesOpt slices;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false, bfield = false;
@@ -702,6 +763,17 @@ int main(int argc, const char **argv)
 				return -1;
 			}
 			i += 2;
+		}
+		else if (a == "-bonds")
+		{
+			if (!need(i, 1, "-bonds")) return -1;
+			bonds_rmax = atof(argv[i + 1]);
+			if (!std::isfinite(bonds_rmax) || !(bonds_rmax > 0))
+			{
+				std::cerr << "Error: invalid argument to '-bonds': " << argv[i + 1] << " (rmax greater than 0)\n";
+				return -1;
+			}
+			++i;
 		}
 		else if (a == "-aperture")
 		{
@@ -878,6 +950,9 @@ int main(int argc, const char **argv)
 		std::vector<double> probes_out(4 * (probes.size() / 3));
 		std::vector<unsigned long long> pairs_counts;
 		std::vector<double> pairs_nn2(pairs.bins ? (size_t)nBodies : 0);
+		std::vector<int> bonds_nb;
+		std::vector<double> bonds_q;
+		BondsLog blog(bonds_rmax, strout);
 		LossLog llog(aperture.on, strout);
 		std::vector<int> lost_rows;
 		std::vector<float> lost_recs;
@@ -941,6 +1016,12 @@ int main(int argc, const char **argv)
 				nbco_cpu::pair_stats(st.data(), nBodies, pairs.bins, pairs.rmax, pairs_counts, pairs_nn2);
 				if (!write_pairs(strout, iter, dt, pairs_counts, pairs_nn2)) return -1;
 			}
+			if (bonds_rmax > 0)
+			{
+				nbco_bond_summary bsum;
+				nbco_cpu::bond_order(st.data(), nBodies, bonds_rmax, bonds_nb, bonds_q, bsum);
+				if (!blog.record(iter, dt, bonds_nb, bonds_q, bsum)) return -1;
+			}
 		}
 		std::cout << std::endl;
 		return 0;
@@ -954,7 +1035,7 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
+		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
 		                     b_accuracy ? nbco_bath{} : bath);
 	}
 	return rc;

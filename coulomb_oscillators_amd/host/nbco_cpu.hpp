@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../include/nbco.h"
 #include "../csrc/integ_compose.hpp"
+#include "../csrc/bond_order.hpp"
 
 namespace nbco_cpu {
 
@@ -217,6 +218,53 @@ inline void pair_stats(const V3 *x, int n, int bins, double rmax, std::vector<un
 		for (int b = 0; b < bins; ++b) counts[(size_t)b] += part[(size_t)w * (size_t)bins + (size_t)b];
 	for (int b = 0; b < bins; ++b) inside += counts[(size_t)b];
 	counts[(size_t)bins] = (unsigned long long)n * (unsigned long long)(n - 1) / 2ull - inside;
+}
+
+// Bond-orientational order of the positions x[0..n) for `nbco3 -cpu -bonds`, by the neighbour rule of nbco_bond_order (include/nbco.h)
+// in fp64 over the fp32 positions: d = x_j - x_i, r2 = (dx dx + dy dy) + dz dz with every product and sum rounded once (the program is
+// compiled with -ffp-contract=off), j a neighbour of i iff 0 < r2 && r2 < rmax * rmax; the harmonics of a bond, q from the sums and the
+// summary come from csrc/bond_order.hpp, the header the device kernels use.  nb gets n values, q gets n pairs {q4, q6}.  Every worker
+// owns a range of i and takes all j in index order; the summary adds the particles in index order afterwards.
+inline void bond_order(const V3 *x, int n, double rmax, std::vector<int> &nb, std::vector<double> &q, nbco_bond_summary &sum)
+{
+	const double R2 = rmax * rmax;
+	nb.assign((size_t)n, 0);
+	q.assign(2 * (size_t)n, 0.0);
+	std::vector<double> sums((size_t)kBondSums3 * (size_t)n, 0.0);
+	int *nbp = nb.data();
+	double *qp = q.data(), *sp = sums.data();
+	for_ranges(n, [=](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			double S[kBondSums3] = {};
+			int cnt = 0;
+			for (int j = 0; j < n; ++j)
+			{
+				const double dx = (double)x[j].x - (double)x[i].x, dy = (double)x[j].y - (double)x[i].y, dz = (double)x[j].z - (double)x[i].z;
+				const double xx = dx * dx, yy = dy * dy, zz = dz * dz, xy = xx + yy, r2 = xy + zz;
+				if (!(0.0 < r2 && r2 < R2)) continue;
+				++cnt;
+				bond_add<3>(dx, dy, dz, r2, S);
+			}
+			double qi[2];
+			bond_q<3>(S, cnt, qi);
+			nbp[i] = cnt;
+			qp[2 * (size_t)i] = qi[0]; qp[2 * (size_t)i + 1] = qi[1];
+			std::copy(S, S + kBondSums3, sp + (size_t)kBondSums3 * (size_t)i);
+		}
+	});
+	double S[kBondSums3] = {}, qsum[2] = {0.0, 0.0};
+	long long bonds = 0, isolated = 0, top = 0;
+	for (int i = 0; i < n; ++i)
+	{
+		for (int m = 0; m < kBondSums3; ++m) S[m] += sums[(size_t)kBondSums3 * (size_t)i + (size_t)m];
+		if (nb[(size_t)i] > 0) { qsum[0] += q[2 * (size_t)i]; qsum[1] += q[2 * (size_t)i + 1]; }
+		else ++isolated;
+		bonds += nb[(size_t)i];
+		top = std::max<long long>(top, nb[(size_t)i]);
+	}
+	sum = nbco_bond_summary{};
+	bond_summary_fill(S, qsum, bonds, isolated, top, n, 3, sum);
 }
 
 // The aperture of `nbco3 -cpu -aperture`, by the rule of nbco_aperture_apply (include/nbco.h) in fp64 over the fp32 positions:

@@ -764,6 +764,53 @@ int nbco_2d_slice_moments(nbco_ctx *c, const double *buf, long long n, const nbc
 int nbco_pair_hist(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
 int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
 int nbco_2d_pair_hist(nbco_ctx *c, const double *p, long long n, int bins, double rmax, unsigned long long *counts_dev, double *nn2_dev);
+/* nbco_bond_order / nbco_bond_order_tree / nbco_2d_bond_order: is the cloud ordered, and into which lattice -- the bond-orientational
+ * order parameters of Steinhardt, Nelson and Ronchetti (Phys. Rev. B 28, 784): per particle the number of neighbours nb and q4, q6,
+ * and a summary with their means and the global Q4, Q6; in 2-D |psi4| and |psi6| (the hexatic order).  g(r) is an angular average
+ * and cannot tell bcc from fcc from hcp; these can, particle by particle.  p is as in nbco_pair_hist and is neither modified nor
+ * reordered.
+ * Neighbours, by the pair rule of nbco_pair_hist: d_a = (double) x_j[a] - (double) x_i[a]; r2 = (dx dx + dy dy) + dz dz (2-D:
+ * dx dx + dy dy), every product and sum rounded once, no fused multiply-add; R2 = rmax * rmax; j is a neighbour of i iff
+ * 0 < r2 && r2 < R2.  A NaN is outside, and two coincident particles are NOT neighbours of each other: a bond of length 0 has no
+ * direction.  nb[i] is the number of neighbours, an exact integer, the same in every form.
+ * 3-D, l = 4 and 6: u = d * (1 / sqrt(r2)) in fp64; S_lm(i) = sum over the neighbours of Y_lm(u_ij), Y_lm an orthonormal real basis of
+ * the degree-l spherical harmonics (9 + 13 components); q_l(i) = sqrt(4 pi / (2l+1) * sum_m S_lm(i)^2) / nb[i], and 0 where nb[i] = 0,
+ * never NaN.  q_l does not depend on the choice of basis: by the addition theorem q_l^2 = (1 / nb^2) sum_{j,k} P_l(u_ij . u_ik).
+ * 2-D: psi_l(i) = |sum_j (u_x + i u_y)^l| / nb[i], the powers by repeated complex multiplication, no trigonometric call; 0 where nb = 0.
+ * The harmonics are formed in one place (csrc/bond_order.hpp): polynomials in (x, y, z), the Legendre part in z times the real and
+ * imaginary parts of (x + i y)^m by recurrence, no trigonometry and no table.  nbco_bond_harmonics exports them: host only, no GPU
+ * needed; y4[0] and y6[0] are m = 0, entries 2m - 1 and 2m the cosine and sine parts of m.  u3 is taken as it is (not normalised).
+ * NBCO_ERR_ARG: a null pointer or a non-finite component.  The device kernels, `nbco3 -cpu` and the tests take them from it. */
+int nbco_bond_harmonics(const double u3[3], double y4[9], double y6[13]);
+/* The summary: a HOST struct, filled when a non-NULL pointer is given; the call then synchronises. */
+typedef struct nbco_bond_summary {
+	long long n, bonds, isolated;   /* bonds = sum nb[i] (directed), isolated = #{nb[i] == 0} */
+	int nb_max, dim;
+	double q_mean[2];               /* mean of q4 / q6 (2-D: psi4 / psi6) over the particles with nb > 0; 0 if none */
+	double Q[2];                    /* global: sqrt(4 pi/(2l+1) sum_m (sum_i S_lm(i))^2) / bonds; 2-D: |sum_i sum_j z^l| / bonds; 0 if bonds == 0 */
+} nbco_bond_summary;
+/* nb_dev receives n int32, q_dev n pairs {q4, q6} of doubles (2-D: {psi4, psi6}), both in the caller's particle order, both in DEVICE
+ * memory.  Any of the three outputs may be NULL, not all three; a NULL output costs nothing.  Without sum_host the calls return as the
+ * evaluators do (opts.sync, opts.stream).
+ * Refused before any launch, the outputs untouched: with NBCO_ERR_ARG a NULL c or p, n <= 0, all outputs NULL, rmax not finite or <= 0;
+ * with NBCO_ERR_UNSUPPORTED n >= 2^31, and for the tree form exactly the n and tree_L that nbco_pair_hist_tree refuses.  The exact
+ * forms treat a non-finite coordinate as outside: that particle is isolated and nobody's neighbour; the tree form requires finite
+ * coordinates, as the evaluator does.
+ * Determinism: no float atomics; every sum has a fixed order, so a second call returns the same bytes.  The exact form meets a
+ * particle's neighbours in index order, the tree form in the order of the tree's leaves, and the summary adds the particles in waves
+ * of 64 of the caller's order and of the tree order respectively: nb IS EQUAL INTEGER FOR INTEGER IN BOTH FORMS, BUT q AND THE
+ * SUMMARY AGREE ONLY TO ROUNDING (|delta q_l^2| below 1e-11 for nb <= 256), NOT BIT FOR BIT -- unlike nbco_pair_hist_tree.
+ * State: the exact forms use only the transient reduction scratch of the context, as nbco_beam_moments does.  The tree form is
+ * self-contained like nbco_pair_hist_tree: on the private context it takes a scratch copy of p, builds the kd-tree over it (the build
+ * only) and walks it as that call does, with the harmonics of the bonds at the leaves.  In both forms this context's tree, rebuild
+ * schedule, warm-select history, order tracking and nbco_kd_get_info stay as they were, and a following evaluation or diagnostic
+ * returns the bits it would have returned.
+ * Not offered: other l, the third-order invariants w_l, the neighbour-averaged q-bar_l and solid-bond counting (a second pass over
+ * stored S_lm), Voronoi or k-nearest neighbours instead of a cutoff, a 2-D tree form, sharded runs, and a form on the tree of the
+ * LAST EVALUATION, for the reason given at nbco_pair_hist_tree. */
+int nbco_bond_order(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
+int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
+int nbco_2d_bond_order(nbco_ctx *c, const double *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 /* ---- aperture: particles that cross a boundary (a pipe wall, an electrode) are lost -- dropped from the state on the device,
  * recorded, and no longer simulated.  nbco_aperture_count / nbco_aperture_apply serve the 3-D fp32 state, the nbco_2d_ forms the
  * 2-D fp64 state (they read centre[0..1] and half[0..1] only).  *ap_host lies in HOST memory.
