@@ -116,26 +116,15 @@ __global__ __launch_bounds__(kBlock) void bond_exact_kernel(const T *__restrict_
 	__shared__ double src[3][kBlock];
 	const int tid = threadIdx.x;
 	const long long nt = (n + kBlock - 1) / kBlock, i = (long long)blockIdx.x * kBlock + tid;
-	// a thread without a particle carries NaNs: nobody is its neighbour
-	double x0 = __longlong_as_double(0x7FF8000000000000ll), x1 = x0, x2 = x0;
-	if (i < n)
-	{
-		const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[i];
-		x0 = (double)q.v[0]; x1 = (double)q.v[1];
-		if (D == 3) x2 = (double)q.v[D - 1];
-	}
+	double x0, x1, x2;
+	pair_target<T, D>(p, i, n, x0, x1, x2);
 	double S[D == 3 ? kBondSums3 : kBondSums2] = {};
 	int nb = 0;
 	for (long long J = 0; J < nt; ++J)
 	{
 		__syncthreads();
 		const long long j = J * kBlock + tid;
-		if (j < n)
-		{
-			const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[j];
-			src[0][tid] = (double)q.v[0]; src[1][tid] = (double)q.v[1];
-			if (D == 3) src[2][tid] = (double)q.v[D - 1];
-		}
+		pair_stage<T, D>(p, j, n, src);
 		__syncthreads();
 		const int cnt = (int)(n - J * kBlock < kBlock ? n - J * kBlock : kBlock);
 		for (int u = 0; u < cnt; ++u)
@@ -159,90 +148,36 @@ __global__ __launch_bounds__(kBlock) void bond_exact_kernel(const T *__restrict_
 #endif   // NBCO_BOND_EXACT
 
 #ifdef NBCO_BOND_WALK
-// ---- tree form: the walk of kd_pair_walk_kernel with another visitor ------------------------------------------------------------------
-// The control flow is that kernel's, unchanged: a wave takes 64 consecutive particles of the tree order, goes through the implicit
-// tree without a stack, opens a node iff the box of the node is within R2 (1 + 1e-9) of a lane's particle, and stages a leaf's
-// particles in its LDS tile 64 at a time.  The tree decides only what is skipped: a lane meets exactly its neighbours, in the order
-// of the leaves.  The particle itself and a coincident one fall out through r2 > 0, so the tree position is not asked.  nb and q go
-// through the build's unsort map into the caller's order.  A workgroup is kPairWalkWaves waves of kPairWalkChunks chunks each.
+// ---- tree form: a visitor of the radius walk (kd_radius_walk, pair_stat_kernels.hpp) ----------------------------------------------------
+// A lane meets exactly its neighbours, in the order of the leaves: its sums are added in that order.  The particle itself and a
+// coincident one fall out through r2 > 0, so the tree position is not asked.  nb and q go through the build's unsort map into the
+// caller's order.
 template <bool SUM>
 __global__ __launch_bounds__(64 * kPairWalkWaves) void kd_bond_walk_kernel(const float *__restrict__ lbound, const float *__restrict__ rbound,
                                                                             const int *__restrict__ mult, const int *__restrict__ index,
                                                                             const float4 *__restrict__ pos, const int *__restrict__ unsort, int ntot, long long n,
-                                                                            double R2, double R2m, int *__restrict__ nb_out, double *__restrict__ q_out,
+                                                                            double R2m, double R2, int *__restrict__ nb_out, double *__restrict__ q_out,
                                                                             double *__restrict__ rec)
 {
 	__shared__ double tile[kPairWalkWaves][3][64];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 	for (int q = 0; q < kPairWalkChunks; ++q)
 	{
-		const long long s0 = (((long long)blockIdx.x * kPairWalkWaves + w) * kPairWalkChunks + q) * 64;
+		const long long s0 = kd_walk_chunk(q), s = s0 + (threadIdx.x & 63);
 		if (s0 >= n) break;   // (the whole wave)
-		const long long s = s0 + lane;
-		const bool valid = s < n;
-		const float4 me = pos[valid ? s : n - 1];
-		const double X = (double)me.x, Y = (double)me.y, Z = (double)me.z;
 		double S[kBondSums3] = {};
 		int nb = 0;
-		int k = 0;
-		for (;;)
-		{
-			k = __builtin_amdgcn_readfirstlane(k);   // (uniform by construction: it moves on ballots only)
-			const double gx = fmax(fmax((double)lbound[3 * k] - X, 0.0), X - (double)rbound[3 * k]);
-			const double gy = fmax(fmax((double)lbound[3 * k + 1] - Y, 0.0), Y - (double)rbound[3 * k + 1]);
-			const double gz = fmax(fmax((double)lbound[3 * k + 2] - Z, 0.0), Z - (double)rbound[3 * k + 2]);
-			const bool need = valid && gx * gx + gy * gy + gz * gz <= R2m;
-			const bool any_need = __ballot(need) != 0;
-			const bool leaf = 2 * k + 1 >= ntot;
-			if (leaf && any_need)
+		kd_radius_walk(lbound, rbound, mult, index, pos, ntot, n, R2m, s, tile[threadIdx.x >> 6], [&](bool need, long long, long long, double dx, double dy, double dz) {
+			const double r2 = pair_r2(dx, dy, dz);
+			const bool in = need && 0.0 < r2 && r2 < R2;
+			if (__ballot(in) == 0) return;
+			if (in)
 			{
-				// (a leaf's range lies inside [0, n) by the build; the clamp keeps a damaged tree from reading past the array, and the
-				// checked build counts what the clamp would have hidden)
-				const long long i0 = index[k];
-				long long ml = mult[k];
-				(void)NBCO_CHECKED_OK(i0 >= 0 && ml >= 0 && i0 + ml <= n, NBCO_CHK_WALK);
-				if (i0 < 0 || i0 >= n) ml = 0;
-				else if (ml > n - i0) ml = n - i0;
-				for (long long j0 = 0; j0 < ml; j0 += 64)
-				{
-					wave_lds_sync();
-					if (j0 + lane < ml)
-					{
-						const float4 v = pos[i0 + j0 + lane];
-						tile[w][0][lane] = (double)v.x; tile[w][1][lane] = (double)v.y; tile[w][2][lane] = (double)v.z;
-					}
-					wave_lds_sync();
-					const int cnt = (int)(ml - j0 < 64 ? ml - j0 : 64);
-					for (int u = 0; u < cnt; ++u)
-					{
-						const double dx = tile[w][0][u] - X, dy = tile[w][1][u] - Y, dz = tile[w][2][u] - Z;
-						const double r2 = pair_r2(dx, dy, dz);
-						const bool in = need && 0.0 < r2 && r2 < R2;
-						if (__ballot(in) == 0) continue;
-						if (in)
-						{
-							++nb;
-							bond_add<3>(dx, dy, dz, r2, S);
-						}
-					}
-				}
+				++nb;
+				bond_add<3>(dx, dy, dz, r2, S);
 			}
-			if (!leaf && any_need) k = 2 * k + 1;
-			else
-			{
-				while (k != 0 && (k & 1) == 0) k = (k - 1) >> 1;   // up while a right child
-				if (k == 0) break;
-				k = k + 1;   // the sibling of a left child
-			}
-		}
-		long long dst = -1;
-		if (valid)
-		{
-			dst = unsort[s];   // (a permutation of [0, n) by the build; the check keeps a damaged map from writing outside the outputs)
-			(void)NBCO_CHECKED_OK(dst >= 0 && dst < n, NBCO_CHK_WALK);
-			if (dst >= n) dst = -1;
-		}
-		bond_finish<3, SUM>(valid, dst, nb, S, nb_out, q_out, SUM ? rec + (s0 >> 6) * kBondRec : nullptr);
+		});
+		const bool valid = s < n;
+		bond_finish<3, SUM>(valid, valid ? kd_walk_row(unsort, n, s) : -1, nb, S, nb_out, q_out, SUM ? rec + (s0 >> 6) * kBondRec : nullptr);
 	}
 }
 #endif   // NBCO_BOND_WALK

@@ -809,24 +809,33 @@ int kd_probe_last(nbco_ctx *c, const float *t, long long m, const float *param, 
 	return kd_probe_walk(c, probe_src(c, le, le.pos, le.n), t, m, param, a, psi);   // (not sharded: the root box is that of the context's own tree)
 }
 
-// nbco_probe_tree, on the private context: tree and multipoles over x[0..n) and the walk.  The probes need kd_build + kd_upward only.
-int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long m, const float *param, double *a, double *psi)
+// The tree of the private context's calls over x[0..n): kd_build alone -- no traversal, no lists -- with the multipoles if `upward`
+// is set, and its bookkeeping once all of that has succeeded
+static int kd_private_tree(nbco_ctx *c, float *x, long long n, int L, bool upward)
 {
-	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
 	c->last_eval.valid = false;   // the lists of an earlier evaluation belong to another tree
 	bool rebuild = false;
 	NBCO_TRY(kd_build_settled(c, [&] { return kd_build(c, x, n, L, KdRoot{}, rebuild, nullptr); }, rebuild, true));
-	NBCO_TRY(kd_upward(c));
-	NBCO_TRY(c->join_aux());
+	if (upward)
+	{
+		NBCO_TRY(kd_upward(c));
+		NBCO_TRY(c->join_aux());
+	}
 	c->tree_valid = true;   // (the boxes in the tree arrays are this build's: the next build of the same shape may select around them)
 	c->tree_n = n;
 	c->tree_order = c->kd.order;
+	return NBCO_OK;
+}
+
+// nbco_probe_tree, on the private context: that tree with its multipoles (the probes need kd_build + kd_upward only) and the walk
+int kd_probe_tree(nbco_ctx *c, float *x, long long n, const float *t, long long m, const float *param, double *a, double *psi)
+{
+	NBCO_TRY(kd_private_tree(c, x, n, kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L), true));
 	return kd_probe_walk(c, probe_src(c, c->kd, c->pos4.as<float4>(), n), t, m, param, a, psi);
 }
 
-// The tree of nbco_pair_hist_tree and nbco_bond_order_tree, on the private context, over x[0..n) -- kd_build only: no upward pass, no
-// traversal, no lists.
-static int kd_build_for_walk(nbco_ctx *c, float *x, long long n)
+// The tree of nbco_pair_hist_tree and nbco_bond_order_tree, on the private context: that tree, with what the radius walk asks of it
+static int kd_radius_walk_tree(nbco_ctx *c, float *x, long long n)
 {
 	const int L = kd_levels(n, c->o.fmm_order, c->o.dens_inhom, c->o.tree_L);
 	// The build finishes every leaf inside one workgroup's LDS slice of kSubS particles.  A tree_L that leaves more than that per
@@ -834,33 +843,33 @@ static int kd_build_for_walk(nbco_ctx *c, float *x, long long n)
 	// launched, because the walks scatter their results through that map.
 	if (((n + (1LL << L) - 1) >> L) > kSubS)
 		return c->fail(NBCO_ERR_UNSUPPORTED, "tree_L leaves more than " + std::to_string(kSubS) + " particles per leaf: the kd-tree build cannot hold them");
-	c->last_eval.valid = false;   // the lists of an earlier evaluation belong to another tree
-	bool rebuild = false;
-	NBCO_TRY(kd_build_settled(c, [&] { return kd_build(c, x, n, L, KdRoot{}, rebuild, nullptr); }, rebuild, true));
-	c->tree_valid = true;   // (the boxes in the tree arrays are this build's: the next build of the same shape may select around them)
-	c->tree_n = n;
-	c->tree_order = c->kd.order;
-	return NBCO_OK;
+	return kd_private_tree(c, x, n, L, false);
 }
 
-// nbco_pair_hist_tree: that tree and the range-limited walk over its boxes.  nn2 is written for every particle; the counts are cleared
-// first and closed with the pairs outside.
+// The launch of a radius walk of rmax^2 = R2 over that tree, one wave per 64 particles of the tree order: the head of the kernel's
+// parameter list (the tree and R2m) is filled in here, `own` is what the visitor takes behind it.
+template <class Kernel, class... Own>
+static void launch_radius_walk(nbco_ctx *c, Kernel kernel, size_t lds_bytes, long long n, double R2, Own... own)
+{
+	const KdTreeDev &k = c->kd;
+	const dim3 grid((unsigned)((n + kPairWgParticles - 1) / kPairWgParticles)), block(64 * kPairWalkWaves);
+	hipLaunchKernelGGL(kernel, grid, block, lds_bytes, c->stream, (const float *)k.lbound, (const float *)k.rbound, (const int *)k.mult, (const int *)k.index,
+	                   (const float4 *)c->pos4.as<float4>(), (const int *)c->unsort.as<int>(), k.ntot, n, R2 * (1.0 + 1e-9), own...);
+}
+
+// nbco_pair_hist_tree: the pair statistics as that walk's visitor.  nn2 is written for every particle; the counts are cleared first and
+// closed with the pairs outside.
 int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts, double *nn2)
 {
-	NBCO_TRY(kd_build_for_walk(c, x, n));
+	NBCO_TRY(kd_radius_walk_tree(c, x, n));
 	if (counts) NBCO_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * ((size_t)pb.bins + 1), c->stream));
 	// the LDS histogram while its 32-bit counters cannot wrap (a workgroup bins fewer than kPairWgParticles * n pairs) and the bins fit
 	const bool lds = pb.bins <= kPairLdsBins && (unsigned long long)kPairWgParticles * (unsigned long long)n < (1ull << 32);
-	const dim3 grid((unsigned)((n + kPairWgParticles - 1) / kPairWgParticles)), block(64 * kPairWalkWaves);
-	const KdTreeDev &k = c->kd;
-	const double R2m = pb.R2 * (1.0 + 1e-9);
 	auto launch = [&](auto use_lds) {
 		constexpr bool LDS = decltype(use_lds)::value;
 		const size_t bytes = LDS && counts ? sizeof(unsigned) * (size_t)pb.bins : 0;
 		with_outputs((const double *)counts, nn2, [&](auto wc, auto wn) {
-			hipLaunchKernelGGL((kd_pair_walk_kernel<LDS, decltype(wc)::value, decltype(wn)::value>), grid, block, bytes, c->stream, (const float *)k.lbound,
-			                   (const float *)k.rbound, (const int *)k.mult, (const int *)k.index, (const float4 *)c->pos4.as<float4>(),
-			                   (const int *)c->unsort.as<int>(), k.ntot, n, pb, R2m, counts, nn2);
+			launch_radius_walk(c, kd_pair_walk_kernel<LDS, decltype(wc)::value, decltype(wn)::value>, bytes, n, pb.R2, pb, counts, nn2);
 		});
 	};
 	if (lds) launch(std::true_type{});
@@ -871,11 +880,11 @@ int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, un
 	return NBCO_OK;
 }
 
-// nbco_bond_order_tree: that tree and the same walk with the bonds' harmonics at the leaves; nb and q are written for every particle,
-// the summary from one record per wave (the reduction scratch of the private context)
+// nbco_bond_order_tree: the bonds' harmonics as that walk's visitor; nb and q are written for every particle, the summary from one
+// record per wave (the reduction scratch of the private context)
 int kd_bond_order_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb, double *q, nbco_bond_summary *sum_host)
 {
-	NBCO_TRY(kd_build_for_walk(c, x, n));
+	NBCO_TRY(kd_radius_walk_tree(c, x, n));
 	const long long records = (n + 63) / 64;
 	double *rec = nullptr;
 	if (sum_host)
@@ -883,14 +892,7 @@ int kd_bond_order_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb, d
 		NBCO_TRY(c->reserve(c->part, sizeof(double) * kBondRec * (size_t)records));
 		rec = c->part.as<double>();
 	}
-	const dim3 grid((unsigned)((n + kPairWgParticles - 1) / kPairWgParticles)), block(64 * kPairWalkWaves);
-	const KdTreeDev &k = c->kd;
-	const double R2m = R2 * (1.0 + 1e-9);
-	with_flag(sum_host != nullptr, [&](auto ws) {
-		hipLaunchKernelGGL((kd_bond_walk_kernel<decltype(ws)::value>), grid, block, 0, c->stream, (const float *)k.lbound, (const float *)k.rbound,
-		                   (const int *)k.mult, (const int *)k.index, (const float4 *)c->pos4.as<float4>(), (const int *)c->unsort.as<int>(), k.ntot, n, R2, R2m,
-		                   nb, q, rec);
-	});
+	with_flag(sum_host != nullptr, [&](auto ws) { launch_radius_walk(c, kd_bond_walk_kernel<decltype(ws)::value>, 0, n, R2, R2, nb, q, rec); });
 	NBCO_HIP(hipGetLastError());
 	return sum_host ? bond_summary_finish(c, rec, records, n, 3, sum_host) : NBCO_OK;
 }

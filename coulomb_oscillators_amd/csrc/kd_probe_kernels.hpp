@@ -156,6 +156,16 @@ __global__ __launch_bounds__(kBlock) void kd_probe_keys_kernel(const float *t, l
 	}
 }
 
+// One step of a walk through the implicit tree (children 2k + 1, 2k + 2) without a stack, k the same in every lane: down to the left
+// child if the wave opens node k, else up while a right child and over to the sibling of a left child.  The node after k, or 0 (the
+// root, which no step leads to): the walk is done.  (the probe walk here and the radius walk of pair_stat_kernels.hpp)
+__device__ inline int kd_walk_next(int k, bool open)
+{
+	if (open) return 2 * k + 1;
+	while (k != 0 && (k & 1) == 0) k = (k - 1) >> 1;
+	return k == 0 ? 0 : k + 1;
+}
+
 // The walk.  One wave takes 64 consecutive probes of the sorted order and goes through the implicit tree (children 2k + 1, 2k + 2)
 // without a stack; the current node k is the same in every lane, so its record, multiplicity and multipole are scalar loads.  Every
 // lane takes its own decision.  A lane that has accepted a node is covered while the walk stays in that node's subtree (cov1: the
@@ -236,13 +246,8 @@ __global__ __launch_bounds__(kProbeWave) void kd_probe_walk_kernel(const float4 
 					}
 			}
 		}
-		if (!leaf && any_open) k = 2 * k + 1;
-		else
-		{
-			while (k != 0 && (k & 1) == 0) k = (k - 1) >> 1;   // up while a right child
-			if (k == 0) break;
-			k = k + 1;   // the sibling of a left child
-		}
+		k = kd_walk_next(k, !leaf && any_open);
+		if (k == 0) break;
 	}
 	if (!valid) return;
 	const double s0 = (double)param[0];

@@ -616,7 +616,7 @@ int nbco_kd_potential(nbco_ctx *c, const float *buf, long long n, const float *p
 	return energy_from_potential(c, buf, n, param, out3_host, phi_dev);
 }
 
-// The private context of nbco_energy_tree and nbco_probe_tree (`who`), created on first use: everything of theirs runs on it, and this
+// The private context of the four *_tree calls (`who`), created on first use: everything of theirs runs on it, and this
 // context's tree, lists, schedule and bookkeeping are not touched.  The child follows this context's expansion and tree options
 // (re-read at every call) and always rebuilds, in the caller's particle order.
 static int private_child(nbco_ctx *c, const char *who, nbco_ctx *&k)
@@ -634,24 +634,36 @@ static int private_child(nbco_ctx *c, const char *who, nbco_ctx *&k)
 	return NBCO_OK;
 }
 
+// body(k, x) on that context k, with x = a scratch copy of the positions src[0 .. 3n) at the head of `floats` * n floats of room, copied
+// on k's stream; what k refuses comes back as this context's error under the caller's name
+extern "C++" {   // (a template inside the extern "C" block of the exports)
+template <class Body>
+static int on_private_copy(nbco_ctx *c, const char *who, const float *src, long long n, int floats, Body body)
+{
+	nbco_ctx *k;
+	NBCO_TRY(private_child(c, who, k));
+	auto pass = [&]() -> int {
+		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * floats * (size_t)n));
+		float *x = k->pot_xa.as<float>();
+		NBCO_HIP_M(k, hipMemcpyAsync(x, src, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
+		return body(k, x);
+	};
+	const int rc = pass();
+	if (rc != NBCO_OK) return c->fail(rc, std::string(who) + ": " + k->err);
+	return NBCO_OK;
+}
+}   // extern "C++"
+
 int nbco_energy_tree(nbco_ctx *c, const float *buf, long long n, const float *param, double *out3_host, double *phi_dev)
 {
 	if (!c || !buf || !param || !out3_host) return c ? c->fail(NBCO_ERR_ARG, "nbco_energy_tree: null pointer") : NBCO_ERR_ARG;
 	if (n <= 0) return c->fail(NBCO_ERR_ARG, "nbco_energy_tree: n must be positive");
 	if (n > 0x7fffffffLL / 4) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_energy_tree: n too large for 32-bit tree indices");
-	nbco_ctx *k;
-	NBCO_TRY(private_child(c, "nbco_energy_tree", k));
-	auto pass = [&]() -> int {
-		// scratch copy of the positions + room for the accelerations the evaluation writes
-		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 6 * (size_t)n));
-		float *x = k->pot_xa.as<float>(), *a = x + 3 * n;
-		NBCO_HIP_M(k, hipMemcpyAsync(x, buf, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
-		NBCO_TRY(fmm_kdtree_eval(k, x, a, n, param));
+	// (room behind the copy for the accelerations the evaluation writes)
+	return on_private_copy(c, "nbco_energy_tree", buf, n, 6, [&](nbco_ctx *k, float *x) {
+		NBCO_TRY(fmm_kdtree_eval(k, x, x + 3 * n, n, param));
 		return energy_from_potential(k, buf, n, param, out3_host, phi_dev);
-	};
-	const int rc = pass();
-	if (rc != NBCO_OK) return c->fail(rc, "nbco_energy_tree: " + k->err);
-	return NBCO_OK;
+	});
 }
 
 // ---- 3-D probes --------------------------------------------------------------------------------
@@ -686,16 +698,7 @@ int nbco_kd_probe(nbco_ctx *c, const float *t, long long m, const float *param, 
 int nbco_probe_tree(nbco_ctx *c, const float *p, long long n, const float *t, long long m, const float *param, double *a_dev, double *psi_dev)
 {
 	NBCO_TRY(probe_args(c, "nbco_probe_tree", true, p, n, t, m, param, a_dev, psi_dev));
-	nbco_ctx *k;
-	NBCO_TRY(private_child(c, "nbco_probe_tree", k));
-	auto pass = [&]() -> int {
-		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
-		float *x = k->pot_xa.as<float>();
-		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
-		return kd_probe_tree(k, x, n, t, m, param, a_dev, psi_dev);
-	};
-	const int rc = pass();
-	if (rc != NBCO_OK) return c->fail(rc, "nbco_probe_tree: " + k->err);
+	NBCO_TRY(on_private_copy(c, "nbco_probe_tree", p, n, 3, [&](nbco_ctx *k, float *x) { return kd_probe_tree(k, x, n, t, m, param, a_dev, psi_dev); }));
 	return maybe_sync(c);
 }
 
@@ -742,16 +745,7 @@ int nbco_pair_hist_tree(nbco_ctx *c, const float *p, long long n, int bins, doub
 {
 	PairBins pb;
 	NBCO_TRY(pair_args(c, "nbco_pair_hist_tree", true, p, n, bins, rmax, counts_dev, nn2_dev, pb));
-	nbco_ctx *k;
-	NBCO_TRY(private_child(c, "nbco_pair_hist_tree", k));
-	auto pass = [&]() -> int {
-		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
-		float *x = k->pot_xa.as<float>();
-		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
-		return kd_pair_hist_tree(k, x, n, pb, counts_dev, nn2_dev);
-	};
-	const int rc = pass();
-	if (rc != NBCO_OK) return c->fail(rc, "nbco_pair_hist_tree: " + k->err);
+	NBCO_TRY(on_private_copy(c, "nbco_pair_hist_tree", p, n, 3, [&](nbco_ctx *k, float *x) { return kd_pair_hist_tree(k, x, n, pb, counts_dev, nn2_dev); }));
 	return maybe_sync(c);
 }
 
@@ -798,16 +792,7 @@ int nbco_2d_bond_order(nbco_ctx *c, const double *p, long long n, double rmax, i
 int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host)
 {
 	NBCO_TRY(bond_args(c, "nbco_bond_order_tree", true, p, n, rmax, nb_dev, q_dev, sum_host));
-	nbco_ctx *k;
-	NBCO_TRY(private_child(c, "nbco_bond_order_tree", k));
-	auto pass = [&]() -> int {
-		NBCO_TRY(k->reserve(k->pot_xa, sizeof(float) * 3 * (size_t)n));
-		float *x = k->pot_xa.as<float>();
-		NBCO_HIP_M(k, hipMemcpyAsync(x, p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, k->stream));
-		return kd_bond_order_tree(k, x, n, rmax * rmax, nb_dev, q_dev, sum_host);
-	};
-	const int rc = pass();
-	if (rc != NBCO_OK) return c->fail(rc, "nbco_bond_order_tree: " + k->err);
+	NBCO_TRY(on_private_copy(c, "nbco_bond_order_tree", p, n, 3, [&](nbco_ctx *k, float *x) { return kd_bond_order_tree(k, x, n, rmax * rmax, nb_dev, q_dev, sum_host); }));
 	return maybe_sync(c);
 }
 

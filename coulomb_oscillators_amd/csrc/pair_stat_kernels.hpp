@@ -87,6 +87,28 @@ constexpr int kPairGridY = 1024;
 static_assert(kPairLdsBins == kHistLdsBins, "one LDS histogram size for the density maps and the pair statistics");
 static_assert((long long)kBlock * kBlock * kPairSrcTiles * ((1LL << 31) / kBlock / kPairSrcTiles / kPairGridY) < (1LL << 32), "LDS counters could wrap");
 
+// particle i of p, widened (2-D: x2 is left as it is)
+template <class T, int D>
+__device__ inline void pair_widen(const T *__restrict__ p, long long i, double &x0, double &x1, double &x2)
+{
+	const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[i];
+	x0 = (double)q.v[0]; x1 = (double)q.v[1];
+	if (D == 3) x2 = (double)q.v[D - 1];
+}
+// a thread's own particle i; a thread without one carries NaNs: none of its pairs is inside, nobody is its neighbour
+template <class T, int D>
+__device__ inline void pair_target(const T *__restrict__ p, long long i, long long n, double &x0, double &x1, double &x2)
+{
+	x0 = x1 = x2 = __longlong_as_double(0x7FF8000000000000ll);
+	if (i < n) pair_widen<T, D>(p, i, x0, x1, x2);
+}
+// a thread's share of a source tile: particle j, widened once, into its slot of the LDS tile (the caller's barriers around it)
+template <class T, int D>
+__device__ inline void pair_stage(const T *__restrict__ p, long long j, long long n, double (*__restrict__ src)[kBlock])
+{
+	if (j < n) pair_widen<T, D>(p, j, src[0][threadIdx.x], src[1][threadIdx.x], src[2][threadIdx.x]);
+}
+
 template <int D, bool LDS, bool WANT_CNT, bool WANT_NN, bool DIAG>
 __device__ inline void pair_tile(double x0, double x1, double x2, const double (*__restrict__ src)[kBlock], int cnt, const PairBins &pb, unsigned *hist,
                                  unsigned long long *__restrict__ counts, unsigned long long *smin, double &tmin)
@@ -120,14 +142,8 @@ __global__ __launch_bounds__(kBlock) void pair_hist_kernel(const T *__restrict__
 	if (WANT_CNT && LDS)
 		for (int b = tid; b < pb.bins; b += kBlock) pair_hist_sh[b] = 0u;   // (the tile loop's first barrier comes before any add)
 	const long long i = I * kBlock + tid;
-	// a thread without a particle carries NaNs: none of its pairs is inside
-	double x0 = __longlong_as_double(0x7FF8000000000000ll), x1 = x0, x2 = x0;
-	if (i < n)
-	{
-		const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[i];
-		x0 = (double)q.v[0]; x1 = (double)q.v[1];
-		if (D == 3) x2 = (double)q.v[D - 1];
-	}
+	double x0, x1, x2;
+	pair_target<T, D>(p, i, n, x0, x1, x2);
 	double tmin = __longlong_as_double((long long)kPairInfBits);
 	for (long long c0 = blockIdx.y;; c0 += gridDim.y)
 	{
@@ -138,12 +154,7 @@ __global__ __launch_bounds__(kBlock) void pair_hist_kernel(const T *__restrict__
 		{
 			__syncthreads();
 			const long long j = J * kBlock + tid;
-			if (j < n)
-			{
-				const BeamVec<T, D> q = reinterpret_cast<const BeamVec<T, D> *>(p)[j];
-				src[0][tid] = (double)q.v[0]; src[1][tid] = (double)q.v[1];
-				if (D == 3) src[2][tid] = (double)q.v[D - 1];
-			}
+			pair_stage<T, D>(p, j, n, src);
 			if (WANT_NN) smin[tid] = kPairInfBits;
 			__syncthreads();
 			const int cnt = (int)(n - J * kBlock < kBlock ? n - J * kBlock : kBlock);
@@ -187,30 +198,97 @@ __global__ __launch_bounds__(kBlock) void pair_outside_kernel(unsigned long long
 }
 
 #ifdef NBCO_PAIR_STAT_WALK
-// ---- tree form: the walk of kd_probe_walk_kernel with another decision -------------------------------------------------------------
+// ---- tree form: the radius walk, for every diagnostic over the neighbours within a radius --------------------------------------------
 // One wave takes 64 consecutive particles of the tree order -- neighbours in space already -- and goes through the implicit tree
-// without a stack; the current node is the same in every lane, so its box is scalar loads.  A lane needs a node iff the squared
-// distance from its particle to the node's box, per axis max(lb - x, 0, x - rb) in fp64, is <= R2 (1 + 1e-9): the box holds the node's
-// particles, so no pair inside is behind a node that is not needed, and the margin is far above any rounding of the comparison and
-// free, because the result does not depend on what is opened -- the tree decides only what is skipped.  The wave opens a node iff a lane
-// needs it.  A leaf's particles are staged in the wave's LDS tile, 64 at a time, and every lane applies the pair rule to them, self
-// excluded by tree position: it counts a pair only from the lower position, and takes the minimum from both (each end meets the
-// pair on its own walk), so nn2 needs no atomics and goes through the build's unsort map into the caller's order.
-// A workgroup is kPairWalkWaves waves with one LDS histogram; every wave takes kPairWalkChunks chunks of 64, so that one flush serves
-// kPairWgParticles particles.  32-bit LDS counters: a particle counts fewer than n pairs, so a workgroup bins fewer than
-// kPairWgParticles * n between its zeroing and its flush: the launch takes the LDS form only while that is below 2^32 (kd_pair_hist_tree).
+// without a stack (kd_walk_next); the current node is the same in every lane, so its box is scalar loads.  A lane needs a node iff the
+// squared distance from its particle to the node's box, per axis max(lb - x, 0, x - rb) in fp64, is <= R2 (1 + 1e-9): the box holds the
+// node's particles, so no pair inside is behind a node that is not needed, and the margin is far above any rounding of the comparison
+// and free, because the result does not depend on what is opened -- the tree decides only what is skipped.  The wave opens a node iff a
+// lane needs it.  A leaf's particles are staged in the wave's LDS tile, 64 at a time, and every lane hands each of them to its visitor,
+// in wave-uniform control flow: visit(need, s, j, dx, dy, dz) with the lane's `need` of the leaf, the tree positions s of the lane's
+// particle and j of the staged one, and (dx, dy, dz) = staged - own in fp64.  A lane meets its neighbours in the order of the leaves
+// and, within a leaf, of the tree positions, whatever its neighbours in the wave need.
+// A workgroup is kPairWalkWaves waves; every wave takes kPairWalkChunks chunks of 64 (kd_walk_chunk).
 constexpr int kPairWalkWaves = 4, kPairWalkChunks = 4;
 constexpr int kPairWgParticles = 64 * kPairWalkWaves * kPairWalkChunks;
 
+// A walk kernel's parameter list begins with the tree, which launch_radius_walk (k_fmm_kd.hip) fills in: boxes, leaf ranges,
+// tree-ordered positions, the map into the caller's order, ntot, n and R2m = R2 (1 + 1e-9).  They are kernel parameters of their own,
+// const and __restrict__, and not members of a struct (measured: as members the boxes become vector loads): a visitor may issue global
+// atomics, and the boxes stay scalar loads only while the compiler knows that nothing writes them.
+
+// the first tree position of this wave's q-th chunk (at or beyond n: the wave is done)
+__device__ inline long long kd_walk_chunk(int q) { return (((long long)blockIdx.x * kPairWalkWaves + (threadIdx.x >> 6)) * kPairWalkChunks + q) * 64; }
+
+// the caller's row of tree position s < n, or -1 (a permutation of [0, n) by the build; the check keeps a damaged map from writing
+// outside the outputs)
+__device__ inline long long kd_walk_row(const int *__restrict__ unsort, long long n, long long s)
+{
+	const long long dst = unsort[s];
+	(void)NBCO_CHECKED_OK(dst >= 0 && dst < n, NBCO_CHK_WALK);
+	return dst >= 0 && dst < n ? dst : -1;
+}
+
+// the walk of the 64 particles at tree positions s0 .. s0 + 63 (s = s0 + lane; s0 < n and wave-uniform); tile is this wave's own
+template <class Visit>
+__device__ inline void kd_radius_walk(const float *__restrict__ lbound, const float *__restrict__ rbound, const int *__restrict__ mult,
+                                      const int *__restrict__ index, const float4 *__restrict__ pos, int ntot, long long n, double R2m, long long s,
+                                      double (&tile)[3][64], Visit visit)
+{
+	const int lane = threadIdx.x & 63;
+	const bool valid = s < n;
+	const float4 me = pos[valid ? s : n - 1];
+	const double X = (double)me.x, Y = (double)me.y, Z = (double)me.z;
+	int k = 0;
+	for (;;)
+	{
+		k = __builtin_amdgcn_readfirstlane(k);   // (uniform by construction: it moves on ballots only)
+		const double gx = fmax(fmax((double)lbound[3 * k] - X, 0.0), X - (double)rbound[3 * k]);
+		const double gy = fmax(fmax((double)lbound[3 * k + 1] - Y, 0.0), Y - (double)rbound[3 * k + 1]);
+		const double gz = fmax(fmax((double)lbound[3 * k + 2] - Z, 0.0), Z - (double)rbound[3 * k + 2]);
+		const bool need = valid && gx * gx + gy * gy + gz * gz <= R2m;
+		const bool any_need = __ballot(need) != 0;
+		const bool leaf = 2 * k + 1 >= ntot;
+		if (leaf && any_need)
+		{
+			// (a leaf's range lies inside [0, n) by the build; the clamp keeps a damaged tree from reading past the array, and the
+			// checked build counts what the clamp would have hidden)
+			const long long i0 = index[k];
+			long long ml = mult[k];
+			(void)NBCO_CHECKED_OK(i0 >= 0 && ml >= 0 && i0 + ml <= n, NBCO_CHK_WALK);
+			if (i0 < 0 || i0 >= n) ml = 0;
+			else if (ml > n - i0) ml = n - i0;
+			for (long long j0 = 0; j0 < ml; j0 += 64)
+			{
+				wave_lds_sync();
+				if (j0 + lane < ml)
+				{
+					const float4 v = pos[i0 + j0 + lane];
+					tile[0][lane] = (double)v.x; tile[1][lane] = (double)v.y; tile[2][lane] = (double)v.z;
+				}
+				wave_lds_sync();
+				const int cnt = (int)(ml - j0 < 64 ? ml - j0 : 64);
+				for (int u = 0; u < cnt; ++u) visit(need, s, i0 + j0 + u, tile[0][u] - X, tile[1][u] - Y, tile[2][u] - Z);
+			}
+		}
+		k = kd_walk_next(k, !leaf && any_need);
+		if (k == 0) break;
+	}
+}
+
+// Pair statistics as a visitor: the pair rule, self excluded by tree position.  A lane counts a pair only from the lower position and
+// takes the minimum from both (each end meets the pair on its own walk), so nn2 needs no atomics.  One LDS histogram per workgroup,
+// one flush for kPairWgParticles particles.  32-bit LDS counters: a particle counts fewer than n pairs, so a workgroup bins fewer
+// than kPairWgParticles * n between its zeroing and its flush: the launch takes the LDS form only while that is below 2^32
+// (kd_pair_hist_tree).
 template <bool LDS, bool WANT_CNT, bool WANT_NN>
 __global__ __launch_bounds__(64 * kPairWalkWaves) void kd_pair_walk_kernel(const float *__restrict__ lbound, const float *__restrict__ rbound,
                                                                             const int *__restrict__ mult, const int *__restrict__ index,
                                                                             const float4 *__restrict__ pos, const int *__restrict__ unsort, int ntot, long long n,
-                                                                            PairBins pb, double R2m, unsigned long long *__restrict__ counts, double *__restrict__ nn2)
+                                                                            double R2m, PairBins pb, unsigned long long *__restrict__ counts, double *__restrict__ nn2)
 {
 	extern __shared__ unsigned pair_hist_sh[];
 	__shared__ double tile[kPairWalkWaves][3][64];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 	if (WANT_CNT && LDS)
 	{
 		for (int b = threadIdx.x; b < pb.bins; b += 64 * kPairWalkWaves) pair_hist_sh[b] = 0u;
@@ -218,70 +296,25 @@ __global__ __launch_bounds__(64 * kPairWalkWaves) void kd_pair_walk_kernel(const
 	}
 	for (int q = 0; q < kPairWalkChunks; ++q)
 	{
-		const long long s0 = (((long long)blockIdx.x * kPairWalkWaves + w) * kPairWalkChunks + q) * 64;
+		const long long s0 = kd_walk_chunk(q), s = s0 + (threadIdx.x & 63);
 		if (s0 >= n) break;   // (the whole wave)
-		const long long s = s0 + lane;
-		const bool valid = s < n;
-		const float4 me = pos[valid ? s : n - 1];
-		const double X = (double)me.x, Y = (double)me.y, Z = (double)me.z;
 		double tmin = __longlong_as_double((long long)kPairInfBits);
-		int k = 0;
-		for (;;)
-		{
-			k = __builtin_amdgcn_readfirstlane(k);   // (uniform by construction: it moves on ballots only)
-			const double gx = fmax(fmax((double)lbound[3 * k] - X, 0.0), X - (double)rbound[3 * k]);
-			const double gy = fmax(fmax((double)lbound[3 * k + 1] - Y, 0.0), Y - (double)rbound[3 * k + 1]);
-			const double gz = fmax(fmax((double)lbound[3 * k + 2] - Z, 0.0), Z - (double)rbound[3 * k + 2]);
-			const bool need = valid && gx * gx + gy * gy + gz * gz <= R2m;
-			const bool any_need = __ballot(need) != 0;
-			const bool leaf = 2 * k + 1 >= ntot;
-			if (leaf && any_need)
+		kd_radius_walk(lbound, rbound, mult, index, pos, ntot, n, R2m, s, tile[threadIdx.x >> 6], [&](bool need, long long, long long j, double dx, double dy, double dz) {
+			// (& and not &&: with && the compiler guards r2 by a branch on `need` per staged source in the instance without a ballot)
+			const double r2 = pair_r2(dx, dy, dz);
+			const bool in = need & (r2 < pb.R2) & (j != s);
+			if (WANT_NN && in) tmin = fmin(tmin, r2);
+			if (WANT_CNT)
 			{
-				// (a leaf's range lies inside [0, n) by the build; the clamp keeps a damaged tree from reading past the array, and the
-				// checked build counts what the clamp would have hidden)
-				const long long i0 = index[k];
-				long long ml = mult[k];
-				(void)NBCO_CHECKED_OK(i0 >= 0 && ml >= 0 && i0 + ml <= n, NBCO_CHK_WALK);
-				if (i0 < 0 || i0 >= n) ml = 0;
-				else if (ml > n - i0) ml = n - i0;
-				for (long long j0 = 0; j0 < ml; j0 += 64)
-				{
-					wave_lds_sync();
-					if (j0 + lane < ml)
-					{
-						const float4 v = pos[i0 + j0 + lane];
-						tile[w][0][lane] = (double)v.x; tile[w][1][lane] = (double)v.y; tile[w][2][lane] = (double)v.z;
-					}
-					wave_lds_sync();
-					const int cnt = (int)(ml - j0 < 64 ? ml - j0 : 64);
-					for (int u = 0; u < cnt; ++u)
-					{
-						const long long j = i0 + j0 + u;
-						const double r2 = pair_r2(X - tile[w][0][u], Y - tile[w][1][u], Z - tile[w][2][u]);
-						const bool in = need && r2 < pb.R2 && j != s;
-						if (WANT_NN && in) tmin = fmin(tmin, r2);
-						if (WANT_CNT)
-						{
-							const bool mine = in && s < j;
-							const unsigned long long m = __ballot(mine);
-							if (m != 0) pair_count<LDS>(mine, m, mine ? pair_bin(r2, pb) : 0, pair_hist_sh, counts);
-						}
-					}
-				}
+				const bool mine = in && s < j;
+				const unsigned long long m = __ballot(mine);
+				if (m != 0) pair_count<LDS>(mine, m, mine ? pair_bin(r2, pb) : 0, pair_hist_sh, counts);
 			}
-			if (!leaf && any_need) k = 2 * k + 1;
-			else
-			{
-				while (k != 0 && (k & 1) == 0) k = (k - 1) >> 1;   // up while a right child
-				if (k == 0) break;
-				k = k + 1;   // the sibling of a left child
-			}
-		}
-		if (WANT_NN && valid)
+		});
+		if (WANT_NN && s < n)
 		{
-			const long long dst = unsort[s];   // (a permutation of [0, n) by the build; the check keeps a damaged map from writing outside nn2)
-			(void)NBCO_CHECKED_OK(dst >= 0 && dst < n, NBCO_CHK_WALK);
-			if (dst >= 0 && dst < n) nn2[dst] = tmin;
+			const long long dst = kd_walk_row(unsort, n, s);
+			if (dst >= 0) nn2[dst] = tmin;
 		}
 	}
 	if (WANT_CNT && LDS)

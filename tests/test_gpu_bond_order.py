@@ -153,6 +153,38 @@ def test_tree_form_with_leaves_of_several_staging_rounds(engine_lib):
         e.close()
 
 
+@pytest.mark.parametrize("name,opts,rmax", [("ball", {}, 0.5), ("sc", dict(tree_L=3), 1.5)])
+def test_tree_form_and_pair_statistics_see_the_same_walk(engine_lib, name, opts, rmax):
+    """bond_order_tree and pair_hist_tree(bins=1) are two visitors of one walk: on one engine and one input every bond is a counted
+    pair seen from both ends, and a particle has no neighbour exactly where it has no nearest neighbour.  ball(1025): a second
+    workgroup with one particle and both sides of a wave; sc with tree_L = 3: leaves of five staging rounds.  The premise -- no two
+    particles coincide, or a pair at r2 = 0 would be counted and not be a bond -- and the identities themselves are asserted of the
+    numpy models first."""
+    import torch
+    import pairstat_numpy as PN
+    from coulomb_oscillators_amd import Engine
+    pos = ball(1025) if name == "ball" else BN.sc()[0]
+    n = len(pos)
+    m = model((name, n, rmax) if name == "ball" else (name, rmax), pos, rmax)
+    r2_inside, nn2_model = PN.inside_pairs(pos, rmax)
+    assert len(r2_inside) > 0 and r2_inside.min() > 0.0
+    assert m["nb"].sum() == 2 * len(r2_inside) and np.array_equal(m["nb"] == 0, np.isinf(nn2_model)) and m["isolated"] == np.isinf(nn2_model).sum()
+    e = Engine(**opts)
+    try:
+        d = dev(pos)
+        nb, _, s = run(e, "tree", d, n, rmax)
+        nn2 = torch.full((n,), -1.0, dtype=torch.float64, device="cuda")
+        counts = e.pair_hist_tree(d, n, 1, rmax, nn2=nn2)
+        torch.cuda.synchronize()
+        counts, nn2 = [int(v) for v in counts.cpu().numpy()], nn2.cpu().numpy()
+    finally:
+        e.close()
+    assert int(nb.sum()) == 2 * counts[0] and sum(counts) == n * (n - 1) // 2
+    lonely = nn2 == np.inf
+    assert np.array_equal(nb == 0, lonely)
+    assert s.isolated == lonely.sum() and s.bonds == 2 * counts[0]
+
+
 def test_tree_form_on_the_bcc_lattice(eng):
     pos, _ = BN.bcc()
     assert len(pos) == 1024

@@ -20,14 +20,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def median_ms(fn, repeats):
+def times_ms(fn, repeats):
+    """(median, minimum, maximum) of the repeats, after one warm-up call"""
     fn()                                   # (buffers sized, kernels loaded)
     ts = []
     for _ in range(repeats):
         t0 = time.perf_counter()
         fn()
         ts.append(1e3 * (time.perf_counter() - t0))
-    return statistics.median(ts)
+    return statistics.median(ts), min(ts), max(ts)
 
 
 def main():
@@ -56,7 +57,7 @@ def main():
             for name, fn in forms:
                 counts = torch.empty(a.bins + 1, dtype=torch.int64, device="cuda")
                 nn2 = torch.empty(n, dtype=torch.float64, device="cuda")
-                row[name + "_ms"] = median_ms(lambda: fn(d, n, a.bins, rmax, counts=counts, nn2=nn2), a.repeats)
+                row[name + "_ms"], row[name + "_min_ms"], row[name + "_max_ms"] = times_ms(lambda: fn(d, n, a.bins, rmax, counts=counts, nn2=nn2), a.repeats)
                 out[name] = (counts.cpu(), nn2.cpu())
             row["inside"] = int(out["tree"][0][:-1].sum())
             row["with_a_neighbour"] = int(torch.isfinite(out["tree"][1]).sum())
