@@ -150,19 +150,83 @@ class Potential:
         X = np.asarray(X, dtype=np.float64)
         return self.near(lf, X, self_idx) + self.far(lf, X)
 
-    def all(self):
-        """phi_i of every particle, tree order"""
-        out = np.zeros(len(self.pos))
+    def parts(self):
+        """(near_i, far_i) of every particle, tree order: phi_i = near_i + far_i"""
+        near, far = np.zeros(len(self.pos)), np.zeros(len(self.pos))
         for lf in range(self.first + 1):
             i0, m = self.index[self.first + lf], self.mult[self.first + lf]
             idx = np.arange(i0, i0 + m)
-            out[idx] = self.at(lf, self.pos[idx], idx)
-        return out
+            near[idx], far[idx] = self.near(lf, self.pos[idx], idx), self.far(lf, self.pos[idx])
+        return near, far
+
+    def all(self):
+        """phi_i of every particle, tree order"""
+        near, far = self.parts()
+        return near + far
 
 
 def psi(tree, pos, p, eps2, param0, coll=True):
     """psi_i = param0 phi_i in tree order"""
     return float(param0) * Potential(tree, pos, p, eps2, coll).all()
+
+
+def psi_parts(tree, pos, p, eps2, param0, coll=True):
+    """(param0 near_i, param0 far_i) in tree order: the pair sum over the leaf's P2P range and c0[leaf] + lpot; psi_i is their sum"""
+    near, far = Potential(tree, pos, p, eps2, coll).parts()
+    return float(param0) * near, float(param0) * far
+
+
+def m2l_sources(tree):
+    """(start, src): the M2L sources of node v are src[start[v]:start[v + 1]], both directions of every unordered pair"""
+    ntot = len(tree["center"])
+    pairs = np.asarray(tree["m2l"], dtype=np.int64).reshape(-1, 2)
+    tgt = np.concatenate([pairs[:, 0], pairs[:, 1]])
+    src = np.concatenate([pairs[:, 1], pairs[:, 0]])
+    order = np.argsort(tgt, kind="stable")
+    start = np.concatenate([[0], np.cumsum(np.bincount(tgt, minlength=ntot))])
+    return start, src[order]
+
+
+def restated_energy_fmm(tree, pos, p, eps2, param0, coll=True):
+    """The Coulomb energy as kd_potential_kernel (csrc/kd_energy_kernels.hpp, nbco_energy_fmm) forms it: per particle the pair sum
+    over its leaf's P2P range (j != i by index) plus m2p of every M2L source of the leaf and of each of its ancestors, evaluated AT
+    THE PARTICLE; param0 / 2 times the sum.  No locals are read, and a particle's leaf is the one whose index / mult range holds
+    it -- the kernel's (2^L i) / n is not restated."""
+    x = np.asarray(pos, dtype=np.float64)
+    C = np.asarray(tree["center"], dtype=np.float64)
+    M = np.asarray(tree["mpole"], dtype=np.float64)
+    index, mult = np.asarray(tree["index"]), np.asarray(tree["mult"])
+    first = (1 << int(tree["L"])) - 1
+    nb = leaf_neighbours(tree, coll)
+    start, srcs = m2l_sources(tree)
+    seen = np.zeros(len(x), dtype=np.int64)
+    total = 0.0
+    for lf in range(first + 1):
+        idx = np.arange(index[first + lf], index[first + lf] + mult[first + lf])
+        if not len(idx):
+            continue
+        seen[idx] += 1
+        X = x[idx]
+        phi = np.zeros(len(idx))
+        near = [np.arange(index[first + s], index[first + s] + mult[first + s]) for s in nb[lf]]
+        if near:
+            j = np.concatenate(near)
+            d = X[:, None, :] - x[j][None, :, :]
+            w = 1.0 / np.sqrt((d * d).sum(-1) + float(eps2))
+            w[idx[:, None] == j[None, :]] = 0.0
+            phi += w.sum(1)
+        chain, node = [], first + lf
+        while True:
+            chain.append(srcs[start[node]:start[node + 1]])
+            if node == 0:
+                break
+            node = (node - 1) >> 1
+        s = np.concatenate(chain)
+        if len(s):
+            phi += m2p(M[s][None, :, :], X[:, None, :] - C[s][None, :, :], float(eps2), p).sum(1)
+        total += phi.sum()
+    assert (seen == 1).all(), "the leaves' index / mult ranges hold every particle once"
+    return 0.5 * float(param0) * total
 
 
 def pair_potential(pos, eps2):

@@ -421,3 +421,147 @@ def tie_orders(tree, pos_tree_order):
         blind = tied[np.lexsort((org[i + tied], k23[1]))][:left]
         rows.append((int(v), set(full.tolist()) == went_left, set(blind.tolist()) == went_left))
     return rows
+
+
+# ---- the 3-D energy diagnostics and the tree bond order on the shapes (test_energy_shapes_host.py, test_gpu_energy_shapes3d.py,
+# test_gpu_bond_order.py) ------------------------------------------------------------------------------------------------------------
+# the options a row of ENERGY_SHAPE_CASES runs with unless it says otherwise (Engine.set names)
+ENERGY_BASE = dict(unsort=1, m2l_first=0, coll=1, p2p_mutual=0, tree_steps=1, tree_L=0, far_fp64=0, eps2=1e-18, tree_radius=1.0)
+# where points coincide the softened near field buries the far field at eps2 = 1e-18: those rows run with a softening length of 1e-4,
+# below the ball's median nearest-neighbour distance of 4.5e-4
+EPS2_TIED = 1e-8
+
+
+def energy_shape_cases():
+    """(shape, n, p, opts): the rows of the energy diagnostics.  n = 4096 at p = 4 gives 256 leaves of 16; tree_L = 5 gives 32 leaves
+    of 128 (two tiles of 64 targets in kd_psi_leaf_kernel), of 125 / 126 at n = 4001 (an uneven last tile); p = 10 gives 32 leaves
+    of 128 by the level formula itself.  The last row is all near field (no M2L pair): the only form in which 64 copies per point
+    give finite numbers, compared with the pair sum alone.
+
+    Two rows are not the obvious ones, because the obvious ones have no far field (test_energy_shapes_host.py measures it).  Three
+    particles at 40..70 R stretch a tree of 32 leaves until the whole ball is one another's near field: late at p = 10 (32 leaves by
+    the formula) has a far part of 0 % of max |psi|, late at n = 4001 with tree_L = 5 of 3 %.  So late at p = 10 runs with
+    tree_L = 8 (77 % of the particles above the 10 %), and the uneven last tile (125 / 126 per leaf) runs on plane_off (88 %)."""
+    tied = dict(eps2=EPS2_TIED)
+    rows = [(s, 4096, 4, {}) for s in ("gauss", "plane", "plane_off", "line", "lattice", "late", "ejected", "two_clumps", "zeros", "offset")]
+    rows += [(s, 4096, 4, tied) for s in ("dup2", "dup8", "dup16", "quant16")]
+    rows += [("plane", 4096, 10, dict(far_fp64=1)), ("late", 4096, 10, dict(far_fp64=1, tree_L=8))]
+    rows += [("line", 8000, 6, {}), ("dup8", 8000, 6, tied)]
+    rows += [("plane", 4096, 4, dict(tree_L=5)), ("dup16", 4096, 4, dict(tree_L=5, **tied)), ("plane_off", 4001, 4, dict(tree_L=5))]
+    rows += [("plane_off", 4096, 4, dict(unsort=0)), ("late", 4096, 4, dict(p2p_mutual=1, unsort=0)), ("line", 4096, 4, dict(m2l_first=1)),
+             ("ejected", 4096, 4, dict(coll=0))]
+    rows += [("dup64", 4096, 4, dict(tree_radius=1e6))]
+    return rows
+
+
+ENERGY_SHAPE_CASES = energy_shape_cases()
+# the rows that claim more than 64 per leaf: tree_L = 5, and plane at p = 10 by the level formula
+ENERGY_WIDE_LEAVES = [r for r in ENERGY_SHAPE_CASES if r[3].get("tree_L") == 5 or (r[2] == 10 and not r[3].get("tree_L"))]
+
+
+def energy_id(row):
+    shape, n, p, opts = row
+    return "-".join(["%s-%d-p%d" % (shape, n, p)] + ["%s=%g" % kv for kv in sorted(opts.items())])
+
+
+def energy_all_near(row):
+    return row[3].get("tree_radius", 1.0) > 1e3
+
+
+def energy_opts(row):
+    """a row's Engine options, fmm_order included"""
+    return dict(ENERGY_BASE, fmm_order=row[2], **row[3])
+
+
+def energy_oracle_kw(oracle, row):
+    """run_oracle's keywords for a row: the oracle has no tree_L, and takes its levels from dens_inhom * n / p^2 -- a power of two
+    there moves the level count by whole levels; far_fp64 and p2p_mutual change no tree and no list"""
+    _, n, p, _ = row
+    o = energy_opts(row)
+    kw = dict(radius=o["tree_radius"], eps2=o["eps2"], coll=bool(o["coll"]), unsort=bool(o["unsort"]), m2l_first=o["m2l_first"])
+    if o["tree_L"]:
+        kw["dens_inhom"] = 2.0 ** (o["tree_L"] - oracle.lib.oracle_kd_levels(n, p, 1.0))
+    return kw
+
+
+def energy_floor(oracle32, oracle64, row):
+    """What the METHOD gives on a row, from the fp32 oracle's tree and no device output, once per process: dict of
+      tree, pos     the fp32 oracle's tree and the positions in its order
+      near, far     the two parts of the restated psi (energy3d_numpy.psi_parts), tree order; None on the all-near-field row
+      exact         param0 * the fp64 pair sum, tree order
+      energy        oracle64.energy of the state: kinetic, elastic, Coulomb
+      floor_energy  |0.5 sum psi - energy[2]| / energy[2]
+      floor_mean    mean_i |psi_i - exact_i| / exact_i"""
+    import energy3d_numpy as e3
+    key = ("energy_floor", energy_id(row))
+    if key in _cache:
+        return _cache[key]
+    shape, n, p, _ = row
+    o = energy_opts(row)
+    eps2 = np.float32(o["eps2"])
+    buf, par = state(oracle32, shape, n), oracle32.params(n)
+    kw = energy_oracle_kw(oracle32, row)
+    _, pv, t = run_oracle(oracle32, "kd", buf, par, p, **kw)
+    pos = buf[0][t["perm"]] if kw["unsort"] else pv[0]
+    r = {"tree": t, "pos": pos, "buf": buf, "par": par, "near": None, "far": None}
+    r["exact"] = float(par[0]) * e3.pair_potential(pos, eps2)
+    r["energy"] = oracle64.energy(buf.astype(np.float64), par.astype(np.float64), eps2=float(eps2), threads=THREADS)
+    if not energy_all_near(row):
+        with np.errstate(all="ignore"):
+            r["near"], r["far"] = e3.psi_parts(t, pos, p, eps2, par[0], coll=kw["coll"])
+        psi = r["near"] + r["far"]
+        # (a coll = 0 evaluation leaves the near field out: its floors are the near field's share, and its sharp test is the restatement)
+        r["floor_energy"] = float(abs(0.5 * psi.sum() - r["energy"][2]) / r["energy"][2])
+        r["floor_mean"] = float(np.mean(np.abs(psi - r["exact"]) / r["exact"]))
+    _cache[key] = r
+    return r
+
+
+# Bond order: the neighbour radius per shape as (factor, length), at the sizes of bond_shape_n.  Lengths, in the units of the state:
+#   "box"   the longest side of the shape's bounding box over the ball's (the scale of test_tree_is_exact_is_reference_on_every_shape)
+#   "ball"  1: the ball's own scale, where a few outliers (or a second clump) set the bounding box
+#   "grid"  one grid spacing: R / m on the lattice of side m, R / 16 on quant16 (R = the ball's largest |coordinate|)
+# 0.002 box is the middle window of the pair statistics.  line: 0.002 gives several hundred neighbours, 0.0006 gives 199.  lattice:
+# 1.5 spacings take the 6 + 12 first and second neighbours.  quant16: 1.2 spacings take the 6 face cells only (the 12 edge cells at
+# 1.41 spacings bring 698 neighbours at n = 4001), and even those hold 340 particles at n = 4001: the shape runs at n = 2001 (166).
+# dup64 / dup128: 64 / 32 distinct points, so nb is a multiple of 64 / 128; 0.002 box links 704 particles of dup64 and no radius
+# links a quarter of dup128 with fewer than two other points in reach.
+# test_energy_shapes_host.py asserts of every row: nb_max <= 256, a quarter of the particles linked, one isolated (lattice: none).
+BOND_SHAPE_RMAX = {
+    "gauss": (0.002, "box"), "plane": (0.002, "box"), "plane_off": (0.002, "box"), "line": (0.0006, "box"), "lattice": (1.5, "grid"),
+    "quant16": (1.2, "grid"), "dup2": (0.002, "box"), "dup8": (0.002, "box"), "dup16": (0.002, "box"), "dup64": (0.002, "ball"),
+    "late": (0.002, "ball"), "two_clumps": (0.002, "ball"), "offset": (0.002, "box"), "dup128": (0.0017, "ball"), "ejected": (0.002, "ball"),
+    "zeros": (0.002, "box"), "quant2048": (0.002, "box"),
+}
+BOND_COINCIDENT = ("quant16", "dup2", "dup8", "dup16", "dup64", "dup128")          # shapes with pairs at r2 = 0
+
+
+def bond_shape_n(name):
+    """the sizes of test_tree_is_exact_is_reference_on_every_shape, but for quant16 (above)"""
+    return 3375 if name == "lattice" else 4096 if name.startswith("dup") else 2001 if name == "quant16" else 4001
+
+
+def bond_rmax(oracle32, name):
+    n = bond_shape_n(name)
+    factor, length = BOND_SHAPE_RMAX[name]
+    gauss = state(oracle32, "gauss", n)[0]
+    if length == "box":
+        pos = state(oracle32, name, n)[0]
+        return factor * float((pos.max(0) - pos.min(0)).max() / (gauss.max(0) - gauss.min(0)).max())
+    if length == "ball":
+        return factor
+    assert length == "grid" and name in ("lattice", "quant16")
+    return factor * float(np.abs(gauss).max()) / (lattice_side(n) if name == "lattice" else 16)
+
+
+def bond_model(oracle32, name):
+    """(pos, rmax, bond_numpy.bond_order, pairs inside, pairs at r2 = 0) of a shape, once per process"""
+    import bond_numpy as BN
+    import pairstat_numpy as PN
+    key = ("bond", name)
+    if key not in _cache:
+        pos = np.ascontiguousarray(state(oracle32, name, bond_shape_n(name))[0])
+        rmax = bond_rmax(oracle32, name)
+        r2, _ = PN.inside_pairs(pos, rmax)
+        _cache[key] = (pos, rmax, BN.bond_order(pos, rmax), len(r2), int((r2 == 0).sum()))
+    return _cache[key]

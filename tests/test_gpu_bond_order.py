@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import bond_numpy as BN
+import shapes3d
 
 pytestmark = pytest.mark.gpu
 
@@ -183,6 +184,40 @@ def test_tree_form_and_pair_statistics_see_the_same_walk(engine_lib, name, opts,
     lonely = nn2 == np.inf
     assert np.array_equal(nb == 0, lonely)
     assert s.isolated == lonely.sum() and s.bonds == 2 * counts[0]
+
+
+@pytest.mark.parametrize("shape", shapes3d.SHAPES)
+def test_tree_and_exact_forms_on_every_shape(eng, engine_lib, oracle32, shape):
+    """flat, collinear, tied, duplicated, stretched and late-run inputs (the sizes of the pair statistics' shape test, the radii of
+    shapes3d.BOND_SHAPE_RMAX, whose premises test_energy_shapes_host.py asserts): both forms against the model, the same nb from
+    both, and the tree form once more with tree_L = 3, where a leaf of about 500 particles takes eight staging rounds.  On dup8 and
+    quant16 the identity of test_tree_form_and_pair_statistics_see_the_same_walk with coincident points: the pair visitor counts a
+    pair at r2 = 0 (j != s), the bond visitor does not (0 < r2), so sum nb = 2 (pairs inside - pairs at r2 = 0), the second count
+    from the numpy model."""
+    import torch
+    from coulomb_oscillators_amd import Engine
+    pos, rmax, m, inside, zero = shapes3d.bond_model(oracle32, shape)
+    assert m["nb_max"] <= 256
+    n = len(pos)
+    d = dev(pos)
+    ex, tr = run(eng, "exact", d, n, rmax), run(eng, "tree", d, n, rmax)
+    check(ex, m, (shape, "exact"))
+    check(tr, m, (shape, "tree"))
+    assert np.array_equal(ex[0], tr[0])
+    e = Engine(tree_L=3)
+    try:
+        t3 = run(e, "tree", d, n, rmax)
+        check(t3, m, (shape, "tree_L=3"))
+        if shape in ("dup8", "quant16"):
+            assert zero > 0
+            counts = e.pair_hist_tree(d, n, 1, rmax)
+            torch.cuda.synchronize()
+            counts = [int(v) for v in counts.cpu().numpy()]
+            assert counts[0] == inside and sum(counts) == n * (n - 1) // 2
+            assert int(t3[0].sum()) == 2 * (counts[0] - zero) and t3[2].bonds == 2 * (counts[0] - zero)
+    finally:
+        e.close()
+    assert np.array_equal(d.cpu().numpy(), pos)
 
 
 def test_tree_form_on_the_bcc_lattice(eng):
