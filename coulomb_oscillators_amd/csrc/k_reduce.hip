@@ -6,6 +6,7 @@
 #include "nbco_internal.hpp"
 #include "host_util.hpp"
 #include "bond_order.hpp"
+#include "structure_factor.hpp"
 #include <algorithm>
 #include <cfloat>
 
@@ -185,6 +186,7 @@ static int grid_for(long long n)
 #define NBCO_BOND_EXACT
 #include "bond_order_kernels.hpp"   // bond-orientational order: the all-pairs kernel, the wave records of the summary and their sum
 #undef NBCO_BOND_EXACT
+#include "structure_factor_kernels.hpp"   // the static structure factor: the tile kernel and the sum over the particle ranges
 
 } // namespace
 
@@ -520,6 +522,90 @@ int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R
 	});
 	NBCO_HIP(hipGetLastError());
 	return sum_host ? bond_summary_finish(c, rec, records, n, dim, sum_host) : NBCO_OK;
+}
+
+// ---- static structure factor (structure_factor_kernels.hpp) -----------------------------------------
+// The shape of a call, from n and the grid alone (never from the device): runs of ix of at most kSkMaxAcc, the cut of the items into
+// workgroups (the fewest workgroups that keep 85 % of the lanes busy with `copies` copies of `lanes` items each, else the best cut up to
+// four times as many), the tile that fills the LDS budget, and the particle ranges -- at least 512 particles each, no more of them than bring the launch to about 2048 workgroups
+// or the partial sums to 256 MiB.
+static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g)
+{
+	SkShape s;
+	s.hx = g.h[0]; s.hy = g.h[1]; s.hz = dim == 3 ? g.h[2] : 0;
+	s.nch = (s.hx + kSkMaxAcc) / kSkMaxAcc;
+	s.L = (s.hx + s.nch) / s.nch;
+	s.ny = 2 * s.hy + 1; s.nz = 2 * s.hz + 1;
+	s.items = s.nch * s.ny * s.nz;
+	s.K = sk_count(g.h, dim);
+	const int per = 1 + (s.hy + 1) + (dim == 3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0);   // complex numbers per particle
+	s.tile = std::min(kSkBlock, kSkLdsBytes / (16 * per));
+	const int kt0 = (s.items + kSkBlock - 1) / kSkBlock;
+	int kt = kt0;
+	double best = 0.0;
+	for (int t = kt0; t <= 4 * kt0; ++t)
+	{
+		const int lanes = (s.items + t - 1) / t, copies = kSkBlock / lanes;
+		const double busy = (double)s.items * copies / ((double)t * kSkBlock);
+		if (busy > best) { best = busy; kt = t; }
+		if (busy >= 0.85) break;
+	}
+	s.lanes = (s.items + kt - 1) / kt;
+	s.copies = s.lanes <= kSkBlock / 2 ? kSkBlock / s.lanes : 1;
+	long long r0 = std::min((n + 511) / 512, std::max(1LL, (long long)(2048 / kt)));
+	r0 = std::max(1LL, std::min(r0, (256LL << 20) / (16 * s.K)));
+	s.range = ((n + r0 - 1) / r0 + 63) / 64 * 64;
+	s.wx = g.kstep[0] / kSkTwoPi; s.wy = g.kstep[1] / kSkTwoPi; s.wz = dim == 3 ? g.kstep[2] / kSkTwoPi : 0.0;
+	return s;
+}
+
+template <bool DIM3, typename T>
+static int sk_run(nbco_ctx *c, const T *p, long long n, const SkShape &s, double *rho)
+{
+	const long long ranges = (n + s.range - 1) / s.range;
+	double *out = rho;
+	if (ranges > 1)
+	{
+		NBCO_TRY(c->reserve(c->sk_part, sizeof(double) * 2 * (size_t)s.K * (size_t)ranges));
+		out = c->sk_part.as<double>();
+	}
+	const int per = 1 + (s.hy + 1) + (DIM3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0);
+	const size_t lds = (size_t)16 * per * s.tile;
+	const dim3 grid((unsigned)((s.items + s.lanes - 1) / s.lanes), (unsigned)ranges), block(kSkBlock);
+#define NBCO_SK_STEP(A_) hipLaunchKernelGGL((sk_accumulate_kernel<A_, DIM3, T>), grid, block, lds, c->stream, p, n, s, out)
+	// the template steps of the run length L
+	if (s.L <= 1) NBCO_SK_STEP(1);
+	else if (s.L <= 2) NBCO_SK_STEP(2);
+	else if (s.L <= 3) NBCO_SK_STEP(3);
+	else if (s.L <= 5) NBCO_SK_STEP(5);
+	else if (s.L <= 9) NBCO_SK_STEP(9);
+	else if (s.L <= 13) NBCO_SK_STEP(13);
+	else NBCO_SK_STEP(17);
+#undef NBCO_SK_STEP
+	NBCO_HIP(hipGetLastError());
+	if (ranges > 1)
+	{
+		hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)((2 * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, 2 * s.K, rho);
+		NBCO_HIP(hipGetLastError());
+	}
+	return NBCO_OK;
+}
+
+int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, const nbco_sk_grid &g, double *rho, long long *n_used_host)
+{
+	const SkShape s = sk_shape(dim, n, g);
+	if (dim == 3) NBCO_TRY((sk_run<true, float>(c, (const float *)p, n, s, rho)));
+	else NBCO_TRY((sk_run<false, double>(c, (const double *)p, n, s, rho)));
+	if (n_used_host)
+	{
+		// rho at k = 0 is the exact count of the particles that counted
+		const size_t k0 = (size_t)s.hy * (size_t)s.nz + (size_t)s.hz;
+		double cnt = 0;
+		NBCO_HIP(hipMemcpyAsync(&cnt, rho + 2 * k0, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+		NBCO_HIP(hipStreamSynchronize(c->stream));
+		*n_used_host = (long long)cnt;
+	}
+	return NBCO_OK;
 }
 
 // ---- aperture (aperture_kernels.hpp) -------------------------------------------------------------

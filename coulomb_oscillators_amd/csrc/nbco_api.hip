@@ -3,6 +3,7 @@
 // The symplectic integrators (integrator.cuh:32-167) are nbco_integrate.hip.
 #include "nbco_internal.hpp"
 #include "bond_order.hpp"
+#include "structure_factor.hpp"
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -793,6 +794,46 @@ int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, 
 {
 	NBCO_TRY(bond_args(c, "nbco_bond_order_tree", true, p, n, rmax, nb_dev, q_dev, sum_host));
 	NBCO_TRY(on_private_copy(c, "nbco_bond_order_tree", p, n, 3, [&](nbco_ctx *k, float *x) { return kd_bond_order_tree(k, x, n, rmax * rmax, nb_dev, q_dev, sum_host); }));
+	return maybe_sync(c);
+}
+
+// ---- static structure factor -------------------------------------------------------------------
+int nbco_sk_phase(double t, double *cs_host)
+{
+	if (!cs_host || !std::isfinite(t)) return NBCO_ERR_ARG;
+	const SkC e = sk_phase(t);
+	cs_host[0] = e.re;
+	cs_host[1] = e.im;
+	return NBCO_OK;
+}
+
+// what both calls refuse before any launch
+static int sk_args(nbco_ctx *c, const char *who, int dim, const void *p, long long n, const nbco_sk_grid *g, const void *rho_dev)
+{
+	if (!c) return NBCO_ERR_ARG;
+	const std::string w(who);
+	if (!p || !g || !rho_dev) return c->fail(NBCO_ERR_ARG, w + ": null pointer");
+	if (n <= 0) return c->fail(NBCO_ERR_ARG, w + ": n must be positive");
+	for (int a = 0; a < dim; ++a)
+	{
+		if (g->h[a] < 0 || g->h[a] > kSkMaxH) return c->fail(NBCO_ERR_ARG, w + ": h must be 0..64 on every axis");
+		if (!std::isfinite(g->kstep[a]) || !(g->kstep[a] > 0.0)) return c->fail(NBCO_ERR_ARG, w + ": kstep must be finite and positive on every axis");
+	}
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, w + ": n too large for 32-bit particle indices");
+	return NBCO_OK;
+}
+
+int nbco_structure_factor(nbco_ctx *c, const float *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host)
+{
+	NBCO_TRY(sk_args(c, "nbco_structure_factor", 3, p, n, g_host, rho_dev));
+	NBCO_TRY(launch_structure_factor(c, p, 3, n, *g_host, rho_dev, n_used_host));
+	return maybe_sync(c);
+}
+
+int nbco_2d_structure_factor(nbco_ctx *c, const double *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host)
+{
+	NBCO_TRY(sk_args(c, "nbco_2d_structure_factor", 2, p, n, g_host, rho_dev));
+	NBCO_TRY(launch_structure_factor(c, p, 2, n, *g_host, rho_dev, n_used_host));
 	return maybe_sync(c);
 }
 

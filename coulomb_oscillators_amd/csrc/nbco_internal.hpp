@@ -307,6 +307,7 @@ struct nbco_ctx
 	nbco_ctx *energy_child = nullptr;   // nbco_energy_tree, nbco_probe_tree: a private context for the tree they build (created on first use, freed by nbco_destroy)
 	bool drifted = false;               // nbco_integrate has moved the particles since the last kd-tree evaluation (a scheme that ends on a drift): nbco_kd_probe refuses
 	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
+	DevBuf sk_part;                     // nbco_structure_factor: the partial sums of the particle ranges
 	DevBuf ap_cnt, ap_state;            // nbco_aperture_*: the total and the levels of workgroup counts; the compacted state before it is copied back
 	DevBuf sl_keys, sl_tmp, sl_tab, sl_part;   // nbco_slice_moments: keys and permutation, the sort's and the scan's scratch, the slice table and records, the chunk slabs
 	// bookkeeping of the last evaluation
@@ -411,6 +412,8 @@ int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const Pai
 int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R2, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 // the wave records of a bond-order call (`records` of them, on the device) -> *sum_host.  Synchronises.
 int bond_summary_finish(nbco_ctx *c, const double *rec, long long records, long long n, int dim, nbco_bond_summary *sum_host);
+// static structure factor (structure_factor_kernels.hpp): 2 K doubles to rho_dev; with n_used_host the call synchronises
+int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, const nbco_sk_grid &g, double *rho_dev, long long *n_used_host);
 // aperture (aperture_kernels.hpp): the rule of a call, formed once on the host by include/nbco.h: w[a] = 1.0 / half[a]
 struct ApRule
 {

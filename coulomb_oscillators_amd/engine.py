@@ -106,6 +106,11 @@ class BondSummary(C.Structure):
                 ("q_mean", C.c_double * 2), ("Q", C.c_double * 2)]
 
 
+class SkGrid(C.Structure):
+    """nbco_sk_grid (include/nbco.h)"""
+    _fields_ = [("h", C.c_int * 3), ("kstep", C.c_double * 3)]
+
+
 ERR_CAPACITY = 3              # NBCO_ERR_CAPACITY
 
 COLL_DONE, COLL_ALLREDUCE_MIN_I32, COLL_ALLREDUCE_SUM_I32, COLL_ALLGATHER, COLL_ALLTOALL = range(5)
@@ -242,6 +247,9 @@ def _load():
         "nbco_bond_order": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
         "nbco_bond_order_tree": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
         "nbco_2d_bond_order": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
+        "nbco_structure_factor": [P, P, LL, C.POINTER(SkGrid), P, C.POINTER(LL)],
+        "nbco_2d_structure_factor": [P, P, LL, C.POINTER(SkGrid), P, C.POINTER(LL)],
+        "nbco_sk_phase": [D, C.POINTER(D)],
         "nbco_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
         "nbco_aperture_apply": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL), P, P, LL],
         "nbco_2d_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
@@ -348,6 +356,16 @@ def bond_harmonics(u):
     if rc != 0:
         raise EngineError("nbco_bond_harmonics failed with status %d" % rc, status=rc)
     return np.array(y4[:], dtype=np.float64), np.array(y6[:], dtype=np.float64)
+
+
+def sk_phase(t):
+    """(cos 2 pi t, sin 2 pi t) as the structure-factor kernels form the phase of t cycles (nbco_sk_phase, include/nbco.h): an exact
+    reduction and fixed polynomials, no libm.  Host only, needs no GPU; the one place it is formed."""
+    cs = (C.c_double * 2)()
+    rc = _load().nbco_sk_phase(float(t), cs)
+    if rc != 0:
+        raise EngineError("nbco_sk_phase failed with status %d" % rc, status=rc)
+    return cs[0], cs[1]
 
 
 def default_opts(**kw):
@@ -749,6 +767,33 @@ class Engine:
     def bond_order_2d(self, p, n, rmax, nb=None, q=None, summary=True):
         """the exact form for the 2-D fp64 positions (xy pairs; nbco_2d_bond_order): q holds |psi4| and |psi6|, the hexatic order"""
         return self._bond_order(self.lib.nbco_2d_bond_order, p, n, rmax, nb, q, summary)
+
+    # ---- static structure factor -------------------------------------------------------------------
+    def _structure_factor(self, fn, dim, p, n, h, kstep, rho, count):
+        g = SkGrid()
+        for a in range(dim):
+            g.h[a] = int(h[a])
+            g.kstep[a] = float(kstep[a])
+        if rho is None:
+            ok = all(0 <= int(h[a]) <= 64 for a in range(dim))   # (the library refuses the call; nothing is sized by a bad h)
+            K = (int(h[0]) + 1) * (2 * int(h[1]) + 1) * (2 * int(h[2]) + 1 if dim == 3 else 1) if ok else 0
+            rho = self.torch.empty(K, dtype=self.torch.complex128, device=p.device)
+        used = C.c_longlong(0)
+        self._chk(fn(self.ctx, _ptr(p), n, C.byref(g), _ptr(rho), C.byref(used) if count else None))
+        return rho, (used.value if count else None)
+
+    def structure_factor(self, p, n, h, kstep, rho=None, count=True):
+        """rho_k = sum_j exp(i k . x_j) of the n positions p (float32 xyz triplets; the head of a state works) on the grid
+        k = (ix kstep[0], iy kstep[1], iz kstep[2]), ix = 0..h[0], iy = -h[1]..h[1], iz = -h[2]..h[2] (nbco_structure_factor).
+        Returns (rho, n_used): rho a complex128 device tensor of K = (h[0]+1)(2 h[1]+1)(2 h[2]+1) values at index
+        (ix (2 h[1]+1) + iy + h[1]) (2 h[2]+1) + iz + h[2] (allocated if None, overwritten if given), n_used the number of particles
+        that counted (those with finite coordinates); rho at k = 0 is exactly n_used.  count=False returns n_used = None and does
+        not synchronise.  S(k) = |rho|^2 / n_used is the caller's.  p is not modified."""
+        return self._structure_factor(self.lib.nbco_structure_factor, 3, p, n, h, kstep, rho, count)
+
+    def structure_factor_2d(self, p, n, h, kstep, rho=None, count=True):
+        """the same for the 2-D fp64 positions (xy pairs; nbco_2d_structure_factor): K = (h[0]+1)(2 h[1]+1), index ix (2 h[1]+1) + iy + h[1]"""
+        return self._structure_factor(self.lib.nbco_2d_structure_factor, 2, p, n, h, kstep, rho, count)
 
     # ---- aperture ---------------------------------------------------------------------------------
     @staticmethod

@@ -5,7 +5,8 @@
 // Additions: -energy writes the energies of every snapshot to energy.txt (nbco_2d_energy_fmm); -probes <file> writes the field and
 // the potential at the file's points for every snapshot (nbco_2d_probe_fmm); -moments writes the beam's phase-space moments of every
 // snapshot to moments.txt (nbco_2d_beam_moments); -slices writes them per slice along one coordinate to slices<iter>_<ds>.txt
-// (nbco_2d_slice_moments); without them nothing changes.
+// (nbco_2d_slice_moments); -sk writes the static structure factor of every snapshot to sk<iter>_<ds>.bin and sk.txt
+// (nbco_2d_structure_factor); without them nothing changes.
 // Deviations: -cpu / -cpu-threads are refused (main.cu -cpu runs a host FMM, which this product does not have); -gpu, -gridsize
 // and -cacheline are validated as main.cu does and then have no effect; -p above 10 is refused by the library (NBCO_ERR_ARG).
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include <vector>
 #include "../../include/nbco.h"
 #include "slices_file.hpp"
+#include "sk_file.hpp"
 
 namespace {
 
@@ -64,6 +66,11 @@ const char *kHelp =
     "                    `# outside <k>` counts the particles outside the window, then one line per slice: `s lo_s n`,\n"
     "                    the 4 means, then per plane `sig_q sig_p cov_qp emit halo_q halo` of the slice's particles\n"
     "                    alone (an empty slice: zeros); no effect with -test\n"
+    "  -sk <hx> <hy> <kx> <ky>\n"
+    "                    at every snapshot write the static structure factor of the positions to <dir>/sk<iter>_<ds>.bin\n"
+    "                    (nbco_2d_structure_factor): K x 2 doubles {re, im} of rho_k = sum_j exp(i k . x_j), k = (ix kx, iy ky),\n"
+    "                    ix = 0..hx, iy = -hy..hy (h <= 64), K = (hx+1)(2hy+1), index ix (2hy+1) + iy + hy; and append\n"
+    "                    `iter n_used S_max ix iy` to <dir>/sk.txt: the largest |rho_k|^2 / n_used over k != 0\n"
     "  -probes <file>    binary file of probe points as pairs of doubles (M = file size / 16).  At every snapshot\n"
     "                    write <dir>/probes<iter>_<ds>.bin: the M accelerations (pairs) and then the M potentials\n"
     "                    of the snapshot's particles at these points (nbco_2d_probe_fmm, order -p; the points feel\n"
@@ -115,6 +122,7 @@ int main(const int argc, const char **argv)
 	bool in = false, cpu = false, test = false, ga = false, calc_u = false, calc_omega = false, coll = true, energy = false, moments = false;
 	bool aperture = false;
 	SlicesOpt slices;
+	SkOpt sk;
 	nbco_aperture ap{NBCO_AP_ELLIPSOID, {0, 0, 0}, {0, 0, 0}};
 
 	// KV parameters matched to the emittances (main.cu:271-313)
@@ -250,6 +258,12 @@ int main(const int argc, const char **argv)
 			if (!parse_slices(2, argv[i + 1], argv[i + 2], argv[i + 3], argv[i + 4], slices))
 				return fail("Error: invalid argument(s) to " + opt + ": " + argv[i + 1] + " " + argv[i + 2] + " " + argv[i + 3] + " " + argv[i + 4] +
 				            " (x, y, vx or vy, 1..65536 bins, lo below hi, both finite)\n");
+			i += 4;
+		}
+		else if (is(a, "sk"))
+		{
+			if (need(i, 4, a)) return missing2();
+			if (!parse_sk(2, argv + i + 1, sk)) return fail("Error: invalid argument(s) to " + opt + " (hx hy: integers 0..64; kx ky: finite and greater than 0)\n");
 			i += 4;
 		}
 		else if (is(a, "probes")) { if (need(i, 1, a)) return missing(); strprobes = argv[++i]; }
@@ -422,6 +436,10 @@ int main(const int argc, const char **argv)
 		std::fflush(fmo);
 	}
 	std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
+	// -sk: rho on the device, its host copy and <dir>/sk.txt
+	double *d_rho = nullptr;
+	std::vector<double> rho_host(sk.on ? 2 * (size_t)sk.K : 0);
+	SkLog sklog(2, sk, strout);
 	std::vector<double> pout;
 	if (nprobes > 0)
 	{
@@ -446,6 +464,7 @@ int main(const int argc, const char **argv)
 		if (flo) std::fclose(flo);
 		if (d_lost) (void)hipFree(d_lost);
 		if (d_lost_row) (void)hipFree(d_lost_row);
+		if (d_rho) (void)hipFree(d_rho);
 		return done(code);
 	};
 	if (aperture)
@@ -525,6 +544,19 @@ int main(const int argc, const char **argv)
 				long long outside = 0;
 				if (!lib_ok(nbco_2d_slice_moments(ctx, d_buf, n, &slices.axis, slice_recs.data(), &outside))) return finish(-1);
 				if (!write_slices(strout, iter, std::to_string(dt), 2, slices.axis, slice_recs.data(), outside))
+				{
+					std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
+					return finish(-1);
+				}
+			}
+			if (sk.on)
+			{
+				long long n_used = 0;
+				if ((!d_rho && !hip_ok(hipMalloc(&d_rho, sizeof(double) * rho_host.size()))) ||
+				    !lib_ok(nbco_2d_structure_factor(ctx, d_buf, n, &sk.g, d_rho, &n_used)) ||
+				    !hip_ok(hipMemcpy(rho_host.data(), d_rho, sizeof(double) * rho_host.size(), hipMemcpyDeviceToHost)))
+					return finish(-1);
+				if (!sklog.record(iter, std::to_string(dt), rho_host, n_used))
 				{
 					std::cerr << "Error: cannot write on output location. Check that \"" << strout << "\" folder exists. Create it if not." << std::endl;
 					return finish(-1);

@@ -23,6 +23,7 @@
 #include "nbco_reference_api.hpp"
 #include "nbco_cpu.hpp"
 #include "slices_file.hpp"
+#include "sk_file.hpp"
 
 using namespace nbco_ref;
 using namespace std::chrono;
@@ -91,12 +92,18 @@ const char *kHelp =
     "                    q6_mean Q4 Q6' to <output>/bonds.txt.  From a range-limited kd-tree walk of its own (nbco_bond_order_tree; with -cpu:\n"
     "                    all pairs on the host, the same neighbour rule and harmonics: the same nb, q to rounding).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -sk <hx> <hy> <hz> <kx> <ky> <kz>   At every snapshot write the static structure factor of the positions to <output>/sk<iter>_<ds>.bin:\n"
+    "                    K x 2 doubles {re, im} of rho_k = sum_j exp(i k . x_j) on the grid k = (ix kx, iy ky, iz kz), ix = 0..hx, iy = -hy..hy,\n"
+    "                    iz = -hz..hz (h <= 64), K = (hx+1)(2hy+1)(2hz+1), at index ((ix)(2hy+1) + iy + hy)(2hz+1) + iz + hz, and append\n"
+    "                    'iter n_used S_max ix iy iz' to <output>/sk.txt: the largest |rho_k|^2 / n_used over k != 0 and where it sits\n"
+    "                    (nbco_structure_factor; with -cpu the same rule from the same header on the host: equal to rounding).\n"
+    "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -aperture <ellipsoid|box> <hx> <hy> <hz>   At every snapshot iteration, after the step and before the snapshot, drop the particles\n"
     "                    outside the aperture with these half axes ('inf' opens an axis: pipes, slabs) from the run: they are lost and no\n"
     "                    longer simulated (nbco_aperture_apply; with -cpu the same rule on the host).  Per snapshot\n"
     "                    <output>/lost<iter>_<ds>.bin receives k int32 rows (the rows the lost particles had in the state; with\n"
     "                    -snapshot-order input their particle numbers), then k x 6 floats x y z vx vy vz -- empty when nobody was lost --\n"
-    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs, -bonds\n"
+    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs, -bonds, -sk\n"
     "                    describe the survivors; the snapshot files shrink with n.  A run that loses everybody ends with an error.\n"
     "                    Refused with -test, -test2 and -accuracy.\n"
     "  -aperture-centre <cx> <cy> <cz>   Centre of the aperture (default 0 0 0).\n"
@@ -394,7 +401,7 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const ApertureOpt &aperture,
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const SkOpt &sk, const ApertureOpt &aperture,
 	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath)
 	{
 		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
@@ -419,6 +426,10 @@ struct Session
 		std::vector<int> bonds_nb_host(bond_n), bonds_nb_rows(input_order ? bond_n : 0);
 		std::vector<double> bonds_q_host(2 * bond_n), bonds_q_rows(input_order ? 2 * bond_n : 0);
 		BondsLog blog(bonds_rmax, folder);
+		// -sk: rho on the device and the host copy that goes into the file
+		DeviceArray<double> sk_rho(sk.on ? 2 * (size_t)sk.K : 0);
+		std::vector<double> sk_rho_host(sk.on ? 2 * (size_t)sk.K : 0);
+		SkLog sklog(3, sk, folder);
 		EnergyLog elog(energy, folder);
 		MomentsLog mlog(moments, folder);
 		// -probes: the points and their results [field m x 3 | potential m] on the device, and the host copy that goes into the files
@@ -591,6 +602,18 @@ struct Session
 				}
 				else if (!blog.record(snap, dt, bonds_nb_host, bonds_q_host, bsum)) return -1;
 			}
+			if (sk.on)
+			{
+				// a sum over the particles: the order of the state does not matter to it
+				long long n_used = 0;
+				check(nbco_structure_factor(ctx(), state.ptr, n, &sk.g, sk_rho.ptr, &n_used), "structure_factor");
+				HIPCHK(hipMemcpy(sk_rho_host.data(), sk_rho.ptr, sk_rho_host.size() * sizeof(double), hipMemcpyDeviceToHost));
+				if (!sklog.record(snap, std::to_string(dt), sk_rho_host, n_used))
+				{
+					std::cerr << "Error: cannot write the structure factor files of iteration " << snap << " into \"" << folder << "\"" << std::endl;
+					return -1;
+				}
+			}
 			if (snap == 0) { loop_t0 = std::chrono::steady_clock::now(); loop_first = 1; }   // the timer below starts behind the first snapshot
 		}
 		check(nbco_sync(ctx()), "sync");
@@ -619,6 +642,7 @@ int main(int argc, const char **argv)
 	std::vector<float> probes;
 	PairsOpt pairs;
 	double bonds_rmax = 0;
+	SkOpt sk;
 	ApertureOpt aperture;
 	SlicesOpt slices;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false, bfield = false;
@@ -774,6 +798,16 @@ int main(int argc, const char **argv)
 				return -1;
 			}
 			++i;
+		}
+		else if (a == "-sk")
+		{
+			if (!need(i, 6, "-sk")) return -1;
+			if (!parse_sk(3, argv + i + 1, sk))
+			{
+				std::cerr << "Error: invalid argument(s) to '-sk' (hx hy hz: integers 0..64; kx ky kz: finite and greater than 0)\n";
+				return -1;
+			}
+			i += 6;
 		}
 		else if (a == "-aperture")
 		{
@@ -953,6 +987,8 @@ int main(int argc, const char **argv)
 		std::vector<int> bonds_nb;
 		std::vector<double> bonds_q;
 		BondsLog blog(bonds_rmax, strout);
+		std::vector<double> sk_rho;
+		SkLog sklog(3, sk, strout);
 		LossLog llog(aperture.on, strout);
 		std::vector<int> lost_rows;
 		std::vector<float> lost_recs;
@@ -1022,6 +1058,15 @@ int main(int argc, const char **argv)
 				nbco_cpu::bond_order(st.data(), nBodies, bonds_rmax, bonds_nb, bonds_q, bsum);
 				if (!blog.record(iter, dt, bonds_nb, bonds_q, bsum)) return -1;
 			}
+			if (sk.on)
+			{
+				const long long n_used = nbco_cpu::structure_factor(st.data(), nBodies, sk.g, sk_rho);
+				if (!sklog.record(iter, std::to_string(dt), sk_rho, n_used))
+				{
+					std::cerr << "Error: cannot write the structure factor files of iteration " << iter << " into \"" << strout << "\"" << std::endl;
+					return -1;
+				}
+			}
 		}
 		std::cout << std::endl;
 		return 0;
@@ -1035,7 +1080,7 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
+		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, b_accuracy ? SkOpt{} : sk, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
 		                     b_accuracy ? nbco_bath{} : bath);
 	}
 	return rc;

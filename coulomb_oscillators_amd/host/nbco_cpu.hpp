@@ -15,6 +15,7 @@
 #include "../../include/nbco.h"
 #include "../csrc/integ_compose.hpp"
 #include "../csrc/bond_order.hpp"
+#include "../csrc/structure_factor.hpp"
 
 namespace nbco_cpu {
 
@@ -265,6 +266,56 @@ inline void bond_order(const V3 *x, int n, double rmax, std::vector<int> &nb, st
 	}
 	sum = nbco_bond_summary{};
 	bond_summary_fill(S, qsum, bonds, isolated, top, n, 3, sum);
+}
+
+// The static structure factor of the positions x[0..n) for `nbco3 -cpu -sk`, by the rule of nbco_structure_factor (include/nbco.h) from
+// csrc/structure_factor.hpp, the header the device kernels use: the phases sk_phase(t_a), the powers and the products by sk_mul, the
+// term (e_y^iy e_z^iz) e_x^ix with one multiplication per ix.  rho gets K pairs {re, im}; returns the number of particles that counted.
+// A fixed partition: every worker owns a range of columns (iy, iz) and adds all particles in index order, in blocks of 64 whose tables
+// it forms itself, so the bytes do not depend on the number of threads.  The device adds in another order: equal to rounding only.
+inline long long structure_factor(const V3 *x, int n, const nbco_sk_grid &g, std::vector<double> &rho)
+{
+	const int hx = g.h[0], hy = g.h[1], hz = g.h[2], ny = 2 * hy + 1, nz = 2 * hz + 1, cols = ny * nz;
+	const double w[3] = {g.kstep[0] / kSkTwoPi, g.kstep[1] / kSkTwoPi, g.kstep[2] / kSkTwoPi};
+	rho.assign(2 * (size_t)sk_count(g.h, 3), 0.0);
+	double *out = rho.data();
+	for_ranges(cols, [=](int lo, int hi) {
+		constexpr int B = 64;
+		std::vector<SkC> ex(B), ty((size_t)B * (hy + 1)), tz((size_t)B * (hz + 1));
+		for (int base = 0; base < n; base += B)
+		{
+			const int cnt = std::min(B, n - base);
+			for (int j = 0; j < cnt; ++j)
+			{
+				const V3 p = x[base + j];
+				const double t0 = (double)p.x * w[0], t1 = (double)p.y * w[1], t2 = (double)p.z * w[2];
+				const bool ok = std::isfinite(t0) && std::isfinite(t1) && std::isfinite(t2);
+				const SkC zero{0.0, 0.0}, first{ok ? 1.0 : 0.0, 0.0};
+				ex[j] = ok ? sk_phase(t0) : zero;
+				SkC *py = &ty[(size_t)j * (hy + 1)], *pz = &tz[(size_t)j * (hz + 1)];
+				const SkC ey = ok ? sk_phase(t1) : zero, ez = ok ? sk_phase(t2) : zero;
+				py[0] = pz[0] = first;
+				for (int m = 1; m <= hy; ++m) py[m] = m == 1 ? ey : sk_mul(py[m - 1], ey);
+				for (int m = 1; m <= hz; ++m) pz[m] = m == 1 ? ez : sk_mul(pz[m - 1], ez);
+			}
+			for (int col = lo; col < hi; ++col)
+			{
+				const int iy = col / nz - hy, iz = col % nz - hz;
+				for (int j = 0; j < cnt; ++j)
+				{
+					SkC v = sk_mul(sk_conj_if(ty[(size_t)j * (hy + 1) + std::abs(iy)], iy < 0), sk_conj_if(tz[(size_t)j * (hz + 1) + std::abs(iz)], iz < 0));
+					for (int ix = 0; ix <= hx; ++ix)
+					{
+						double *o = out + 2 * ((size_t)ix * (size_t)cols + (size_t)col);
+						o[0] += v.re;
+						o[1] += v.im;
+						v = sk_mul(v, ex[j]);
+					}
+				}
+			}
+		}
+	});
+	return (long long)rho[2 * ((size_t)hy * nz + hz)];
 }
 
 // The aperture of `nbco3 -cpu -aperture`, by the rule of nbco_aperture_apply (include/nbco.h) in fp64 over the fp32 positions:

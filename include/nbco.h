@@ -811,6 +811,40 @@ typedef struct nbco_bond_summary {
 int nbco_bond_order(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 int nbco_2d_bond_order(nbco_ctx *c, const double *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
+/* nbco_structure_factor / nbco_2d_structure_factor: the static structure factor -- what Bragg scattering off a Coulomb crystal and the
+ * spatial spectrum of a beam's density (micro-bunching, density waves) measure.  For the wave vectors of a grid, k = (ix kstep[0],
+ * iy kstep[1], iz kstep[2]) with ix = 0..h[0], iy = -h[1]..h[1], iz = -h[2]..h[2] (the half space ix >= 0: rho_{-k} is the conjugate;
+ * the plane ix = 0 is stored whole), rho_dev receives rho_k = sum_j exp(i k . x_j) as K pairs of doubles {re, im} in DEVICE memory,
+ * K = (h[0]+1)(2 h[1]+1)(2 h[2]+1), at index ((ix)(2 h[1]+1) + (iy + h[1]))(2 h[2]+1) + (iz + h[2]).  The 2-D form reads h[0..1]
+ * and kstep[0..1]: K = (h[0]+1)(2 h[1]+1), index ix (2 h[1]+1) + (iy + h[1]), over the fp64 xy pairs.  S(k) = |rho_k|^2 / n_used is
+ * the caller's.  p is as in nbco_pair_hist and is neither modified nor reordered; *g_host lies in HOST memory.  rho_dev is
+ * overwritten, all K entries, not accumulated.  n_used_host may be NULL; with it the call synchronises and writes the number of
+ * particles that counted, without it the call returns as the evaluators do (opts.sync, opts.stream).
+ * The rule, which is the numerical contract, is written once, in csrc/structure_factor.hpp, for the kernels, nbco_sk_phase,
+ * `nbco3 -cpu -sk` and `nbco -sk`: w_a = kstep[a] / 6.283185307179586 on the host; t_a = (double) x_a * w_a, the phase in cycles; a
+ * particle counts iff every t_a is finite (for kstep below 1e269: iff every coordinate is finite) and otherwise contributes nothing
+ * to any k; e_a = phase(t_a) from an exact reduction to |theta| <= pi/4 and fixed polynomials in fixed fma order -- no libm or ocml
+ * trigonometry, the same operations on host and device, each component within 4 * 2^-53 of the true value, exact at the multiples
+ * of a quarter turn; powers by repeated complex multiplication from (1, 0), the conjugate for negative indices; the term is
+ * (e_y^iy e_z^iz) e_x^ix, the last factor applied one multiplication per ix; one fma order for the complex product.  rho at k = 0 is
+ * exactly (n_used, 0).  nbco_sk_phase exports the phase: cs_host = {cos 2 pi t, sin 2 pi t}; host only, no GPU needed; NBCO_ERR_ARG
+ * for a NULL cs_host or a non-finite t.
+ * Determinism: every sum has a fixed order and there are no float atomics; the particles are cut into ranges by n and the grid alone,
+ * never by the device, so a second call returns the same bytes, on any stream, in either opts.sync setting and on any card.
+ * THE DEVICE AND `nbco3 -cpu -sk` AGREE ONLY TO ROUNDING, NOT BIT FOR BIT (they add the particles in different orders): within
+ * n u (8 (h[0]+h[1]+h[2]+1) + n), u = 2^-53, of the exact sums of the rule's t, and far closer in practice.
+ * Refused before any launch, the outputs untouched: with NBCO_ERR_ARG a NULL c, p, g_host or rho_dev, n <= 0, any h[a] < 0 or > 64,
+ * any kstep[a] not finite or <= 0; with NBCO_ERR_UNSUPPORTED n >= 2^31.
+ * State: the partial sums of the particle ranges live in scratch of the call's own (at most 256 MiB: the number of ranges is bounded
+ * by it, no grid is refused for it).  The tree, the rebuild schedule, the warm-select history, the order tracking, nbco_kd_get_info
+ * and a valid nbco_energy_fmm / nbco_kd_potential / nbco_kd_probe stay as they were; a following call returns the bits it would
+ * have returned.
+ * Not offered: arbitrary k lists, weights, the dynamic S(k, omega), the shell average S(|k|) and the division by n (fold on the
+ * host), and sharded runs (add the rho of the shards). */
+typedef struct nbco_sk_grid { int h[3]; double kstep[3]; } nbco_sk_grid;      /* HOST memory; 2-D reads [0..1] */
+int nbco_structure_factor(nbco_ctx *c, const float *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host);
+int nbco_2d_structure_factor(nbco_ctx *c, const double *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host);
+int nbco_sk_phase(double t, double *cs_host);
 /* ---- aperture: particles that cross a boundary (a pipe wall, an electrode) are lost -- dropped from the state on the device,
  * recorded, and no longer simulated.  nbco_aperture_count / nbco_aperture_apply serve the 3-D fp32 state, the nbco_2d_ forms the
  * 2-D fp64 state (they read centre[0..1] and half[0..1] only).  *ap_host lies in HOST memory.
