@@ -7,6 +7,7 @@
 #include "host_util.hpp"
 #include "bond_order.hpp"
 #include "structure_factor.hpp"
+#include "time_corr.hpp"
 #include <algorithm>
 #include <cfloat>
 
@@ -187,6 +188,7 @@ static int grid_for(long long n)
 #include "bond_order_kernels.hpp"   // bond-orientational order: the all-pairs kernel, the wave records of the summary and their sum
 #undef NBCO_BOND_EXACT
 #include "structure_factor_kernels.hpp"   // the static structure factor: the tile kernel and the sum over the particle ranges
+#include "time_corr_kernels.hpp"          // tracked trajectories: the recording passes, the correlation kernel and the sum over the row ranges
 
 } // namespace
 
@@ -604,6 +606,66 @@ int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, co
 		NBCO_HIP(hipMemcpyAsync(&cnt, rho + 2 * k0, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
 		NBCO_HIP(hipStreamSynchronize(c->stream));
 		*n_used_host = (long long)cnt;
+	}
+	return NBCO_OK;
+}
+
+// ---- tracked trajectories and their time correlations (time_corr_kernels.hpp) -----------------------
+int launch_traj_record(nbco_ctx *c, const float *buf, long long n, const int *ids, float *traj, long long rows, int frames_cap, int frame, int stride)
+{
+	hipLaunchKernelGGL(traj_fill_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, traj, rows, (long long)frames_cap, frame);
+	NBCO_HIP(hipGetLastError());
+	hipLaunchKernelGGL(traj_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, buf, n, ids, traj, rows, (long long)frames_cap, frame, stride);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// The shape of a call, from (rows, frames, lags) alone (never from the device): the lags a lane keeps (1 up to 64 lags, else pairs: 2 up
+// to 512 lags, 4 up to 1024, 8 beyond), the lanes of a row (a multiple of 64), the rows a workgroup has in flight (what 256 lanes and
+// 64 KiB of LDS hold) and the row ranges: no more than kTcMaxRanges, all but the last of one length.
+static int tc_shape(long long rows, int frames_cap, int frames, int lags, TcShape &s)
+{
+	int A;
+	s.frames = frames; s.lags = lags; s.cap = frames_cap;
+	if (lags <= 64) { A = 1; s.half = lags; s.W = 64; }
+	else
+	{
+		s.half = (lags + 1) / 2;
+		A = s.half <= 256 ? 2 : s.half <= 512 ? 4 : 8;
+		s.W = A == 2 ? (s.half + 63) / 64 * 64 : kTcBlock;
+	}
+	s.S = std::max(1, std::min(kTcBlock / s.W, kTcLdsBytes / (32 * frames)));
+	const long long groups = (rows + s.S - 1) / s.S;
+	const long long want = std::min(groups, (long long)kTcMaxRanges);
+	s.range = (groups + want - 1) / want * s.S;
+	s.ranges = (rows + s.range - 1) / s.range;
+	return A;
+}
+
+int launch_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_cap, int frames, int lags, nbco_corr_lag *out_dev)
+{
+	TcShape s;
+	const int A = tc_shape(rows, frames_cap, frames, lags, s);
+	nbco_corr_lag *out = out_dev;
+	if (s.ranges > 1)
+	{
+		NBCO_TRY(c->reserve(c->tc_part, sizeof(nbco_corr_lag) * (size_t)lags * (size_t)s.ranges));
+		out = c->tc_part.as<nbco_corr_lag>();
+	}
+	const size_t lds = std::max((size_t)32 * (size_t)frames * (size_t)s.S, (size_t)8 * kTcBlock);
+	const dim3 grid((unsigned)s.ranges), block(kTcBlock);
+#define NBCO_TC_STEP(A_) hipLaunchKernelGGL((tc_accumulate_kernel<A_>), grid, block, lds, c->stream, traj, rows, s, out)
+	// the template steps of the lags a lane keeps
+	if (A == 1) NBCO_TC_STEP(1);
+	else if (A == 2) NBCO_TC_STEP(2);
+	else if (A == 4) NBCO_TC_STEP(4);
+	else NBCO_TC_STEP(8);
+#undef NBCO_TC_STEP
+	NBCO_HIP(hipGetLastError());
+	if (s.ranges > 1)
+	{
+		hipLaunchKernelGGL(tc_reduce_kernel, dim3((unsigned)((8 * lags + kTcBlock - 1) / kTcBlock)), dim3(kTcBlock), 0, c->stream, (const nbco_corr_lag *)out, s.ranges, lags, out_dev);
+		NBCO_HIP(hipGetLastError());
 	}
 	return NBCO_OK;
 }

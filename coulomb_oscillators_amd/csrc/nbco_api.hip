@@ -4,6 +4,7 @@
 #include "nbco_internal.hpp"
 #include "bond_order.hpp"
 #include "structure_factor.hpp"
+#include "time_corr.hpp"
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -835,6 +836,44 @@ int nbco_2d_structure_factor(nbco_ctx *c, const double *p, long long n, const nb
 	NBCO_TRY(sk_args(c, "nbco_2d_structure_factor", 2, p, n, g_host, rho_dev));
 	NBCO_TRY(launch_structure_factor(c, p, 2, n, *g_host, rho_dev, n_used_host));
 	return maybe_sync(c);
+}
+
+// ---- tracked trajectories and their time correlations ------------------------------------------
+int nbco_traj_record(nbco_ctx *c, const float *buf, long long n, const int *ids_dev, float *traj, long long rows, int frames_cap, int frame, int stride)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!buf || !traj) return c->fail(NBCO_ERR_ARG, "nbco_traj_record: null pointer");
+	if (n <= 0 || rows <= 0) return c->fail(NBCO_ERR_ARG, "nbco_traj_record: n and rows must be positive");
+	if (stride < 1) return c->fail(NBCO_ERR_ARG, "nbco_traj_record: stride must be at least 1");
+	if (frame < 0 || frame >= frames_cap) return c->fail(NBCO_ERR_ARG, "nbco_traj_record: frame must lie in [0, frames_cap)");
+	if (n >= (1LL << 31)) return c->fail(NBCO_ERR_UNSUPPORTED, "nbco_traj_record: n too large for 32-bit particle numbers");
+	const int *ids = ids_dev;
+	if (!ids && c->o.track_order)
+	{
+		// the map must describe this state: the condition of nbco_kd_copy(NBCO_KD_ORDER)
+		if (c->order_n != n) return c->fail(NBCO_ERR_ARG, "nbco_traj_record: opts.track_order is set but no tracked evaluation of these n particles has run (pass ids_dev)");
+		ids = c->order.as<int>();
+	}
+	NBCO_TRY(launch_traj_record(c, buf, n, ids, traj, rows, frames_cap, frame, stride));
+	return maybe_sync(c);
+}
+
+int nbco_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_cap, int frames, int lags, nbco_corr_lag *out_dev)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!traj || !out_dev) return c->fail(NBCO_ERR_ARG, "nbco_time_corr: null pointer");
+	if (rows <= 0) return c->fail(NBCO_ERR_ARG, "nbco_time_corr: rows must be positive");
+	if (lags < 1 || lags > frames || frames > frames_cap) return c->fail(NBCO_ERR_ARG, "nbco_time_corr: need 1 <= lags <= frames <= frames_cap");
+	if (frames > kTcMaxFrames) return c->fail(NBCO_ERR_ARG, "nbco_time_corr: at most 2048 frames");
+	NBCO_TRY(launch_time_corr(c, traj, rows, frames_cap, frames, lags, out_dev));
+	return maybe_sync(c);
+}
+
+int nbco_time_corr_derive(const nbco_corr_lag *in, int lags, double *out)
+{
+	if (!in || !out || lags < 0) return NBCO_ERR_ARG;
+	for (int l = 0; l < lags; ++l) tc_derive(in[l].dx2, in[l].r4, in[l].vv, in[l].pairs, out + 8 * (size_t)l);
+	return NBCO_OK;
 }
 
 // ---- aperture ----------------------------------------------------------------------------------

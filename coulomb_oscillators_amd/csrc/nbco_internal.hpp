@@ -308,6 +308,7 @@ struct nbco_ctx
 	bool drifted = false;               // nbco_integrate has moved the particles since the last kd-tree evaluation (a scheme that ends on a drift): nbco_kd_probe refuses
 	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
 	DevBuf sk_part;                     // nbco_structure_factor: the partial sums of the particle ranges
+	DevBuf tc_part;                     // nbco_time_corr: the records of the row ranges
 	DevBuf ap_cnt, ap_state;            // nbco_aperture_*: the total and the levels of workgroup counts; the compacted state before it is copied back
 	DevBuf sl_keys, sl_tmp, sl_tab, sl_part;   // nbco_slice_moments: keys and permutation, the sort's and the scan's scratch, the slice table and records, the chunk slabs
 	// bookkeeping of the last evaluation
@@ -414,6 +415,10 @@ int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R
 int bond_summary_finish(nbco_ctx *c, const double *rec, long long records, long long n, int dim, nbco_bond_summary *sum_host);
 // static structure factor (structure_factor_kernels.hpp): 2 K doubles to rho_dev; with n_used_host the call synchronises
 int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, const nbco_sk_grid &g, double *rho_dev, long long *n_used_host);
+// tracked trajectories (time_corr_kernels.hpp): frame `frame` of traj from the state buf, particle numbers from ids (device; NULL: the row);
+// the raw sums of `lags` lags over the first `frames` frames of every row to out_dev.  Neither synchronises.
+int launch_traj_record(nbco_ctx *c, const float *buf, long long n, const int *ids, float *traj, long long rows, int frames_cap, int frame, int stride);
+int launch_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_cap, int frames, int lags, nbco_corr_lag *out_dev);
 // aperture (aperture_kernels.hpp): the rule of a call, formed once on the host by include/nbco.h: w[a] = 1.0 / half[a]
 struct ApRule
 {

@@ -250,6 +250,9 @@ def _load():
         "nbco_structure_factor": [P, P, LL, C.POINTER(SkGrid), P, C.POINTER(LL)],
         "nbco_2d_structure_factor": [P, P, LL, C.POINTER(SkGrid), P, C.POINTER(LL)],
         "nbco_sk_phase": [D, C.POINTER(D)],
+        "nbco_traj_record": [P, P, LL, P, P, LL, I, I, I],
+        "nbco_time_corr": [P, P, LL, I, I, I, P],
+        "nbco_time_corr_derive": [P, I, P],
         "nbco_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
         "nbco_aperture_apply": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL), P, P, LL],
         "nbco_2d_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
@@ -366,6 +369,24 @@ def sk_phase(t):
     if rc != 0:
         raise EngineError("nbco_sk_phase failed with status %d" % rc, status=rc)
     return cs[0], cs[1]
+
+
+CORR_LAG = [("dx2", "<f8", (3,)), ("r4", "<f8"), ("vv", "<f8", (3,)), ("pairs", "<u8")]   # nbco_corr_lag as a numpy record, 64 bytes
+
+
+def time_corr_derive(rec):
+    """msd_x msd_y msd_z msd alpha2 vacf_x vacf_y vacf_z per lag from the raw sums of Engine.time_corr (nbco_time_corr_derive,
+    include/nbco.h): rec a device tensor as time_corr returns it, or a numpy array of CORR_LAG records or of lags x 8 float64 holding
+    them.  Returns a float64 array lags x 8.  A lag without pairs gives zeros, msd == 0 gives alpha2 = 0.  Host only, needs no GPU."""
+    import numpy as np
+    if hasattr(rec, "cpu"):
+        rec = rec.cpu().numpy()
+    raw = np.ascontiguousarray(rec).view(np.uint8).reshape(-1, 64)
+    out = np.empty((raw.shape[0], 8), dtype=np.float64)
+    rc = _load().nbco_time_corr_derive(raw.ctypes.data_as(C.c_void_p), raw.shape[0], out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise EngineError("nbco_time_corr_derive failed with status %d" % rc, status=rc)
+    return out
 
 
 def default_opts(**kw):
@@ -794,6 +815,28 @@ class Engine:
     def structure_factor_2d(self, p, n, h, kstep, rho=None, count=True):
         """the same for the 2-D fp64 positions (xy pairs; nbco_2d_structure_factor): K = (h[0]+1)(2 h[1]+1), index ix (2 h[1]+1) + iy + h[1]"""
         return self._structure_factor(self.lib.nbco_2d_structure_factor, 2, p, n, h, kstep, rho, count)
+
+    # ---- tracked trajectories and their time correlations ------------------------------------------
+    def traj_record(self, buf, n, traj, frame, stride=1, ids=None):
+        """writes frame `frame` of the trajectory buffer traj (a float32 device tensor rows x frames_cap x 6: x y z vx vy vz of the
+        particle with number row * stride) from the state buf = [pos n | vel n ..] (nbco_traj_record): the frame is first filled
+        with NaN, then every state row whose particle number p has p % stride == 0 and p // stride < rows is copied with its bits.
+        p is ids[i] (an int32 device tensor) if given, else the engine's order map where tracking is live (track_order = 1 and
+        unsort = 0 evaluations of these n particles), else the row.  A lost particle's later frames stay NaN.  The state and the
+        engine are not touched; enqueued on the engine's stream."""
+        rows, cap = int(traj.shape[0]), int(traj.shape[1])
+        self._chk(self.lib.nbco_traj_record(self.ctx, _ptr(buf), n, _ptr(ids), _ptr(traj), rows, cap, int(frame), int(stride)))
+
+    def time_corr(self, traj, rows, frames, lags, out=None):
+        """the raw time-correlation sums of the first `rows` rows and `frames` frames of traj for the lags 0 .. lags - 1
+        (nbco_time_corr; 1 <= lags <= frames <= traj.shape[1], frames <= 2048): a float64 device tensor lags x 8 (allocated if None,
+        overwritten if given) whose rows are nbco_corr_lag records -- dx2[3], r4, vv[3] and, in the last 8 bytes, the integer
+        pairs: out.cpu().numpy().view(CORR_LAG) reads them, time_corr_derive(out) gives msd, alpha2 and vacf.  A (row, t, lag) counts
+        only if both frames are finite.  The same bytes on every call.  traj is not modified."""
+        if out is None:
+            out = self.torch.empty((max(int(lags), 0), 8), dtype=self.torch.float64, device=traj.device)
+        self._chk(self.lib.nbco_time_corr(self.ctx, _ptr(traj), int(rows), int(traj.shape[1]), int(frames), int(lags), _ptr(out)))
+        return out
 
     # ---- aperture ---------------------------------------------------------------------------------
     @staticmethod

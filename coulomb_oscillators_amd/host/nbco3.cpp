@@ -24,6 +24,7 @@
 #include "nbco_cpu.hpp"
 #include "slices_file.hpp"
 #include "sk_file.hpp"
+#include "corr_file.hpp"
 
 using namespace nbco_ref;
 using namespace std::chrono;
@@ -98,6 +99,20 @@ const char *kHelp =
     "                    'iter n_used S_max ix iy iz' to <output>/sk.txt: the largest |rho_k|^2 / n_used over k != 0 and where it sits\n"
     "                    (nbco_structure_factor; with -cpu the same rule from the same header on the host: equal to rounding).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -corr <stride> <frames> <lags>   Time correlations of individual particles: from the first snapshot iteration >= -corr-start on, every\n"
+    "                    snapshot records one frame x y z vx vy vz of the particles number 0, stride, 2 stride, .. (numbers of the initial\n"
+    "                    state) until <frames> are in (<= 2048; the frame spacing is the snapshot interval, -steps).  When the window is\n"
+    "                    full, or at the end of the run, <output>/corr.bin receives one 64-byte record per lag 0 .. <lags> - 1 (as far as the\n"
+    "                    recorded frames allow): the raw sums dx2[3], r4, vv[3] as doubles and the count pairs as a 64-bit integer, over all\n"
+    "                    recorded particles and all origins (nbco_time_corr), and <output>/corr.txt one line 'lag tau pairs msd_x msd_y\n"
+    "                    msd_z msd alpha2 vacf_x vacf_y vacf_z' per lag, tau = lag * steps * ds: the mean-square displacement, its\n"
+    "                    non-Gaussian parameter and the velocity autocorrelation.  A frame is recorded after the aperture and before the\n"
+    "                    other outputs; a lost particle's later frames count for nothing.  The flag turns the order tracking of\n"
+    "                    '-snapshot-order input' on (the snapshots stay in the order asked for), so leapfrog runs without its fused pass\n"
+    "                    between two force evaluations: the same trajectory as with '-snapshot-order input', a slower step.  With -cpu the\n"
+    "                    same rule from the same header on the host: pairs equal, the sums to rounding.  Works with -aperture, -bath, -B.\n"
+    "                    Refused with -test, -test2 and -accuracy.\n"
+    "  -corr-start <iter>   The first iteration that may be a frame of -corr (default 0).\n"
     "  -aperture <ellipsoid|box> <hx> <hy> <hz>   At every snapshot iteration, after the step and before the snapshot, drop the particles\n"
     "                    outside the aperture with these half axes ('inf' opens an axis: pipes, slabs) from the run: they are lost and no\n"
     "                    longer simulated (nbco_aperture_apply; with -cpu the same rule on the host).  Per snapshot\n"
@@ -402,8 +417,24 @@ struct Session
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
 	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const SkOpt &sk, const ApertureOpt &aperture,
-	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath)
+	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath, const CorrOpt &corr)
 	{
+		// -corr: the window of frames on the device (rows by the particles the run starts with) and the records of the lags
+		CorrWindow cwin(corr, n);
+		DeviceArray<float> corr_traj(corr.on ? (size_t)cwin.rows * (size_t)corr.frames * 6 : 0);
+		DeviceArray<nbco_corr_lag> corr_out(corr.on ? (size_t)corr.lags : 0);
+		auto corr_finish = [&]() {
+			std::vector<nbco_corr_lag> rec((size_t)cwin.lags());
+			if (!rec.empty())
+			{
+				check(nbco_time_corr(ctx(), corr_traj.ptr, cwin.rows, corr.frames, cwin.recorded, cwin.lags(), corr_out.ptr), "time_corr");
+				check(nbco_sync(ctx()), "sync");
+				HIPCHK(hipMemcpy(rec.data(), corr_out.ptr, rec.size() * sizeof(nbco_corr_lag), hipMemcpyDeviceToHost));
+			}
+			if (cwin.write(folder, rec, (double)nSteps * (double)dt)) return true;
+			std::cerr << "Error: cannot write the correlation files into \"" << folder << "\"" << std::endl;
+			return false;
+		};
 		std::vector<nbco_moments> slice_recs(slices.on ? (size_t)slices.axis.bins : 0);
 		// -aperture: the loss record on the device (room for everybody) and the host copies that go into the files
 		const size_t ap_n = aperture.on ? (size_t)n : 0;
@@ -438,7 +469,7 @@ struct Session
 		DeviceArray<double> probes_out(4 * m);
 		std::vector<double> probes_host(4 * m);
 		if (m) HIPCHK(hipMemcpy(probes_dev.ptr, probes.data(), probes.size() * sizeof(float), hipMemcpyHostToDevice));
-		change([&](nbco_opts &c) { c.unsort = 0; c.sync = 0; c.track_order = input_order ? 1 : 0; });
+		change([&](nbco_opts &c) { c.unsort = 0; c.sync = 0; c.track_order = input_order || corr.on ? 1 : 0; });
 		std::vector<int> order(input_order ? (size_t)n : 0);
 		std::vector<float> rows(input_order ? host.size() : 0);
 		check(nbco_force(ctx(), NBCO_EVAL_FMM_KDTREE, state.ptr, n, par.ptr, 1), "compute_force");
@@ -501,6 +532,13 @@ struct Session
 					std::cerr << "\nError: every particle is outside the aperture at iteration " << snap << ": nothing is left to simulate" << std::endl;
 					return -1;
 				}
+			}
+			if (const int frame = cwin.frame_for(snap); frame >= 0)
+			{
+				// through the engine's order map, on the device: row i of the state goes to the row of its particle number
+				check(nbco_traj_record(ctx(), state.ptr, n, nullptr, corr_traj.ptr, cwin.rows, corr.frames, frame, corr.stride), "traj_record");
+				++cwin.recorded;
+				if (cwin.full() && !corr_finish()) return -1;
 			}
 			HIPCHK(hipMemcpy(host.data(), state.ptr, state_bytes, hipMemcpyDeviceToHost));   // acc not copied
 			std::ofstream fout(folder + "/out" + std::to_string(snap) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
@@ -617,6 +655,7 @@ struct Session
 			if (snap == 0) { loop_t0 = std::chrono::steady_clock::now(); loop_first = 1; }   // the timer below starts behind the first snapshot
 		}
 		check(nbco_sync(ctx()), "sync");
+		if (corr.on && !cwin.written && !corr_finish()) return -1;
 		std::cout << std::endl;
 		// (not in the reference: wall time of the integration loop behind the first snapshot -- what bench.py's `cli` leg reads)
 		const auto loop_t1 = std::chrono::steady_clock::now();
@@ -643,6 +682,7 @@ int main(int argc, const char **argv)
 	PairsOpt pairs;
 	double bonds_rmax = 0;
 	SkOpt sk;
+	CorrOpt corr;
 	ApertureOpt aperture;
 	SlicesOpt slices;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false, bfield = false;
@@ -809,6 +849,25 @@ int main(int argc, const char **argv)
 			}
 			i += 6;
 		}
+		else if (a == "-corr")
+		{
+			if (!need(i, 3, "-corr")) return -1;
+			if (!parse_corr(argv + i + 1, corr))
+			{
+				std::cerr << "Error: invalid argument(s) to '-corr' (stride: an integer >= 1; frames, lags: integers with 1 <= lags <= frames <= 2048)\n";
+				return -1;
+			}
+			i += 3;
+		}
+		else if (a == "-corr-start")
+		{
+			if (!need(i, 1, "-corr-start")) return -1;
+			char *end = nullptr;
+			const long v = std::strtol(argv[i + 1], &end, 10);
+			if (end == argv[i + 1] || *end || v < 0 || v > 0x7fffffffL) { std::cerr << "Error: invalid argument to '-corr-start': " << argv[i + 1] << " (an iteration >= 0)\n"; return -1; }
+			corr.start = (int)v;
+			++i;
+		}
 		else if (a == "-aperture")
 		{
 			if (!need(i, 4, "-aperture")) return -1;
@@ -932,6 +991,12 @@ int main(int argc, const char **argv)
 		return -1;
 	}
 
+	if (corr.on && (test || test2 || b_accuracy))
+	{
+		std::cerr << "Error: '-corr' follows a simulation: it cannot be combined with -test, -test2 or -accuracy\n";
+		return -1;
+	}
+
 	// ---- state ---------------------------------------------------------------------------------------
 	std::vector<float> host;   // [pos | vel] as the state files hold them; the accelerations never leave the device
 	if (in)
@@ -993,6 +1058,19 @@ int main(int argc, const char **argv)
 		std::vector<int> lost_rows;
 		std::vector<float> lost_recs;
 		std::vector<nbco_moments> slice_recs;
+		// -corr: the window of frames on the host, and the particle numbers of the state rows (the direct sum never permutes; an
+		// aperture compacts them with the state)
+		CorrWindow cwin(corr, nBodies);
+		std::vector<float> corr_traj(corr.on ? (size_t)cwin.rows * (size_t)corr.frames * 6 : 0);
+		std::vector<int> corr_ids(corr.on ? (size_t)nBodies : 0);
+		for (size_t i = 0; i < corr_ids.size(); ++i) corr_ids[i] = (int)i;
+		auto corr_finish = [&]() {
+			std::vector<nbco_corr_lag> rec;
+			if (cwin.lags() > 0) nbco_cpu::time_corr(corr_traj.data(), cwin.rows, corr.frames, cwin.recorded, cwin.lags(), rec);
+			if (cwin.write(strout, rec, (double)nSteps * (double)dt)) return true;
+			std::cerr << "Error: cannot write the correlation files into \"" << strout << "\"" << std::endl;
+			return false;
+		};
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(scheme, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr, bath_on ? &bath : nullptr, (unsigned long long)iter);
@@ -1002,6 +1080,16 @@ int main(int argc, const char **argv)
 			{
 				// (the direct sum never permutes the state: a row is a particle number until somebody is lost)
 				nbco_cpu::aperture_apply(st, nBodies, aperture.ap.shape, aperture.ap.centre, aperture.ap.half, lost_rows, lost_recs);
+				if (corr.on && !lost_rows.empty())
+				{
+					size_t next = 0, w = 0;
+					for (size_t i = 0; i < corr_ids.size(); ++i)
+					{
+						if (next < lost_rows.size() && (size_t)lost_rows[next] == i) ++next;
+						else corr_ids[w++] = corr_ids[i];
+					}
+					corr_ids.resize(w);
+				}
 				state_bytes = 6 * (size_t)nBodies * sizeof(float);
 				pairs_nn2.resize(pairs.bins ? (size_t)nBodies : 0);
 				if (!llog.record(iter, dt, lost_rows, lost_recs, nBodies)) return -1;
@@ -1010,6 +1098,12 @@ int main(int argc, const char **argv)
 					std::cerr << "\nError: every particle is outside the aperture at iteration " << iter << ": nothing is left to simulate" << std::endl;
 					return -1;
 				}
+			}
+			if (const int frame = cwin.frame_for(iter); frame >= 0)
+			{
+				nbco_cpu::traj_record(st.data(), nBodies, corr_ids, corr_traj, cwin.rows, corr.frames, frame, corr.stride);
+				++cwin.recorded;
+				if (cwin.full() && !corr_finish()) return -1;
 			}
 			std::ofstream fout(strout + "/out" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)
@@ -1068,6 +1162,7 @@ int main(int argc, const char **argv)
 				}
 			}
 		}
+		if (corr.on && !cwin.written && !corr_finish()) return -1;
 		std::cout << std::endl;
 		return 0;
 	}
@@ -1081,7 +1176,7 @@ int main(int argc, const char **argv)
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
 		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, b_accuracy ? SkOpt{} : sk, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
-		                     b_accuracy ? nbco_bath{} : bath);
+		                     b_accuracy ? nbco_bath{} : bath, corr);
 	}
 	return rc;
 }

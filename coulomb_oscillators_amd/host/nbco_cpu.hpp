@@ -12,10 +12,12 @@
 #include <cstdint>
 #include <thread>
 #include <vector>
+#include <limits>
 #include "../../include/nbco.h"
 #include "../csrc/integ_compose.hpp"
 #include "../csrc/bond_order.hpp"
 #include "../csrc/structure_factor.hpp"
+#include "../csrc/time_corr.hpp"
 
 namespace nbco_cpu {
 
@@ -316,6 +318,62 @@ inline long long structure_factor(const V3 *x, int n, const nbco_sk_grid &g, std
 		}
 	});
 	return (long long)rho[2 * ((size_t)hy * nz + hz)];
+}
+
+// One frame of a trajectory buffer for `nbco3 -cpu -corr`, as nbco_traj_record (include/nbco.h) writes it: frame `frame` of every row
+// NaN, then the six floats of every state row whose particle number ids[i] is a multiple of stride with ids[i] / stride < rows, bit for
+// bit.  st = [pos n | vel n | ..]; traj holds rows x frames_cap x 6 floats.  The host never permutes: ids are the numbers the caller
+// keeps through its apertures.
+inline void traj_record(const V3 *st, int n, const std::vector<int> &ids, std::vector<float> &traj, long long rows, int frames_cap, int frame, int stride)
+{
+	const float q = std::numeric_limits<float>::quiet_NaN();
+	for (long long r = 0; r < rows; ++r)
+		for (int j = 0; j < 6; ++j) traj[((size_t)r * frames_cap + frame) * 6 + j] = q;
+	for (int i = 0; i < n; ++i)
+	{
+		const int p = ids[(size_t)i];
+		if (p < 0 || p % stride != 0 || p / stride >= rows) continue;
+		float *o = &traj[((size_t)(p / stride) * frames_cap + frame) * 6];
+		o[0] = st[i].x; o[1] = st[i].y; o[2] = st[i].z;
+		o[3] = st[n + i].x; o[4] = st[n + i].y; o[5] = st[n + i].z;
+	}
+}
+
+// The raw time-correlation sums of `nbco3 -cpu -corr`, by the rule of nbco_time_corr (include/nbco.h) from csrc/time_corr.hpp, the
+// header the device kernel uses.  A fixed partition: every worker owns a range of lags and carries one sum per lag through all rows in
+// index order, the origins of a row in increasing t, so the bytes do not depend on the number of threads.  The device adds the rows
+// in another order: equal to rounding only; pairs equal.
+inline void time_corr(const float *traj, long long rows, int frames_cap, int frames, int lags, std::vector<nbco_corr_lag> &out)
+{
+	out.assign((size_t)lags, nbco_corr_lag{});
+	nbco_corr_lag *o = out.data();
+	std::vector<unsigned char> fin((size_t)rows * frames);
+	for (long long r = 0; r < rows; ++r)
+		for (int f = 0; f < frames; ++f) fin[(size_t)r * frames + f] = tc_finite(traj + ((size_t)r * frames_cap + f) * 6) ? 1 : 0;
+	const unsigned char *ok = fin.data();
+	for_ranges(lags, [=](int lo, int hi) {
+		for (int tau = lo; tau < hi; ++tau)
+		{
+			TcSum s;
+			tc_zero(s);
+			unsigned long long pairs = 0;
+			for (long long r = 0; r < rows; ++r)
+			{
+				const float *row = traj + (size_t)r * frames_cap * 6;
+				for (int t = 0; t + tau < frames; ++t)
+				{
+					if (!ok[(size_t)r * frames + t] || !ok[(size_t)r * frames + t + tau]) continue;
+					const float *a = row + 6 * (size_t)t, *b = row + 6 * (size_t)(t + tau);
+					tc_term(s, (double)a[0], (double)a[1], (double)a[2], (double)a[3], (double)a[4], (double)a[5], (double)b[0], (double)b[1], (double)b[2],
+					        (double)b[3], (double)b[4], (double)b[5]);
+					++pairs;
+				}
+			}
+			for (int c = 0; c < 3; ++c) { o[tau].dx2[c] = s.dx2[c]; o[tau].vv[c] = s.vv[c]; }
+			o[tau].r4 = s.r4;
+			o[tau].pairs = pairs;
+		}
+	});
 }
 
 // The aperture of `nbco3 -cpu -aperture`, by the rule of nbco_aperture_apply (include/nbco.h) in fp64 over the fp32 positions:

@@ -845,6 +845,54 @@ typedef struct nbco_sk_grid { int h[3]; double kstep[3]; } nbco_sk_grid;      /*
 int nbco_structure_factor(nbco_ctx *c, const float *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host);
 int nbco_2d_structure_factor(nbco_ctx *c, const double *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host);
 int nbco_sk_phase(double t, double *cs_host);
+/* ---- time correlations of individual particles: is the cloud solid?  The mean-square displacement (a plateau in a solid, linear
+ * growth in a liquid; the Lindemann ratio, the diffusion constant), its non-Gaussian parameter alpha2 (caging and hopping) and the
+ * velocity autocorrelation function (whose host-side transform is the spectrum of plasma and trap oscillations, the tune spread of
+ * a space-charge-dominated beam).  3-D only.
+ * nbco_traj_record keeps identity over time.  The caller owns a DEVICE buffer traj of rows x frames_cap x 6 floats; row r belongs to
+ * particle number r * stride, and frame f of row r is the six floats x y z vx vy vz at traj[(r * frames_cap + f) * 6 ..].  buf is a
+ * state (pos at buf, vel at buf + 3 n).  The call fills frame `frame` of every row with NaN (the quiet NaN 0x7fc00000) and then, for
+ * every state row i with particle number p where p % stride == 0 and p / stride < rows, writes the six state floats with their bits
+ * to row p / stride.  p is ids_dev[i] where ids_dev (int[n], DEVICE memory; for callers who compact or permute the state
+ * themselves; a negative number is skipped, a number given twice is the caller's error) is not NULL; otherwise the context's order
+ * map where tracking is live -- the condition of nbco_kd_copy(NBCO_KD_ORDER): opts.track_order and a tracked evaluation of these n
+ * particles behind it; the map is read where it lies, on the device, and nbco_aperture_apply has already compacted it -- and
+ * otherwise i.  A particle that an aperture has removed simply stops being written: its later frames stay NaN.
+ * Refused with NBCO_ERR_ARG before any launch, traj untouched: a NULL c, buf or traj; n <= 0, rows <= 0, stride < 1; frame outside
+ * [0, frames_cap); opts.track_order set without a tracked evaluation of these n particles and without ids_dev (the map does not
+ * describe this state).  NBCO_ERR_UNSUPPORTED for n >= 2^31.
+ * The call reads the state and the map and changes nothing in the context: tree, rebuild schedule, warm-select history, order map and
+ * every valid diagnostic return the bits they would have returned.  Two passes on opts.stream; it returns as the evaluators do
+ * (opts.sync) and never synchronises of its own.
+ * nbco_time_corr sums over all rows and all origins t with t + tau < frames, for tau = 0 .. lags - 1; 1 <= lags <= frames <= frames_cap
+ * and frames <= 2048.  A (row, t, tau) counts only if all twelve floats of frames t and t + tau are finite.  out_dev (DEVICE memory,
+ * `lags` records, overwritten) receives per lag, as RAW SUMS -- the division is the caller's, or nbco_time_corr_derive's:
+ *   pairs   the number of (row, t) that counted, an exact integer;
+ *   dx2[c]  the sum of D_c^2, D_c = (double) x_c(t + tau) - (double) x_c(t);
+ *   r4      the sum of (D_x^2 + D_y^2 + D_z^2)^2;
+ *   vv[c]   the sum of v_c(t) v_c(t + tau).
+ * The rule, which is the numerical contract, is written once, in csrc/time_corr.hpp, for the kernel, `nbco3 -cpu -corr` and
+ * nbco_time_corr_derive: every float widened first; D_c one subtraction; dx2[c] <- fma(D_c, D_c, dx2[c]);
+ * r2 = fma(D_z, D_z, fma(D_y, D_y, D_x * D_x)); r4 <- fma(r2, r2, r4); vv[c] <- fma(v_c(t), v_c(t + tau), vv[c]).
+ * Determinism: a (row, tau) adds its terms in increasing t; the rows are cut into ranges by (rows, frames, lags) alone, a range's
+ * rows are taken in a fixed order and the ranges are added in index order; no float atomics: a second call returns the same bytes,
+ * on any stream and on any card.  THE DEVICE AND `nbco3 -cpu -corr` AGREE ONLY TO ROUNDING (they add the rows in different orders):
+ * with u = 2^-53, dx2 and r4 within (pairs + 8) u of the exact sums of the rule's terms, relative; vv within (pairs + 8) u times the
+ * sum of the |terms|; pairs equal.
+ * Refused with NBCO_ERR_ARG before any launch, out_dev untouched: a NULL c, traj or out_dev; rows <= 0; lags < 1, lags > frames,
+ * frames > frames_cap, frames > 2048.
+ * State: the records of the row ranges live in scratch of the call's own (at most 64 MiB).  The tree, the rebuild schedule, the
+ * warm-select history, the order tracking, nbco_kd_get_info and every valid diagnostic stay as they were.
+ * nbco_time_corr_derive (host only, no GPU needed, like nbco_moments_derive): `in` and `out` in HOST memory; per lag the eight
+ * doubles msd_x msd_y msd_z msd alpha2 vacf_x vacf_y vacf_z with msd_c = dx2[c] / pairs, msd = (msd_x + msd_y) + msd_z,
+ * alpha2 = 3 <r^4> / (5 <r^2>^2) - 1 and vacf_c = vv[c] / pairs.  pairs == 0 gives eight zeros and msd == 0 (lag 0, particles at rest)
+ * alpha2 = 0: never NaN.  NBCO_ERR_ARG for a NULL pointer or lags < 0.
+ * Not offered: the 2-D state (nbco_2d_fmm leaves it in cell order and keeps no order map), sharded runs, correlations between
+ * different particles and S(k, omega), more than 2048 frames, and the Fourier transform of the VACF (a few thousand points: host). */
+typedef struct nbco_corr_lag { double dx2[3]; double r4; double vv[3]; unsigned long long pairs; } nbco_corr_lag;   /* 64 bytes */
+int nbco_traj_record(nbco_ctx *c, const float *buf, long long n, const int *ids_dev, float *traj, long long rows, int frames_cap, int frame, int stride);
+int nbco_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_cap, int frames, int lags, nbco_corr_lag *out_dev);
+int nbco_time_corr_derive(const nbco_corr_lag *in, int lags, double *out);
 /* ---- aperture: particles that cross a boundary (a pipe wall, an electrode) are lost -- dropped from the state on the device,
  * recorded, and no longer simulated.  nbco_aperture_count / nbco_aperture_apply serve the 3-D fp32 state, the nbco_2d_ forms the
  * 2-D fp64 state (they read centre[0..1] and half[0..1] only).  *ap_host lies in HOST memory.
