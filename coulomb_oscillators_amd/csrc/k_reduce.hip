@@ -8,6 +8,7 @@
 #include "bond_order.hpp"
 #include "structure_factor.hpp"
 #include "time_corr.hpp"
+#include "modes.hpp"
 #include <algorithm>
 #include <cfloat>
 
@@ -189,6 +190,7 @@ static int grid_for(long long n)
 #undef NBCO_BOND_EXACT
 #include "structure_factor_kernels.hpp"   // the static structure factor: the tile kernel and the sum over the particle ranges
 #include "time_corr_kernels.hpp"          // tracked trajectories: the recording passes, the correlation kernel and the sum over the row ranges
+#include "modes_kernels.hpp"              // collective modes: the tile kernel with velocities, the sum over the particle ranges, the lag kernel
 
 } // namespace
 
@@ -530,17 +532,18 @@ int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R
 // The shape of a call, from n and the grid alone (never from the device): runs of ix of at most kSkMaxAcc, the cut of the items into
 // workgroups (the fewest workgroups that keep 85 % of the lanes busy with `copies` copies of `lanes` items each, else the best cut up to
 // four times as many), the tile that fills the LDS budget, and the particle ranges -- at least 512 particles each, no more of them than bring the launch to about 2048 workgroups
-// or the partial sums to 256 MiB.
-static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g)
+// or the partial sums to 256 MiB.  nbco_modes_record shares it: runs of at most max_acc, `extra` more 16-byte slots per particle in a
+// tile, `rec` bytes of partial sums per k.
+static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g, int max_acc = kSkMaxAcc, int extra = 0, int rec = 16)
 {
 	SkShape s;
 	s.hx = g.h[0]; s.hy = g.h[1]; s.hz = dim == 3 ? g.h[2] : 0;
-	s.nch = (s.hx + kSkMaxAcc) / kSkMaxAcc;
+	s.nch = (s.hx + max_acc) / max_acc;
 	s.L = (s.hx + s.nch) / s.nch;
 	s.ny = 2 * s.hy + 1; s.nz = 2 * s.hz + 1;
 	s.items = s.nch * s.ny * s.nz;
 	s.K = sk_count(g.h, dim);
-	const int per = 1 + (s.hy + 1) + (dim == 3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0);   // complex numbers per particle
+	const int per = 1 + (s.hy + 1) + (dim == 3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0) + extra;   // complex numbers per particle
 	s.tile = std::min(kSkBlock, kSkLdsBytes / (16 * per));
 	const int kt0 = (s.items + kSkBlock - 1) / kSkBlock;
 	int kt = kt0;
@@ -555,7 +558,7 @@ static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g)
 	s.lanes = (s.items + kt - 1) / kt;
 	s.copies = s.lanes <= kSkBlock / 2 ? kSkBlock / s.lanes : 1;
 	long long r0 = std::min((n + 511) / 512, std::max(1LL, (long long)(2048 / kt)));
-	r0 = std::max(1LL, std::min(r0, (256LL << 20) / (16 * s.K)));
+	r0 = std::max(1LL, std::min(r0, (256LL << 20) / (rec * s.K)));
 	s.range = ((n + r0 - 1) / r0 + 63) / 64 * 64;
 	s.wx = g.kstep[0] / kSkTwoPi; s.wy = g.kstep[1] / kSkTwoPi; s.wz = dim == 3 ? g.kstep[2] / kSkTwoPi : 0.0;
 	return s;
@@ -587,7 +590,7 @@ static int sk_run(nbco_ctx *c, const T *p, long long n, const SkShape &s, double
 	NBCO_HIP(hipGetLastError());
 	if (ranges > 1)
 	{
-		hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)((2 * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, 2 * s.K, rho);
+		hipLaunchKernelGGL(sk_reduce_kernel<2>, dim3((unsigned)((2 * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, 2 * s.K, rho, 2LL);
 		NBCO_HIP(hipGetLastError());
 	}
 	return NBCO_OK;
@@ -667,6 +670,79 @@ int launch_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_
 		hipLaunchKernelGGL(tc_reduce_kernel, dim3((unsigned)((8 * lags + kTcBlock - 1) / kTcBlock)), dim3(kTcBlock), 0, c->stream, (const nbco_corr_lag *)out, s.ranges, lags, out_dev);
 		NBCO_HIP(hipGetLastError());
 	}
+	return NBCO_OK;
+}
+
+// ---- collective modes (modes_kernels.hpp) -------------------------------------------------------------
+int launch_modes_record(nbco_ctx *c, const float *buf, long long n, const nbco_sk_grid &g, double *series, int frames_cap, int frame, long long *n_used_host)
+{
+	const SkShape s = sk_shape(3, n, g, kMdMaxAcc, kMdExtra, 64);
+	const long long ranges = (n + s.range - 1) / s.range;
+	double *rec = series + 8 * (size_t)frame;   // record k of this frame lies at rec + k * stride
+	const long long stride = 8 * (long long)frames_cap;
+	double *out = rec;
+	long long ostride = stride;
+	if (ranges > 1)
+	{
+		NBCO_TRY(c->reserve(c->md_part, sizeof(double) * 8 * (size_t)s.K * (size_t)ranges));
+		out = c->md_part.as<double>();
+		ostride = 8;
+	}
+	const int per = 1 + kMdExtra + (s.hy + 1) + (s.hz + 1) + (s.nch > 1 ? s.nch : 0);
+	const size_t lds = std::max((size_t)16 * per * s.tile, (size_t)16 * kSkBlock);   // the tables of a tile; the copies' sums at the end
+	const dim3 grid((unsigned)((s.items + s.lanes - 1) / s.lanes), (unsigned)ranges), block(kSkBlock);
+#define NBCO_MD_STEP(A_) hipLaunchKernelGGL((modes_accumulate_kernel<A_>), grid, block, lds, c->stream, buf, n, s, out, ostride)
+	// the template steps of the run length L
+	if (s.L <= 1) NBCO_MD_STEP(1);
+	else if (s.L <= 2) NBCO_MD_STEP(2);
+	else if (s.L <= 3) NBCO_MD_STEP(3);
+	else NBCO_MD_STEP(4);
+#undef NBCO_MD_STEP
+	NBCO_HIP(hipGetLastError());
+	if (ranges > 1)
+	{
+		hipLaunchKernelGGL(sk_reduce_kernel<8>, dim3((unsigned)((8 * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, 8 * s.K, rec, stride);
+		NBCO_HIP(hipGetLastError());
+	}
+	if (n_used_host)
+	{
+		// rho at k = 0 is the exact count of the particles that counted
+		const size_t k0 = (size_t)s.hy * (size_t)s.nz + (size_t)s.hz;
+		double cnt = 0;
+		NBCO_HIP(hipMemcpyAsync(&cnt, rec + k0 * (size_t)stride, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+		NBCO_HIP(hipStreamSynchronize(c->stream));
+		*n_used_host = (long long)cnt;
+	}
+	return NBCO_OK;
+}
+
+// The shape of a correlation call, from (frames, lags) alone: the lags a lane keeps (1 up to 64 lags, else pairs: 2 up to 512 lags, 4
+// beyond), the lanes of a k (a multiple of 64) and the k a workgroup serves (what 256 lanes and 64 KiB of LDS hold).
+int launch_mode_corr(nbco_ctx *c, const double *series, const nbco_sk_grid &g, int frames_cap, int frames, int lags, nbco_mode_lag *out_dev)
+{
+	TcShape s;
+	int A;
+	s.frames = frames; s.lags = lags; s.cap = frames_cap;
+	if (lags <= 64) { A = 1; s.half = lags; s.W = 64; }
+	else
+	{
+		s.half = (lags + 1) / 2;
+		A = s.half <= 256 ? 2 : 4;
+		s.W = A == 2 ? (s.half + 63) / 64 * 64 : kTcBlock;
+	}
+	s.S = std::max(1, std::min(kTcBlock / s.W, kTcLdsBytes / (64 * frames)));
+	const long long K = sk_count(g.h, 3);
+	s.range = s.S;
+	s.ranges = (K + s.S - 1) / s.S;
+	const size_t lds = (size_t)64 * (size_t)frames * (size_t)s.S;
+	const dim3 grid((unsigned)s.ranges), block(kTcBlock);
+#define NBCO_MC_STEP(A_) hipLaunchKernelGGL((mode_corr_kernel<A_>), grid, block, lds, c->stream, series, K, g, s, out_dev)
+	// the template steps of the lags a lane keeps
+	if (A == 1) NBCO_MC_STEP(1);
+	else if (A == 2) NBCO_MC_STEP(2);
+	else NBCO_MC_STEP(4);
+#undef NBCO_MC_STEP
+	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }
 

@@ -5,6 +5,7 @@
 #include "bond_order.hpp"
 #include "structure_factor.hpp"
 #include "time_corr.hpp"
+#include "modes.hpp"
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -873,6 +874,84 @@ int nbco_time_corr_derive(const nbco_corr_lag *in, int lags, double *out)
 {
 	if (!in || !out || lags < 0) return NBCO_ERR_ARG;
 	for (int l = 0; l < lags; ++l) tc_derive(in[l].dx2, in[l].r4, in[l].vv, in[l].pairs, out + 8 * (size_t)l);
+	return NBCO_OK;
+}
+
+// ---- collective modes ----------------------------------------------------------------------------
+int nbco_modes_record(nbco_ctx *c, const float *buf, long long n, const nbco_sk_grid *g_host, double *series_dev, int frames_cap, int frame, long long *n_used_host)
+{
+	NBCO_TRY(sk_args(c, "nbco_modes_record", 3, buf, n, g_host, series_dev));
+	if (frames_cap < 1) return c->fail(NBCO_ERR_ARG, "nbco_modes_record: frames_cap must be at least 1");
+	if (frame < 0 || frame >= frames_cap) return c->fail(NBCO_ERR_ARG, "nbco_modes_record: frame must lie in [0, frames_cap)");
+	NBCO_TRY(launch_modes_record(c, buf, n, *g_host, series_dev, frames_cap, frame, n_used_host));
+	return maybe_sync(c);
+}
+
+// what the correlation calls refuse of a grid and a shape
+static bool md_shape_ok(const nbco_sk_grid *g, int frames_cap, int frames, int lags)
+{
+	for (int a = 0; a < 3; ++a)
+		if (g->h[a] < 0 || g->h[a] > kSkMaxH || !std::isfinite(g->kstep[a]) || !(g->kstep[a] > 0.0)) return false;
+	return lags >= 1 && lags <= frames && frames <= frames_cap && frames <= kMdMaxFrames;
+}
+
+int nbco_mode_corr(nbco_ctx *c, const double *series_dev, const nbco_sk_grid *g_host, int frames_cap, int frames, int lags, nbco_mode_lag *out_dev)
+{
+	if (!c) return NBCO_ERR_ARG;
+	if (!series_dev || !g_host || !out_dev) return c->fail(NBCO_ERR_ARG, "nbco_mode_corr: null pointer");
+	if (!md_shape_ok(g_host, frames_cap, frames, lags))
+		return c->fail(NBCO_ERR_ARG, "nbco_mode_corr: need h 0..64 and kstep finite and positive on every axis, 1 <= lags <= frames <= frames_cap and at most 1024 frames");
+	NBCO_TRY(launch_mode_corr(c, series_dev, *g_host, frames_cap, frames, lags, out_dev));
+	return maybe_sync(c);
+}
+
+int nbco_mode_corr_ref(const double *series_host, const nbco_sk_grid *g_host, int frames_cap, int frames, int lags, nbco_mode_lag *out_host)
+{
+	if (!series_host || !g_host || !out_host || !md_shape_ok(g_host, frames_cap, frames, lags)) return NBCO_ERR_ARG;
+	const long long K = sk_count(g_host->h, 3);
+	for (long long k = 0; k < K; ++k)
+	{
+		const double *row = series_host + (size_t)k * (size_t)frames_cap * 8;
+		double kv[3];
+		md_wave_vector(k, g_host->h, g_host->kstep, kv);
+		for (int tau = 0; tau < lags; ++tau)
+		{
+			MdSum s;
+			md_sum_zero(s);
+			for (int t = 0; t + tau < frames; ++t)
+			{
+				const double *a = row + 8 * (size_t)t, *b = row + 8 * (size_t)(t + tau);
+				const SkC arho = {a[0], a[1]}, ajx = {a[2], a[3]}, ajy = {a[4], a[5]}, ajz = {a[6], a[7]};
+				const SkC brho = {b[0], b[1]}, bjx = {b[2], b[3]}, bjy = {b[4], b[5]}, bjz = {b[6], b[7]};
+				md_term(s, kv[0], kv[1], kv[2], arho, ajx, ajy, ajz, md_long(kv[0], kv[1], kv[2], ajx, ajy, ajz), brho, bjx, bjy, bjz);
+			}
+			nbco_mode_lag &o = out_host[(size_t)k * (size_t)lags + (size_t)tau];
+			o.rr = s.rr; o.ll = s.ll; o.jj = s.jj;
+			o.s0[0] = s.s0.re; o.s0[1] = s.s0.im;
+			o.s1[0] = s.s1.re; o.s1[1] = s.s1.im;
+			o.pairs = (unsigned long long)(frames - tau);
+		}
+	}
+	return NBCO_OK;
+}
+
+int nbco_mode_corr_derive(const nbco_mode_lag *in, const nbco_sk_grid *g_host, int lags, double n_norm, double *out)
+{
+	if (!in || !g_host || !out || lags < 0) return NBCO_ERR_ARG;
+	for (int a = 0; a < 3; ++a)
+		if (g_host->h[a] < 0 || g_host->h[a] > kSkMaxH) return NBCO_ERR_ARG;
+	const long long K = sk_count(g_host->h, 3);
+	for (long long k = 0; k < K; ++k)
+	{
+		double kv[3];
+		md_wave_vector(k, g_host->h, g_host->kstep, kv);
+		const double k2 = md_k2(kv);
+		for (int l = 0; l < lags; ++l)
+		{
+			const nbco_mode_lag &r = in[(size_t)k * (size_t)lags + (size_t)l];
+			md_derive(r.rr, r.ll, r.jj, r.s0, r.s1, r.pairs, k2, n_norm, out + 4 * ((size_t)k * (size_t)lags + (size_t)l));
+		}
+	}
 	return NBCO_OK;
 }
 

@@ -309,6 +309,7 @@ struct nbco_ctx
 	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
 	DevBuf sk_part;                     // nbco_structure_factor: the partial sums of the particle ranges
 	DevBuf tc_part;                     // nbco_time_corr: the records of the row ranges
+	DevBuf md_part;                     // nbco_modes_record: the mode records of the particle ranges
 	DevBuf ap_cnt, ap_state;            // nbco_aperture_*: the total and the levels of workgroup counts; the compacted state before it is copied back
 	DevBuf sl_keys, sl_tmp, sl_tab, sl_part;   // nbco_slice_moments: keys and permutation, the sort's and the scan's scratch, the slice table and records, the chunk slabs
 	// bookkeeping of the last evaluation
@@ -419,6 +420,10 @@ int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, co
 // the raw sums of `lags` lags over the first `frames` frames of every row to out_dev.  Neither synchronises.
 int launch_traj_record(nbco_ctx *c, const float *buf, long long n, const int *ids, float *traj, long long rows, int frames_cap, int frame, int stride);
 int launch_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_cap, int frames, int lags, nbco_corr_lag *out_dev);
+// collective modes (modes_kernels.hpp): the K records of the state buf to frame `frame` of series (with n_used_host the call synchronises);
+// the raw sums of `lags` lags over the first `frames` frames of every k to out_dev, K * lags records (does not synchronise)
+int launch_modes_record(nbco_ctx *c, const float *buf, long long n, const nbco_sk_grid &g, double *series, int frames_cap, int frame, long long *n_used_host);
+int launch_mode_corr(nbco_ctx *c, const double *series, const nbco_sk_grid &g, int frames_cap, int frames, int lags, nbco_mode_lag *out_dev);
 // aperture (aperture_kernels.hpp): the rule of a call, formed once on the host by include/nbco.h: w[a] = 1.0 / half[a]
 struct ApRule
 {

@@ -31,6 +31,48 @@ struct SkShape
 	double wx, wy, wz;     // kstep / 2 pi
 };
 
+// The power tables of a tile of cnt particles from their base phases (ex[j], ty[j][1], tz[j][1]; the entries 0 are set): one lane per
+// (particle, axis) chain fills ty[j][2..hy], tz[j][2..hz] and, where the ix run is cut, tc[j][1..nch-1] = e_x^{cL}.  Shared with
+// modes_accumulate_kernel (modes_kernels.hpp).
+template <bool DIM3>
+__device__ __forceinline__ void sk_power_tables(const SkShape &s, int cnt, const SkC *ex, SkC *ty, SkC *tz, SkC *tc)
+{
+	const int tid = (int)threadIdx.x, sy = s.hy + 1, sz = s.hz + 1, nch = s.nch;
+	const int chains = cnt * 3;
+	for (int c = tid; c < chains; c += kSkBlock)
+	{
+		const int j = c / 3, a = c % 3;
+		if (a == 0)
+		{
+			if (nch > 1)
+			{
+				const SkC z1 = ex[j];
+				SkC z = z1;   // z = e_x^m
+				for (int m = 1; m <= (nch - 1) * s.L; ++m)
+				{
+					if (m % s.L == 0) tc[(size_t)j * nch + m / s.L] = z;
+					z = sk_mul(z, z1);
+				}
+			}
+		}
+		else if (a == 1)
+		{
+			if (s.hy > 1)
+			{
+				const SkC z1 = ty[(size_t)j * sy + 1];
+				SkC z = z1;
+				for (int m = 2; m <= s.hy; ++m) { z = sk_mul(z, z1); ty[(size_t)j * sy + m] = z; }
+			}
+		}
+		else if (DIM3 && s.hz > 1)
+		{
+			const SkC z1 = tz[(size_t)j * sz + 1];
+			SkC z = z1;
+			for (int m = 2; m <= s.hz; ++m) { z = sk_mul(z, z1); tz[(size_t)j * sz + m] = z; }
+		}
+	}
+}
+
 template <int A, bool DIM3, typename T>
 __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__restrict__ p, long long n, SkShape s, double *__restrict__ out)
 {
@@ -91,40 +133,7 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 			if (nch > 1) tc[(size_t)j * nch] = first;
 		}
 		__syncthreads();
-		// the power tables: one lane per (particle, axis) chain
-		const int chains = cnt * 3;
-		for (int c = tid; c < chains; c += kSkBlock)
-		{
-			const int j = c / 3, a = c % 3;
-			if (a == 0)
-			{
-				if (nch > 1)
-				{
-					const SkC z1 = ex[j];
-					SkC z = z1;   // z = e_x^m
-					for (int m = 1; m <= (nch - 1) * s.L; ++m)
-					{
-						if (m % s.L == 0) tc[(size_t)j * nch + m / s.L] = z;
-						z = sk_mul(z, z1);
-					}
-				}
-			}
-			else if (a == 1)
-			{
-				if (s.hy > 1)
-				{
-					const SkC z1 = ty[(size_t)j * sy + 1];
-					SkC z = z1;
-					for (int m = 2; m <= s.hy; ++m) { z = sk_mul(z, z1); ty[(size_t)j * sy + m] = z; }
-				}
-			}
-			else if (DIM3 && s.hz > 1)
-			{
-				const SkC z1 = tz[(size_t)j * sz + 1];
-				SkC z = z1;
-				for (int m = 2; m <= s.hz; ++m) { z = sk_mul(z, z1); tz[(size_t)j * sz + m] = z; }
-			}
-		}
+		sk_power_tables<DIM3>(s, cnt, ex, ty, tz, tc);
 		__syncthreads();
 		if (live)
 		{
@@ -188,9 +197,11 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 
 // rho[j] = the sum over the ranges of part[range][j], j over the 2 K doubles, in a fixed order: the ranges are cut into kSkSlices
 // consecutive slices, a lane adds the ranges of one slice in index order, and the lane of slice 0 adds the slice sums in slice order.
-// A workgroup serves 256 / kSkSlices neighbouring j (one 128-byte line per slice and range).
+// A workgroup serves 256 / kSkSlices neighbouring j (one 128-byte line per slice and range).  In general a k has a record of REC
+// doubles and record k goes to rho + k * ostride: REC = ostride = 2 here, 8 doubles into a frame of a series for nbco_modes_record.
 constexpr int kSkSlices = 16, kSkReduceJ = kSkBlock / kSkSlices;
-__global__ __launch_bounds__(kSkBlock) void sk_reduce_kernel(const double *__restrict__ part, long long ranges, long long K2, double *__restrict__ rho)
+template <int REC>
+__global__ __launch_bounds__(kSkBlock) void sk_reduce_kernel(const double *__restrict__ part, long long ranges, long long K2, double *__restrict__ rho, long long ostride)
 {
 	__shared__ double slice_sum[kSkBlock];
 	const int tid = (int)threadIdx.x, q = tid / kSkReduceJ;
@@ -208,6 +219,6 @@ __global__ __launch_bounds__(kSkBlock) void sk_reduce_kernel(const double *__res
 	if (q == 0 && j < K2)
 	{
 		for (int t = 1; t < kSkSlices; ++t) sum += slice_sum[t * kSkReduceJ + tid];
-		rho[j] = sum;
+		rho[(size_t)(j / REC) * (size_t)ostride + (size_t)(j % REC)] = sum;
 	}
 }

@@ -253,6 +253,10 @@ def _load():
         "nbco_traj_record": [P, P, LL, P, P, LL, I, I, I],
         "nbco_time_corr": [P, P, LL, I, I, I, P],
         "nbco_time_corr_derive": [P, I, P],
+        "nbco_modes_record": [P, P, LL, C.POINTER(SkGrid), P, I, I, C.POINTER(LL)],
+        "nbco_mode_corr": [P, P, C.POINTER(SkGrid), I, I, I, P],
+        "nbco_mode_corr_ref": [P, C.POINTER(SkGrid), I, I, I, P],
+        "nbco_mode_corr_derive": [P, C.POINTER(SkGrid), I, D, P],
         "nbco_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
         "nbco_aperture_apply": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL), P, P, LL],
         "nbco_2d_aperture_count": [P, P, LL, C.POINTER(Aperture), C.POINTER(LL)],
@@ -386,6 +390,61 @@ def time_corr_derive(rec):
     rc = _load().nbco_time_corr_derive(raw.ctypes.data_as(C.c_void_p), raw.shape[0], out.ctypes.data_as(C.c_void_p))
     if rc != 0:
         raise EngineError("nbco_time_corr_derive failed with status %d" % rc, status=rc)
+    return out
+
+
+MODE_LAG = [("rr", "<f8"), ("ll", "<f8"), ("jj", "<f8"), ("s0", "<f8", (2,)), ("s1", "<f8", (2,)), ("pairs", "<u8")]   # nbco_mode_lag as a numpy record, 64 bytes
+
+
+def _sk_grid(h, kstep, dim=3):
+    g = SkGrid()
+    for a in range(dim):
+        g.h[a] = int(h[a])
+        g.kstep[a] = float(kstep[a])
+    return g
+
+
+def _sk_count(h):
+    """K of a 3-D grid, 0 for an h the library refuses (nothing is sized by a bad h)"""
+    if not all(0 <= int(h[a]) <= 64 for a in range(3)):
+        return 0
+    return (int(h[0]) + 1) * (2 * int(h[1]) + 1) * (2 * int(h[2]) + 1)
+
+
+def mode_corr_ref(series, h, kstep, frames, lags):
+    """the raw sums of Engine.mode_corr formed on the host by the same rule (nbco_mode_corr_ref, include/nbco.h): series a float64
+    numpy array K x frames_cap x 8 of mode records.  Returns a numpy array K x lags of MODE_LAG records with the bytes the device
+    returns for the same series.  Host only, needs no GPU."""
+    import numpy as np
+    series = np.ascontiguousarray(series, dtype=np.float64)
+    K = _sk_count(h)
+    if series.ndim != 3 or series.shape[0] != K or series.shape[2] != 8:
+        raise EngineError("mode_corr_ref: series must be K x frames_cap x 8 for this grid", status=1)
+    out = np.zeros((K, max(int(lags), 0)), dtype=MODE_LAG)
+    g = _sk_grid(h, kstep)
+    rc = _load().nbco_mode_corr_ref(series.ctypes.data_as(C.c_void_p), C.byref(g), int(series.shape[1]), int(frames), int(lags), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise EngineError("nbco_mode_corr_ref failed with status %d" % rc, status=rc)
+    return out
+
+
+def mode_corr_derive(rec, h, kstep, n_norm):
+    """F, F_c, C_L, C_T per (k, lag) from the raw sums of Engine.mode_corr (nbco_mode_corr_derive, include/nbco.h): rec a device tensor
+    as mode_corr returns it, or a numpy array K x lags of MODE_LAG records (or K x lags x 8 float64 holding them).  Returns a float64
+    array K x lags x 4.  pairs == 0 or n_norm <= 0 gives zeros, k = 0 gives C_L = C_T = 0.  Host only, needs no GPU."""
+    import numpy as np
+    if hasattr(rec, "cpu"):
+        rec = rec.cpu().numpy()
+    K = _sk_count(h)
+    raw = np.ascontiguousarray(rec).view(np.uint8).reshape(-1, 64)
+    if K == 0 or raw.shape[0] % K != 0:
+        raise EngineError("mode_corr_derive: rec must hold K x lags records for this grid", status=1)
+    lags = raw.shape[0] // K
+    out = np.empty((K, lags, 4), dtype=np.float64)
+    g = _sk_grid(h, kstep)
+    rc = _load().nbco_mode_corr_derive(raw.ctypes.data_as(C.c_void_p), C.byref(g), lags, float(n_norm), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise EngineError("nbco_mode_corr_derive failed with status %d" % rc, status=rc)
     return out
 
 
@@ -836,6 +895,35 @@ class Engine:
         if out is None:
             out = self.torch.empty((max(int(lags), 0), 8), dtype=self.torch.float64, device=traj.device)
         self._chk(self.lib.nbco_time_corr(self.ctx, _ptr(traj), int(rows), int(traj.shape[1]), int(frames), int(lags), _ptr(out)))
+        return out
+
+    # ---- collective modes ----------------------------------------------------------------------------
+    def modes_record(self, buf, n, h, kstep, series=None, frames_cap=1, frame=0, count=True):
+        """the mode records {rho, jx, jy, jz} (complex: eight doubles) of the state buf = [pos n | vel n ..] on the grid of
+        structure_factor, written to frame `frame` of series, a float64 device tensor K x frames_cap x 8 (nbco_modes_record;
+        allocated if None -- the other frames then hold whatever the allocation held -- and only that frame overwritten if given,
+        its frames_cap then taken from the tensor).  Returns (series, n_used): n_used the number of particles that counted (finite
+        position and velocity); rho at k = 0 is exactly (n_used, 0).  count=False returns n_used = None and does not synchronise.
+        The state and the engine are not touched."""
+        if series is None:
+            series = self.torch.empty((_sk_count(h), max(int(frames_cap), 0), 8), dtype=self.torch.float64, device=buf.device)
+        else:
+            frames_cap = int(series.shape[1])
+        used = C.c_longlong(0)
+        g = _sk_grid(h, kstep)
+        self._chk(self.lib.nbco_modes_record(self.ctx, _ptr(buf), n, C.byref(g), _ptr(series), int(frames_cap), int(frame), C.byref(used) if count else None))
+        return series, (used.value if count else None)
+
+    def mode_corr(self, series, h, kstep, frames, lags, out=None):
+        """the raw time-correlation sums of the first `frames` frames of every k of series (as modes_record fills it) for the lags
+        0 .. lags - 1 (nbco_mode_corr; 1 <= lags <= frames <= series.shape[1], frames <= 1024): a float64 device tensor
+        K x lags x 8 (allocated if None, overwritten if given) whose rows are nbco_mode_lag records -- rr, ll, jj, s0[2], s1[2] and,
+        in the last 8 bytes, the integer pairs: out.cpu().numpy().view(MODE_LAG) reads them, mode_corr_derive(out, h, kstep, n)
+        gives F, F_c, C_L and C_T.  The bytes are those of mode_corr_ref for the same series.  series is not modified."""
+        if out is None:
+            out = self.torch.empty((_sk_count(h), max(int(lags), 0), 8), dtype=self.torch.float64, device=series.device)
+        g = _sk_grid(h, kstep)
+        self._chk(self.lib.nbco_mode_corr(self.ctx, _ptr(series), C.byref(g), int(series.shape[1]), int(frames), int(lags), _ptr(out)))
         return out
 
     # ---- aperture ---------------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "slices_file.hpp"
 #include "sk_file.hpp"
 #include "corr_file.hpp"
+#include "modes_file.hpp"
 
 using namespace nbco_ref;
 using namespace std::chrono;
@@ -113,6 +114,19 @@ const char *kHelp =
     "                    same rule from the same header on the host: pairs equal, the sums to rounding.  Works with -aperture, -bath, -B.\n"
     "                    Refused with -test, -test2 and -accuracy.\n"
     "  -corr-start <iter>   The first iteration that may be a frame of -corr (default 0).\n"
+    "  -modes <hx> <hy> <hz> <kx> <ky> <kz> <frames> <lags>   Collective dynamics: from the first snapshot iteration >= -modes-start on, every\n"
+    "                    snapshot records the density and current modes rho_k = sum_j exp(i k . x_j), j_k = sum_j v_j exp(i k . x_j) on the\n"
+    "                    grid of -sk until <frames> are in (<= 1024; the frame spacing is the snapshot interval, -steps).  When the window is\n"
+    "                    full, or at the end of the run, <output>/modes.bin receives one 64-byte record per k and lag 0 .. <lags> - 1 (as far\n"
+    "                    as the recorded frames allow; record (k, lag) at k * lags + lag): the raw sums rr, ll, jj, s0[2], s1[2] as doubles\n"
+    "                    and pairs as a 64-bit integer (nbco_mode_corr), <output>/modes_derived.bin four doubles F F_c C_L C_T per record --\n"
+    "                    the intermediate scattering function, its connected part, the longitudinal and the transverse current correlation\n"
+    "                    (nbco_mode_corr_derive, normalised by the mean number of particles that counted) -- and <output>/modes.txt one line\n"
+    "                    'ix iy iz |k| F Fc CL CT' per k at lag 0.  A frame is recorded after the aperture and before the other outputs.  No\n"
+    "                    particle identity is needed: the order tracking stays as it is and leapfrog keeps its fused pass.  With -cpu the\n"
+    "                    frames are summed on the host in index order (equal to rounding) and correlated by nbco_mode_corr_ref.  Works with\n"
+    "                    -aperture, -bath, -B.  Refused with -test, -test2 and -accuracy.\n"
+    "  -modes-start <iter>   The first iteration that may be a frame of -modes (default 0).\n"
     "  -aperture <ellipsoid|box> <hx> <hy> <hz>   At every snapshot iteration, after the step and before the snapshot, drop the particles\n"
     "                    outside the aperture with these half axes ('inf' opens an axis: pipes, slabs) from the run: they are lost and no\n"
     "                    longer simulated (nbco_aperture_apply; with -cpu the same rule on the host).  Per snapshot\n"
@@ -417,8 +431,27 @@ struct Session
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
 	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const SkOpt &sk, const ApertureOpt &aperture,
-	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath, const CorrOpt &corr)
+	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath, const CorrOpt &corr, const ModesOpt &modes)
 	{
+		// -modes: the series of mode records on the device (K x frames x 8 doubles) and the records of the lags
+		ModesWindow mwin(modes);
+		DeviceArray<double> modes_series(modes.on ? (size_t)modes.K * (size_t)modes.frames * 8 : 0);
+		DeviceArray<nbco_mode_lag> modes_out(modes.on ? (size_t)modes.K * (size_t)modes.lags : 0);
+		auto modes_finish = [&]() {
+			std::vector<nbco_mode_lag> rec((size_t)modes.K * (size_t)mwin.lags());
+			std::vector<double> row((size_t)mwin.recorded * 8), rho0;
+			if (!rec.empty())
+			{
+				check(nbco_mode_corr(ctx(), modes_series.ptr, &modes.g, modes.frames, mwin.recorded, mwin.lags(), modes_out.ptr), "mode_corr");
+				check(nbco_sync(ctx()), "sync");
+				HIPCHK(hipMemcpy(rec.data(), modes_out.ptr, rec.size() * sizeof(nbco_mode_lag), hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(row.data(), modes_series.ptr + mwin.k0() * (size_t)modes.frames * 8, row.size() * sizeof(double), hipMemcpyDeviceToHost));
+				for (int f = 0; f < mwin.recorded; ++f) rho0.push_back(row[8 * (size_t)f]);
+			}
+			if (mwin.write(folder, rec, rho0)) return true;
+			std::cerr << "Error: cannot write the modes files into \"" << folder << "\"" << std::endl;
+			return false;
+		};
 		// -corr: the window of frames on the device (rows by the particles the run starts with) and the records of the lags
 		CorrWindow cwin(corr, n);
 		DeviceArray<float> corr_traj(corr.on ? (size_t)cwin.rows * (size_t)corr.frames * 6 : 0);
@@ -540,6 +573,13 @@ struct Session
 				++cwin.recorded;
 				if (cwin.full() && !corr_finish()) return -1;
 			}
+			if (const int frame = mwin.frame_for(snap); frame >= 0)
+			{
+				// sums over the particles: the order of the state does not matter to them
+				check(nbco_modes_record(ctx(), state.ptr, n, &modes.g, modes_series.ptr, modes.frames, frame, nullptr), "modes_record");
+				++mwin.recorded;
+				if (mwin.full() && !modes_finish()) return -1;
+			}
 			HIPCHK(hipMemcpy(host.data(), state.ptr, state_bytes, hipMemcpyDeviceToHost));   // acc not copied
 			std::ofstream fout(folder + "/out" + std::to_string(snap) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)
@@ -656,6 +696,7 @@ struct Session
 		}
 		check(nbco_sync(ctx()), "sync");
 		if (corr.on && !cwin.written && !corr_finish()) return -1;
+		if (modes.on && !mwin.written && !modes_finish()) return -1;
 		std::cout << std::endl;
 		// (not in the reference: wall time of the integration loop behind the first snapshot -- what bench.py's `cli` leg reads)
 		const auto loop_t1 = std::chrono::steady_clock::now();
@@ -683,6 +724,7 @@ int main(int argc, const char **argv)
 	double bonds_rmax = 0;
 	SkOpt sk;
 	CorrOpt corr;
+	ModesOpt modes;
 	ApertureOpt aperture;
 	SlicesOpt slices;
 	bool in = false, test = false, test2 = false, b_accuracy = false, input_order = false, cpu = false, energy = false, moments = false, bfield = false;
@@ -868,6 +910,25 @@ int main(int argc, const char **argv)
 			corr.start = (int)v;
 			++i;
 		}
+		else if (a == "-modes")
+		{
+			if (!need(i, 8, "-modes")) return -1;
+			if (!parse_modes(argv + i + 1, modes))
+			{
+				std::cerr << "Error: invalid argument(s) to '-modes' (hx hy hz: integers 0..64; kx ky kz: finite and greater than 0; frames, lags: integers with 1 <= lags <= frames <= 1024)\n";
+				return -1;
+			}
+			i += 8;
+		}
+		else if (a == "-modes-start")
+		{
+			if (!need(i, 1, "-modes-start")) return -1;
+			char *end = nullptr;
+			const long v = std::strtol(argv[i + 1], &end, 10);
+			if (end == argv[i + 1] || *end || v < 0 || v > 0x7fffffffL) { std::cerr << "Error: invalid argument to '-modes-start': " << argv[i + 1] << " (an iteration >= 0)\n"; return -1; }
+			modes.start = (int)v;
+			++i;
+		}
 		else if (a == "-aperture")
 		{
 			if (!need(i, 4, "-aperture")) return -1;
@@ -997,6 +1058,12 @@ int main(int argc, const char **argv)
 		return -1;
 	}
 
+	if (modes.on && (test || test2 || b_accuracy))
+	{
+		std::cerr << "Error: '-modes' follows a simulation: it cannot be combined with -test, -test2 or -accuracy\n";
+		return -1;
+	}
+
 	// ---- state ---------------------------------------------------------------------------------------
 	std::vector<float> host;   // [pos | vel] as the state files hold them; the accelerations never leave the device
 	if (in)
@@ -1071,6 +1138,25 @@ int main(int argc, const char **argv)
 			std::cerr << "Error: cannot write the correlation files into \"" << strout << "\"" << std::endl;
 			return false;
 		};
+		// -modes: the series of mode records on the host
+		ModesWindow mwin(modes);
+		std::vector<double> modes_series(modes.on ? (size_t)modes.K * (size_t)modes.frames * 8 : 0);
+		auto modes_finish = [&]() {
+			std::vector<nbco_mode_lag> rec((size_t)modes.K * (size_t)mwin.lags());
+			std::vector<double> rho0;
+			if (!rec.empty())
+			{
+				if (nbco_mode_corr_ref(modes_series.data(), &modes.g, modes.frames, mwin.recorded, mwin.lags(), rec.data()) != NBCO_OK)
+				{
+					std::cerr << "Error: nbco_mode_corr_ref refused the recorded series" << std::endl;
+					return false;
+				}
+				for (int f = 0; f < mwin.recorded; ++f) rho0.push_back(modes_series[(mwin.k0() * (size_t)modes.frames + (size_t)f) * 8]);
+			}
+			if (mwin.write(strout, rec, rho0)) return true;
+			std::cerr << "Error: cannot write the modes files into \"" << strout << "\"" << std::endl;
+			return false;
+		};
 		for (int iter = 0; iter < nIters; ++iter)
 		{
 			nbco_cpu::integrate(scheme, st.data(), nBodies, par, o.eps2, (long double)dt, bfield ? omega_b : nullptr, bath_on ? &bath : nullptr, (unsigned long long)iter);
@@ -1104,6 +1190,12 @@ int main(int argc, const char **argv)
 				nbco_cpu::traj_record(st.data(), nBodies, corr_ids, corr_traj, cwin.rows, corr.frames, frame, corr.stride);
 				++cwin.recorded;
 				if (cwin.full() && !corr_finish()) return -1;
+			}
+			if (const int frame = mwin.frame_for(iter); frame >= 0)
+			{
+				nbco_cpu::modes_record(st.data(), nBodies, modes.g, modes_series, modes.frames, frame);
+				++mwin.recorded;
+				if (mwin.full() && !modes_finish()) return -1;
 			}
 			std::ofstream fout(strout + "/out" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
 			if (!fout)
@@ -1163,6 +1255,7 @@ int main(int argc, const char **argv)
 			}
 		}
 		if (corr.on && !cwin.written && !corr_finish()) return -1;
+		if (modes.on && !mwin.written && !modes_finish()) return -1;
 		std::cout << std::endl;
 		return 0;
 	}
@@ -1176,7 +1269,7 @@ int main(int argc, const char **argv)
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
 		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, b_accuracy ? SkOpt{} : sk, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
-		                     b_accuracy ? nbco_bath{} : bath, corr);
+		                     b_accuracy ? nbco_bath{} : bath, corr, modes);
 	}
 	return rc;
 }

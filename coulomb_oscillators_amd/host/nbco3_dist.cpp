@@ -473,6 +473,7 @@ int main(int argc, char **argv)
 		else if (f == "-B") { std::cerr << "Error: '-B' is not available with kd-domain sharding (nbco_dist_turnaround drifts straight; there is no magnetic form of it): nbco3 serves it\n"; return -1; }
 		else if (f == "-sk") { std::cerr << "Error: '-sk' is not available with kd-domain sharding (nbco_structure_factor sums one context's particles; add the rho of the shards): nbco3 serves it\n"; return -1; }
 		else if (f == "-corr" || f == "-corr-start") { std::cerr << "Error: '" << f << "' is not available with kd-domain sharding (a particle changes rank and local row; nbco_traj_record follows one context's order map): nbco3 serves it\n"; return -1; }
+		else if (f == "-modes" || f == "-modes-start") { std::cerr << "Error: '" << f << "' is not available with kd-domain sharding (nbco_modes_record sums one context's particles; add the records of the shards): nbco3 serves it\n"; return -1; }
 		else if (f == "-bath") { std::cerr << "Error: '-bath' is not available with kd-domain sharding (nbco_dist_turnaround has no bath step, and a row there is a rank's local row): nbco3 serves it\n"; return -1; }
 		else { std::cerr << "Error: unrecognised option '" << argv[i] << "'\n"; return -1; }
 	}

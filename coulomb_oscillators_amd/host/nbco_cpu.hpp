@@ -18,6 +18,7 @@
 #include "../csrc/bond_order.hpp"
 #include "../csrc/structure_factor.hpp"
 #include "../csrc/time_corr.hpp"
+#include "../csrc/modes.hpp"
 
 namespace nbco_cpu {
 
@@ -318,6 +319,51 @@ inline long long structure_factor(const V3 *x, int n, const nbco_sk_grid &g, std
 		}
 	});
 	return (long long)rho[2 * ((size_t)hy * nz + hz)];
+}
+
+// One frame of mode records for `nbco3 -cpu -modes`, by the rule of nbco_modes_record (include/nbco.h) from csrc/modes.hpp, the header
+// the device kernels use: the phases, powers and products of structure_factor above, a particle counting iff its phases and its three
+// velocity floats are finite, md_add per counted particle and k.  st = [pos n | vel n | ..]; series holds K x frames_cap x 8 doubles and
+// frame `frame` of every k is overwritten.  Returns the number of particles that counted.  A fixed partition: every worker owns a range
+// of columns (iy, iz) and adds all particles in index order.  The device adds in another order: equal to rounding only.
+inline long long modes_record(const V3 *st, int n, const nbco_sk_grid &g, std::vector<double> &series, int frames_cap, int frame)
+{
+	const int hx = g.h[0], hy = g.h[1], hz = g.h[2], ny = 2 * hy + 1, nz = 2 * hz + 1, cols = ny * nz;
+	const double w[3] = {g.kstep[0] / kSkTwoPi, g.kstep[1] / kSkTwoPi, g.kstep[2] / kSkTwoPi};
+	double *out = series.data();
+	for_ranges(cols, [=](int lo, int hi) {
+		std::vector<MdRec> acc((size_t)(hi - lo) * (hx + 1));
+		for (MdRec &r : acc) md_zero(r);
+		std::vector<SkC> ty((size_t)hy + 1), tz((size_t)hz + 1);
+		for (int j = 0; j < n; ++j)
+		{
+			const V3 p = st[j], v = st[n + j];
+			const double t0 = (double)p.x * w[0], t1 = (double)p.y * w[1], t2 = (double)p.z * w[2];
+			if (!(std::isfinite(t0) && std::isfinite(t1) && std::isfinite(t2) && std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z))) continue;
+			const SkC ex = sk_phase(t0), ey = sk_phase(t1), ez = sk_phase(t2);
+			ty[0] = tz[0] = SkC{1.0, 0.0};
+			for (int m = 1; m <= hy; ++m) ty[m] = m == 1 ? ey : sk_mul(ty[m - 1], ey);
+			for (int m = 1; m <= hz; ++m) tz[m] = m == 1 ? ez : sk_mul(tz[m - 1], ez);
+			for (int col = lo; col < hi; ++col)
+			{
+				const int iy = col / nz - hy, iz = col % nz - hz;
+				SkC t = sk_mul(sk_conj_if(ty[std::abs(iy)], iy < 0), sk_conj_if(tz[std::abs(iz)], iz < 0));
+				for (int ix = 0; ix <= hx; ++ix)
+				{
+					md_add(acc[(size_t)(col - lo) * (hx + 1) + ix], t, (double)v.x, (double)v.y, (double)v.z);
+					t = sk_mul(t, ex);
+				}
+			}
+		}
+		for (int col = lo; col < hi; ++col)
+			for (int ix = 0; ix <= hx; ++ix)
+			{
+				const MdRec &r = acc[(size_t)(col - lo) * (hx + 1) + ix];
+				double *o = out + (((size_t)ix * (size_t)cols + (size_t)col) * (size_t)frames_cap + (size_t)frame) * 8;
+				o[0] = r.rho.re; o[1] = r.rho.im; o[2] = r.jx.re; o[3] = r.jx.im; o[4] = r.jy.re; o[5] = r.jy.im; o[6] = r.jz.re; o[7] = r.jz.im;
+			}
+	});
+	return (long long)series[(((size_t)hy * nz + hz) * (size_t)frames_cap + (size_t)frame) * 8];
 }
 
 // One frame of a trajectory buffer for `nbco3 -cpu -corr`, as nbco_traj_record (include/nbco.h) writes it: frame `frame` of every row

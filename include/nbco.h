@@ -839,8 +839,9 @@ int nbco_2d_bond_order(nbco_ctx *c, const double *p, long long n, double rmax, i
  * by it, no grid is refused for it).  The tree, the rebuild schedule, the warm-select history, the order tracking, nbco_kd_get_info
  * and a valid nbco_energy_fmm / nbco_kd_potential / nbco_kd_probe stay as they were; a following call returns the bits it would
  * have returned.
- * Not offered: arbitrary k lists, weights, the dynamic S(k, omega), the shell average S(|k|) and the division by n (fold on the
- * host), and sharded runs (add the rho of the shards). */
+ * Not offered: arbitrary k lists, weights other than the velocities (the current modes and the time series behind the dynamic
+ * S(k, omega): nbco_modes_record, nbco_mode_corr), the shell average S(|k|) and the division by n (fold on the host), and sharded
+ * runs (add the rho of the shards). */
 typedef struct nbco_sk_grid { int h[3]; double kstep[3]; } nbco_sk_grid;      /* HOST memory; 2-D reads [0..1] */
 int nbco_structure_factor(nbco_ctx *c, const float *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host);
 int nbco_2d_structure_factor(nbco_ctx *c, const double *p, long long n, const nbco_sk_grid *g_host, double *rho_dev, long long *n_used_host);
@@ -888,11 +889,69 @@ int nbco_sk_phase(double t, double *cs_host);
  * alpha2 = 3 <r^4> / (5 <r^2>^2) - 1 and vacf_c = vv[c] / pairs.  pairs == 0 gives eight zeros and msd == 0 (lag 0, particles at rest)
  * alpha2 = 0: never NaN.  NBCO_ERR_ARG for a NULL pointer or lags < 0.
  * Not offered: the 2-D state (nbco_2d_fmm leaves it in cell order and keeps no order map), sharded runs, correlations between
- * different particles and S(k, omega), more than 2048 frames, and the Fourier transform of the VACF (a few thousand points: host). */
+ * different particles (the collective ones, F(k, tau) and the current correlations behind S(k, omega): nbco_modes_record,
+ * nbco_mode_corr), more than 2048 frames, and the Fourier transform of the VACF (a few thousand points: host). */
 typedef struct nbco_corr_lag { double dx2[3]; double r4; double vv[3]; unsigned long long pairs; } nbco_corr_lag;   /* 64 bytes */
 int nbco_traj_record(nbco_ctx *c, const float *buf, long long n, const int *ids_dev, float *traj, long long rows, int frames_cap, int frame, int stride);
 int nbco_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_cap, int frames, int lags, nbco_corr_lag *out_dev);
 int nbco_time_corr_derive(const nbco_corr_lag *in, int lags, double *out);
+/* ---- collective dynamics: the time correlations of the density and current modes of the cloud -- what one-component-plasma and
+ * Coulomb-crystal work reads off a run: the intermediate scattering function F(k, tau), whose host-side transform is S(k, omega)
+ * (plasmon and trap-mode dispersion, the lifetime of a Bragg peak), the longitudinal current correlation C_L(k, tau) (the plasmon
+ * peak and its damping) and the transverse one C_T(k, tau) (shear modes, which a fluid damps and a solid carries).  3-D only.  No
+ * particle identity is needed: opts.track_order may stay off.
+ * nbco_modes_record writes the MODE RECORD of every wave vector of the grid of nbco_structure_factor -- eight doubles {rho.re, rho.im,
+ * jx.re, jx.im, jy.re, jy.im, jz.re, jz.im}, rho_k = sum_j exp(i k . x_j), j_k = sum_j v_j exp(i k . x_j) -- of the state buf (pos at
+ * buf, vel at buf + 3 n, as for nbco_traj_record) to series_dev[(k * frames_cap + frame) * 8 ..], k nbco_structure_factor's index:
+ * the caller owns a DEVICE buffer of K x frames_cap x 8 doubles in which the series of one k is contiguous; frames_cap = 1, frame = 0
+ * is a plain snapshot of K records.  All K records of that frame are overwritten, not accumulated; nothing else in the buffer is
+ * touched.  n_used_host may be NULL; with it the call synchronises and writes the number of particles that counted, without it the
+ * call returns as the evaluators do (opts.sync, opts.stream).
+ * The rule, which is the numerical contract, is written once, in csrc/modes.hpp, for the kernels, nbco_mode_corr_ref,
+ * nbco_mode_corr_derive and `nbco3 -cpu -modes`.  Phases, powers and the term w of (ix, iy, iz) are those of nbco_structure_factor.  A
+ * particle counts iff every t_a is finite and all three velocity floats are finite, and otherwise adds nothing to any of the four
+ * sums.  Per counted particle and k: rho.re += w.re; rho.im += w.im; j_c.re <- fma(v_c, w.re, j_c.re); j_c.im <- fma(v_c, w.im, j_c.im),
+ * v_c the float widened to double.  rho at k = 0 is exactly (n_used, 0) and j at k = 0 has the imaginary part exactly 0.  The rho
+ * part NEED NOT have the bytes of nbco_structure_factor (that call counts by the positions alone and tiles differently); both lie
+ * within its bound.  j_c lies within u V_c (8 (h[0]+h[1]+h[2]+1) + 2 n + 2) of the exact sum, V_c the sum of |v_c|, u = 2^-53.
+ * Determinism is that of nbco_structure_factor: the particle ranges depend on n and the grid alone, every sum has a fixed order and
+ * there are no float atomics: a second call returns the same bytes, on any stream, in either opts.sync setting and on any card.
+ * `nbco3 -cpu -modes` records in index order and AGREES WITH THE DEVICE ONLY TO ROUNDING.
+ * Refused before any launch, the outputs untouched: what nbco_structure_factor refuses (series_dev in the place of rho_dev), and with
+ * NBCO_ERR_ARG frames_cap < 1 and a frame outside [0, frames_cap).
+ * State: the records of the particle ranges live in scratch of the call's own (at most 256 MiB).  The tree, the rebuild schedule, the
+ * warm-select history, the order map, nbco_kd_get_info and every valid diagnostic stay bit for bit as they were.
+ * nbco_mode_corr sums, for every k and every lag tau = 0 .. lags - 1, over the origins t with t + tau < frames, in increasing t, and
+ * writes record (k, tau) to out_dev[k * lags + tau] (DEVICE memory, K * lags records, overwritten); 1 <= lags <= frames <= frames_cap
+ * and frames <= 1024.  With a = record(t), b = record(t + tau), k_c = (double) i_c * kstep[c] and P(r) = k . j of r,
+ * P(r).re = fma(k_z, r.jz.re, fma(k_y, r.jy.re, k_x * r.jx.re)) and likewise .im, a record holds as RAW SUMS:
+ *   rr      fma(a.rho.im, b.rho.im, fma(a.rho.re, b.rho.re, rr)): the sum of Re[rho(t + tau) conj rho(t)];
+ *   jj      six fma in the order x.re, x.im, y.re, y.im, z.re, z.im: the sum of Re[j(t + tau) . conj j(t)];
+ *   ll      fma(P(a).im, P(b).im, fma(P(a).re, P(b).re, ll)): the sum of Re[P(t + tau) conj P(t)];
+ *   s0, s1  the complex sums of a.rho and of b.rho, plain additions (the means the connected part subtracts);
+ *   pairs   frames - tau, an exact integer.
+ * There is no finiteness test: a record written by nbco_modes_record is finite, and a non-finite one supplied by the caller
+ * propagates.  A (k, tau) is formed by one lane from start to end; there is no sum across lanes or workgroups.
+ * nbco_mode_corr_ref (host only, no GPU needed) is the same rule in plain loops over series_host and out_host in HOST memory:
+ * THE DEVICE AND THIS CALL RETURN THE SAME BYTES for the same series.
+ * Refused with NBCO_ERR_ARG before any launch, out untouched: a NULL pointer; any h[a] < 0 or > 64, any kstep[a] not finite or <= 0;
+ * lags < 1, lags > frames, frames > frames_cap, frames > 1024.
+ * nbco_mode_corr_derive (host only, compiled without contraction, like nbco_time_corr_derive): `in` K * lags records and `out`
+ * K * lags * 4 doubles in HOST memory; per (k, lag), with m = (double) pairs, d = m * n_norm and k2 = (k_x^2 + k_y^2) + k_z^2,
+ *   F   = rr / d;
+ *   F_c = (rr - (s1.re * s0.re + s1.im * s0.im) / m) / d, the connected part: the rho_k of a trapped cloud has a large static
+ *         mean, its form factor;
+ *   C_L = ll / (k2 * d);
+ *   C_T = (jj - ll / k2) / (2 d).
+ * n_norm is the caller's particle number (the mean of rho.re at k = 0 over the frames).  k2 == 0 gives C_L = C_T = 0; pairs == 0 or
+ * n_norm <= 0 gives four zeros: never NaN for finite input.  NBCO_ERR_ARG for a NULL pointer, lags < 0 or an h outside 0..64.
+ * Not offered: the 2-D programs, sharded runs, lists of k, the imaginary parts of the correlations, the transform to omega (a few
+ * thousand points per k: host) and more than 1024 frames per call. */
+typedef struct nbco_mode_lag { double rr, ll, jj; double s0[2]; double s1[2]; unsigned long long pairs; } nbco_mode_lag;   /* 64 bytes */
+int nbco_modes_record(nbco_ctx *c, const float *buf, long long n, const nbco_sk_grid *g_host, double *series_dev, int frames_cap, int frame, long long *n_used_host);
+int nbco_mode_corr(nbco_ctx *c, const double *series_dev, const nbco_sk_grid *g_host, int frames_cap, int frames, int lags, nbco_mode_lag *out_dev);
+int nbco_mode_corr_ref(const double *series_host, const nbco_sk_grid *g_host, int frames_cap, int frames, int lags, nbco_mode_lag *out_host);
+int nbco_mode_corr_derive(const nbco_mode_lag *in, const nbco_sk_grid *g_host, int lags, double n_norm, double *out);
 /* ---- aperture: particles that cross a boundary (a pipe wall, an electrode) are lost -- dropped from the state on the device,
  * recorded, and no longer simulated.  nbco_aperture_count / nbco_aperture_apply serve the 3-D fp32 state, the nbco_2d_ forms the
  * 2-D fp64 state (they read centre[0..1] and half[0..1] only).  *ap_host lies in HOST memory.
