@@ -1,9 +1,10 @@
 // dispatch.hpp -- the switches that turn a run-time choice into a template argument: the expansion order, the element type of the
-// far-field tuples, the output set of a probe call, the variant of the pass between two leapfrog steps.  A launch function calls them around its hipLaunchKernelGGL: the only place
+// far-field tuples, the output set of a probe call, the variant of the pass between two leapfrog steps, the template step of a run-time length.  A launch function calls them around its hipLaunchKernelGGL: the only place
 // where that kernel's variant is chosen.  Nothing here needs rocPRIM, so the kernel translation units include it directly.
 #pragma once
 #include "nbco_internal.hpp"
 #include <type_traits>
+#include <utility>
 
 // f(std::integral_constant<int, P>) for a run-time order 1 <= P <= PMAX; false (and no call) for any other order: the caller
 // reports the refusal in its own words
@@ -49,6 +50,18 @@ static void with_flag(bool on, F &&f)
 	if (on) f(std::true_type{});
 	else f(std::false_type{});
 }
+
+// f(std::integral_constant<int, A>) for the first of the ascending template steps A, .. that is at least v (the last one for a v
+// beyond them all); last_step is that last one
+template <int A, int... REST, class F>
+static void with_step(std::integer_sequence<int, A, REST...>, int v, F &&f)
+{
+	if constexpr (sizeof...(REST) == 0) f(std::integral_constant<int, A>{});
+	else if (v <= A) f(std::integral_constant<int, A>{});
+	else with_step(std::integer_sequence<int, REST...>{}, v, f);
+}
+template <int... A>
+constexpr int last_step(std::integer_sequence<int, A...>) { return (A, ...); }
 
 // f(drift) for the drift of a leapfrog step: the matrices of the helix drift (Helix3) where a magnetic field is given, the step length (float) otherwise
 template <class H, class F>

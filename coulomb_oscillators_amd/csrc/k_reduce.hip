@@ -528,14 +528,15 @@ int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R
 	return sum_host ? bond_summary_finish(c, rec, records, n, dim, sum_host) : NBCO_OK;
 }
 
-// ---- static structure factor (structure_factor_kernels.hpp) -----------------------------------------
-// The shape of a call, from n and the grid alone (never from the device): runs of ix of at most kSkMaxAcc, the cut of the items into
+// ---- sums on the wave-vector grid: static structure factor, mode records (structure_factor_kernels.hpp) ----
+// The shape of a call, from n and the grid alone (never from the device): runs of ix of at most the term's last step, the cut of the items into
 // workgroups (the fewest workgroups that keep 85 % of the lanes busy with `copies` copies of `lanes` items each, else the best cut up to
 // four times as many), the tile that fills the LDS budget, and the particle ranges -- at least 512 particles each, no more of them than bring the launch to about 2048 workgroups
-// or the partial sums to 256 MiB.  nbco_modes_record shares it: runs of at most max_acc, `extra` more 16-byte slots per particle in a
-// tile, `rec` bytes of partial sums per k.
-static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g, int max_acc = kSkMaxAcc, int extra = 0, int rec = 16)
+// or the partial sums to 256 MiB.
+template <class Term>
+static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g)
 {
+	constexpr int max_acc = last_step(typename Term::Steps{});
 	SkShape s;
 	s.hx = g.h[0]; s.hy = g.h[1]; s.hz = dim == 3 ? g.h[2] : 0;
 	s.nch = (s.hx + max_acc) / max_acc;
@@ -543,8 +544,8 @@ static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g, int max_acc
 	s.ny = 2 * s.hy + 1; s.nz = 2 * s.hz + 1;
 	s.items = s.nch * s.ny * s.nz;
 	s.K = sk_count(g.h, dim);
-	const int per = 1 + (s.hy + 1) + (dim == 3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0) + extra;   // complex numbers per particle
-	s.tile = std::min(kSkBlock, kSkLdsBytes / (16 * per));
+	s.per = 1 + Term::kExtra + (s.hy + 1) + (dim == 3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0);
+	s.tile = std::min(kSkBlock, kSkLdsBytes / (16 * s.per));
 	const int kt0 = (s.items + kSkBlock - 1) / kSkBlock;
 	int kt = kt0;
 	double best = 0.0;
@@ -558,59 +559,61 @@ static SkShape sk_shape(int dim, long long n, const nbco_sk_grid &g, int max_acc
 	s.lanes = (s.items + kt - 1) / kt;
 	s.copies = s.lanes <= kSkBlock / 2 ? kSkBlock / s.lanes : 1;
 	long long r0 = std::min((n + 511) / 512, std::max(1LL, (long long)(2048 / kt)));
-	r0 = std::max(1LL, std::min(r0, (256LL << 20) / (rec * s.K)));
+	r0 = std::max(1LL, std::min(r0, (256LL << 20) / (16 * Term::kParts * s.K)));
 	s.range = ((n + r0 - 1) / r0 + 63) / 64 * 64;
 	s.wx = g.kstep[0] / kSkTwoPi; s.wy = g.kstep[1] / kSkTwoPi; s.wz = dim == 3 ? g.kstep[2] / kSkTwoPi : 0.0;
 	return s;
 }
 
-template <bool DIM3, typename T>
-static int sk_run(nbco_ctx *c, const T *p, long long n, const SkShape &s, double *rho)
+// The sums of a term over the n rows at p: record k (2 * Term::kParts doubles) goes to rec + k * stride.  `part` keeps the partial
+// sums of the ranges where there are several.
+template <class Term, bool DIM3, typename T>
+static int kgrid_run(nbco_ctx *c, DevBuf &part, const T *p, long long n, const nbco_sk_grid &g, double *rec, long long stride, long long *n_used_host)
 {
+	constexpr int R = 2 * Term::kParts;
+	const SkShape s = sk_shape<Term>(DIM3 ? 3 : 2, n, g);
 	const long long ranges = (n + s.range - 1) / s.range;
-	double *out = rho;
+	double *out = rec;
+	long long ostride = stride;
 	if (ranges > 1)
 	{
-		NBCO_TRY(c->reserve(c->sk_part, sizeof(double) * 2 * (size_t)s.K * (size_t)ranges));
-		out = c->sk_part.as<double>();
+		NBCO_TRY(c->reserve(part, sizeof(double) * R * (size_t)s.K * (size_t)ranges));
+		out = part.as<double>();
+		ostride = R;
 	}
-	const int per = 1 + (s.hy + 1) + (DIM3 ? s.hz + 1 : 0) + (s.nch > 1 ? s.nch : 0);
-	const size_t lds = (size_t)16 * per * s.tile;
+	const size_t lds = std::max((size_t)16 * s.per * s.tile, (size_t)16 * kSkBlock);   // the tables of a tile; the copies' sums at the end
 	const dim3 grid((unsigned)((s.items + s.lanes - 1) / s.lanes), (unsigned)ranges), block(kSkBlock);
-#define NBCO_SK_STEP(A_) hipLaunchKernelGGL((sk_accumulate_kernel<A_, DIM3, T>), grid, block, lds, c->stream, p, n, s, out)
-	// the template steps of the run length L
-	if (s.L <= 1) NBCO_SK_STEP(1);
-	else if (s.L <= 2) NBCO_SK_STEP(2);
-	else if (s.L <= 3) NBCO_SK_STEP(3);
-	else if (s.L <= 5) NBCO_SK_STEP(5);
-	else if (s.L <= 9) NBCO_SK_STEP(9);
-	else if (s.L <= 13) NBCO_SK_STEP(13);
-	else NBCO_SK_STEP(17);
-#undef NBCO_SK_STEP
+	with_step(typename Term::Steps{}, s.L, [&](auto a) {
+		hipLaunchKernelGGL((kgrid_accumulate_kernel<Term, decltype(a)::value, DIM3, T>), grid, block, lds, c->stream, p, n, s, out, ostride);
+	});
 	NBCO_HIP(hipGetLastError());
 	if (ranges > 1)
 	{
-		hipLaunchKernelGGL(sk_reduce_kernel<2>, dim3((unsigned)((2 * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, 2 * s.K, rho, 2LL);
+		hipLaunchKernelGGL(sk_reduce_kernel<R>, dim3((unsigned)((R * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, R * s.K, rec, stride);
 		NBCO_HIP(hipGetLastError());
+	}
+	if (n_used_host)
+	{
+		// rho at k = 0, the first number of that record, is the exact count of the particles that counted
+		const size_t k0 = (size_t)s.hy * (size_t)s.nz + (size_t)s.hz;
+		double cnt = 0;
+		NBCO_HIP(hipMemcpyAsync(&cnt, rec + k0 * (size_t)stride, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+		NBCO_HIP(hipStreamSynchronize(c->stream));
+		*n_used_host = (long long)cnt;
 	}
 	return NBCO_OK;
 }
 
 int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, const nbco_sk_grid &g, double *rho, long long *n_used_host)
 {
-	const SkShape s = sk_shape(dim, n, g);
-	if (dim == 3) NBCO_TRY((sk_run<true, float>(c, (const float *)p, n, s, rho)));
-	else NBCO_TRY((sk_run<false, double>(c, (const double *)p, n, s, rho)));
-	if (n_used_host)
-	{
-		// rho at k = 0 is the exact count of the particles that counted
-		const size_t k0 = (size_t)s.hy * (size_t)s.nz + (size_t)s.hz;
-		double cnt = 0;
-		NBCO_HIP(hipMemcpyAsync(&cnt, rho + 2 * k0, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-		NBCO_HIP(hipStreamSynchronize(c->stream));
-		*n_used_host = (long long)cnt;
-	}
-	return NBCO_OK;
+	if (dim == 3) return kgrid_run<SkTerm, true>(c, c->sk_part, (const float *)p, n, g, rho, 2, n_used_host);
+	return kgrid_run<SkTerm, false>(c, c->sk_part, (const double *)p, n, g, rho, 2, n_used_host);
+}
+
+// record k of frame `frame` lies at series + 8 * frame + k * 8 * frames_cap
+int launch_modes_record(nbco_ctx *c, const float *buf, long long n, const nbco_sk_grid &g, double *series, int frames_cap, int frame, long long *n_used_host)
+{
+	return kgrid_run<MdTerm, true>(c, c->md_part, buf, n, g, series + 8 * (size_t)frame, 8 * (long long)frames_cap, n_used_host);
 }
 
 // ---- tracked trajectories and their time correlations (time_corr_kernels.hpp) -----------------------
@@ -623,20 +626,24 @@ int launch_traj_record(nbco_ctx *c, const float *buf, long long n, const int *id
 	return NBCO_OK;
 }
 
-// The shape of a call, from (rows, frames, lags) alone (never from the device): the lags a lane keeps (1 up to 64 lags, else pairs: 2 up
-// to 512 lags, 4 up to 1024, 8 beyond), the lanes of a row (a multiple of 64), the rows a workgroup has in flight (what 256 lanes and
-// 64 KiB of LDS hold) and the row ranges: no more than kTcMaxRanges, all but the last of one length.
+// The lags a lane keeps, from the lags alone: 1 up to 64 lags, else pairs (2 up to 512 lags, 4 up to 1024, 8 beyond, at most max_a),
+// with the lanes W of a row or a k (a multiple of 64) and the lags taken from the bottom.  Sets frames, lags, cap, half and W of s.
+static int tc_lag_shape(int frames_cap, int frames, int lags, int max_a, TcShape &s)
+{
+	s.frames = frames; s.lags = lags; s.cap = frames_cap;
+	if (lags <= 64) { s.half = lags; s.W = 64; return 1; }
+	s.half = (lags + 1) / 2;
+	const int A = std::min(max_a, s.half <= 256 ? 2 : s.half <= 512 ? 4 : 8);
+	s.W = A == 2 ? (s.half + 63) / 64 * 64 : kTcBlock;
+	return A;
+}
+
+// The shape of a call, from (rows, frames, lags) alone (never from the device): the lags a lane keeps, the lanes of a row, the rows
+// a workgroup has in flight (what 256 lanes and 64 KiB of LDS hold) and the row ranges: no more than kTcMaxRanges, all but the last
+// of one length.
 static int tc_shape(long long rows, int frames_cap, int frames, int lags, TcShape &s)
 {
-	int A;
-	s.frames = frames; s.lags = lags; s.cap = frames_cap;
-	if (lags <= 64) { A = 1; s.half = lags; s.W = 64; }
-	else
-	{
-		s.half = (lags + 1) / 2;
-		A = s.half <= 256 ? 2 : s.half <= 512 ? 4 : 8;
-		s.W = A == 2 ? (s.half + 63) / 64 * 64 : kTcBlock;
-	}
+	const int A = tc_lag_shape(frames_cap, frames, lags, 8, s);
 	s.S = std::max(1, std::min(kTcBlock / s.W, kTcLdsBytes / (32 * frames)));
 	const long long groups = (rows + s.S - 1) / s.S;
 	const long long want = std::min(groups, (long long)kTcMaxRanges);
@@ -657,13 +664,9 @@ int launch_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_
 	}
 	const size_t lds = std::max((size_t)32 * (size_t)frames * (size_t)s.S, (size_t)8 * kTcBlock);
 	const dim3 grid((unsigned)s.ranges), block(kTcBlock);
-#define NBCO_TC_STEP(A_) hipLaunchKernelGGL((tc_accumulate_kernel<A_>), grid, block, lds, c->stream, traj, rows, s, out)
-	// the template steps of the lags a lane keeps
-	if (A == 1) NBCO_TC_STEP(1);
-	else if (A == 2) NBCO_TC_STEP(2);
-	else if (A == 4) NBCO_TC_STEP(4);
-	else NBCO_TC_STEP(8);
-#undef NBCO_TC_STEP
+	with_step(std::integer_sequence<int, 1, 2, 4, 8>{}, A, [&](auto a) {
+		hipLaunchKernelGGL((tc_accumulate_kernel<decltype(a)::value>), grid, block, lds, c->stream, traj, rows, s, out);
+	});
 	NBCO_HIP(hipGetLastError());
 	if (s.ranges > 1)
 	{
@@ -673,75 +676,22 @@ int launch_time_corr(nbco_ctx *c, const float *traj, long long rows, int frames_
 	return NBCO_OK;
 }
 
-// ---- collective modes (modes_kernels.hpp) -------------------------------------------------------------
-int launch_modes_record(nbco_ctx *c, const float *buf, long long n, const nbco_sk_grid &g, double *series, int frames_cap, int frame, long long *n_used_host)
-{
-	const SkShape s = sk_shape(3, n, g, kMdMaxAcc, kMdExtra, 64);
-	const long long ranges = (n + s.range - 1) / s.range;
-	double *rec = series + 8 * (size_t)frame;   // record k of this frame lies at rec + k * stride
-	const long long stride = 8 * (long long)frames_cap;
-	double *out = rec;
-	long long ostride = stride;
-	if (ranges > 1)
-	{
-		NBCO_TRY(c->reserve(c->md_part, sizeof(double) * 8 * (size_t)s.K * (size_t)ranges));
-		out = c->md_part.as<double>();
-		ostride = 8;
-	}
-	const int per = 1 + kMdExtra + (s.hy + 1) + (s.hz + 1) + (s.nch > 1 ? s.nch : 0);
-	const size_t lds = std::max((size_t)16 * per * s.tile, (size_t)16 * kSkBlock);   // the tables of a tile; the copies' sums at the end
-	const dim3 grid((unsigned)((s.items + s.lanes - 1) / s.lanes), (unsigned)ranges), block(kSkBlock);
-#define NBCO_MD_STEP(A_) hipLaunchKernelGGL((modes_accumulate_kernel<A_>), grid, block, lds, c->stream, buf, n, s, out, ostride)
-	// the template steps of the run length L
-	if (s.L <= 1) NBCO_MD_STEP(1);
-	else if (s.L <= 2) NBCO_MD_STEP(2);
-	else if (s.L <= 3) NBCO_MD_STEP(3);
-	else NBCO_MD_STEP(4);
-#undef NBCO_MD_STEP
-	NBCO_HIP(hipGetLastError());
-	if (ranges > 1)
-	{
-		hipLaunchKernelGGL(sk_reduce_kernel<8>, dim3((unsigned)((8 * s.K + kSkReduceJ - 1) / kSkReduceJ)), dim3(kSkBlock), 0, c->stream, (const double *)out, ranges, 8 * s.K, rec, stride);
-		NBCO_HIP(hipGetLastError());
-	}
-	if (n_used_host)
-	{
-		// rho at k = 0 is the exact count of the particles that counted
-		const size_t k0 = (size_t)s.hy * (size_t)s.nz + (size_t)s.hz;
-		double cnt = 0;
-		NBCO_HIP(hipMemcpyAsync(&cnt, rec + k0 * (size_t)stride, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-		NBCO_HIP(hipStreamSynchronize(c->stream));
-		*n_used_host = (long long)cnt;
-	}
-	return NBCO_OK;
-}
-
-// The shape of a correlation call, from (frames, lags) alone: the lags a lane keeps (1 up to 64 lags, else pairs: 2 up to 512 lags, 4
-// beyond), the lanes of a k (a multiple of 64) and the k a workgroup serves (what 256 lanes and 64 KiB of LDS hold).
+// ---- the time correlations of the collective modes (modes_kernels.hpp) -------------------------------
+// The shape of a correlation call, from (frames, lags) alone: the lags a lane keeps (tc_lag_shape, at most 4), the lanes of a k and
+// the k a workgroup serves (what 256 lanes and 64 KiB of LDS hold).
 int launch_mode_corr(nbco_ctx *c, const double *series, const nbco_sk_grid &g, int frames_cap, int frames, int lags, nbco_mode_lag *out_dev)
 {
 	TcShape s;
-	int A;
-	s.frames = frames; s.lags = lags; s.cap = frames_cap;
-	if (lags <= 64) { A = 1; s.half = lags; s.W = 64; }
-	else
-	{
-		s.half = (lags + 1) / 2;
-		A = s.half <= 256 ? 2 : 4;
-		s.W = A == 2 ? (s.half + 63) / 64 * 64 : kTcBlock;
-	}
+	const int A = tc_lag_shape(frames_cap, frames, lags, 4, s);
 	s.S = std::max(1, std::min(kTcBlock / s.W, kTcLdsBytes / (64 * frames)));
 	const long long K = sk_count(g.h, 3);
 	s.range = s.S;
 	s.ranges = (K + s.S - 1) / s.S;
 	const size_t lds = (size_t)64 * (size_t)frames * (size_t)s.S;
 	const dim3 grid((unsigned)s.ranges), block(kTcBlock);
-#define NBCO_MC_STEP(A_) hipLaunchKernelGGL((mode_corr_kernel<A_>), grid, block, lds, c->stream, series, K, g, s, out_dev)
-	// the template steps of the lags a lane keeps
-	if (A == 1) NBCO_MC_STEP(1);
-	else if (A == 2) NBCO_MC_STEP(2);
-	else NBCO_MC_STEP(4);
-#undef NBCO_MC_STEP
+	with_step(std::integer_sequence<int, 1, 2, 4>{}, A, [&](auto a) {
+		hipLaunchKernelGGL((mode_corr_kernel<decltype(a)::value>), grid, block, lds, c->stream, series, K, g, s, out_dev);
+	});
 	NBCO_HIP(hipGetLastError());
 	return NBCO_OK;
 }

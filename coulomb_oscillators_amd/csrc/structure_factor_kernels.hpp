@@ -1,21 +1,26 @@
-// structure_factor_kernels.hpp -- rho_k = sum_j exp(i k . x_j) on the grid of nbco_structure_factor (include/nbco.h); a section of
-// k_reduce.hip, inside its anonymous namespace.  The rule (phases, powers, the complex product) is structure_factor.hpp.
+// structure_factor_kernels.hpp -- sums over the particles on the wave-vector grid of nbco_structure_factor (include/nbco.h): rho_k =
+// sum_j exp(i k . x_j) for that call (SkTerm, here) and the mode records of nbco_modes_record (MdTerm, modes_kernels.hpp); a section
+// of k_reduce.hip, inside its anonymous namespace.  The rule (phases, powers, the complex product) is structure_factor.hpp.
+//
+// ONE KERNEL, kgrid_accumulate_kernel<Term, A, DIM3, T>, serves every such sum.  A TERM says what a particle adds to a k: the type
+// of the sums of a k and their zero, the 16-byte LDS slots a particle needs beside its tables and how they are staged (which also
+// decides whether the particle counts), the addition per (particle, ix), the complex parts of a record, the template steps of A.
 //
 // An ITEM is one (chunk, iy, iz): the column (iy, iz) of the grid and a run of up to A consecutive ix, ix = chunk * L + m, m < L <= A.
-// A lane owns one item and keeps its A complex sums in registers (A is a template step: the loop over m is unrolled, the sums are
+// A lane owns one item and keeps its A sums in registers (A is a template step: the loop over m is unrolled, the sums are
 // never indexed at run time).  A workgroup of 256 lanes owns `lanes` <= 256 consecutive items and one range of particles; where
 // lanes <= 128 it runs S = 256 / lanes copies of them, copy q taking the particles q, q + S, .. of a tile, and adds the copies in the
-// order of q at the end, through LDS, one sum at a time.  The range is taken in
+// order of q at the end, through LDS, one complex part of one sum at a time.  The range is taken in
 // tiles: per tile the first lanes form the three phases of each particle once and the tables e_y^0..hy, e_z^0..hz and e_x^{cL} by
 // repeated multiplication into LDS; then every lane runs over the tile's particles: two LDS reads (the same particle for the whole
 // wave, neighbouring powers), one product for e_y^iy e_z^iz, one more with e_x^{cL} where the run is cut (a uniform branch), and A
-// times: add, multiply by e_x.  Nothing in that loop is transcendental.  A particle that does not count gets tables of zeros
-// and adds (0, 0).  The sums of a (range, item) go to part[range][K] -- or straight to rho where there is one
-// range -- and sk_reduce_kernel adds the ranges in a fixed order.  No atomics; the ranges are a function of n and the grid alone.
+// times: the term's addition, multiply by e_x.  Nothing in that loop is transcendental.  A particle that does not count gets tables
+// and slots of zeros and adds (0, 0).  The record of a (range, k) goes to part[range][k] -- or straight to out + k * ostride where
+// there is one range -- and sk_reduce_kernel adds the ranges in a fixed order.  No atomics; the ranges are a function of n and the
+// grid alone.
 
 constexpr int kSkBlock = 256;
 constexpr int kSkLdsBytes = 48 * 1024;   // the tables of a tile: three workgroups per CU
-constexpr int kSkMaxAcc = 17;            // the largest run of ix a lane keeps (68 VGPRs of sums)
 
 // what the host works out for a call and the kernels read
 struct SkShape
@@ -26,14 +31,14 @@ struct SkShape
 	int items;             // nch * ny * nz
 	int lanes, copies;     // items per workgroup, copies of them per workgroup: lanes * copies <= 256
 	int tile;              // particles per tile
+	int per;               // 16-byte LDS slots per particle: e_x, the term's, the tables
 	long long range;       // particles per range (a multiple of 64)
 	long long K;
 	double wx, wy, wz;     // kstep / 2 pi
 };
 
 // The power tables of a tile of cnt particles from their base phases (ex[j], ty[j][1], tz[j][1]; the entries 0 are set): one lane per
-// (particle, axis) chain fills ty[j][2..hy], tz[j][2..hz] and, where the ix run is cut, tc[j][1..nch-1] = e_x^{cL}.  Shared with
-// modes_accumulate_kernel (modes_kernels.hpp).
+// (particle, axis) chain fills ty[j][2..hy], tz[j][2..hz] and, where the ix run is cut, tc[j][1..nch-1] = e_x^{cL}.
 template <bool DIM3>
 __device__ __forceinline__ void sk_power_tables(const SkShape &s, int cnt, const SkC *ex, SkC *ty, SkC *tz, SkC *tc)
 {
@@ -73,16 +78,36 @@ __device__ __forceinline__ void sk_power_tables(const SkShape &s, int cnt, const
 	}
 }
 
-template <int A, bool DIM3, typename T>
-__global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__restrict__ p, long long n, SkShape s, double *__restrict__ out)
+// The term of nbco_structure_factor: a counted particle adds its w, a record is one complex number.  A term holds what a k-grid sum
+// is apart from the tile scheme; kgrid_accumulate_kernel and the host (sk_shape, kgrid_run in k_reduce.hip) read everything from it.
+struct SkTerm
+{
+	using Acc = SkC;                                                  // the sums of one k
+	using Steps = std::integer_sequence<int, 1, 2, 3, 5, 9, 13, 17>;   // the template steps A of a run of ix (the last: 68 VGPRs of sums)
+	static constexpr int kExtra = 0;                                  // 16-byte LDS slots of a particle beside its tables
+	static constexpr int kParts = 1;                                  // complex numbers of a record
+	static __device__ __forceinline__ void zero(Acc &a) { a.re = a.im = 0.0; }
+	// Stage particle g of the n rows at p, whose phases are finite iff ok: fill its kExtra slots (zeros unless it counts) and say
+	// whether it counts.
+	template <typename T>
+	static __device__ __forceinline__ bool stage(const T *, long long, size_t, bool ok, SkC *) { return ok; }
+	// one (particle, ix): its term w and its slots
+	static __device__ __forceinline__ void add(Acc &a, SkC w, const SkC *) { a.re += w.re; a.im += w.im; }
+	// part c < kParts of the sums (c is a constant once the loop over it is unrolled)
+	static __device__ __forceinline__ SkC &part(Acc &a, int) { return a; }
+};
+
+template <class Term, int A, bool DIM3, typename T>
+__global__ __launch_bounds__(kSkBlock) void kgrid_accumulate_kernel(const T *__restrict__ p, long long n, SkShape s, double *__restrict__ out, long long ostride)
 {
 	extern __shared__ double sk_lds[];
-	constexpr int D = DIM3 ? 3 : 2;
+	constexpr int D = DIM3 ? 3 : 2, X = Term::kExtra, P = Term::kParts;
 	const int tid = (int)threadIdx.x;
 	const int tile = s.tile, sy = s.hy + 1, sz = s.hz + 1, nch = s.nch;
-	// LDS: ex[tile], ty[tile][hy + 1], tz[tile][hz + 1] (3-D), tc[tile][nch] (nch > 1)
+	// LDS: ex[tile], xs[tile][X], ty[tile][hy + 1], tz[tile][hz + 1] (3-D), tc[tile][nch] (nch > 1)
 	SkC *ex = reinterpret_cast<SkC *>(sk_lds);
-	SkC *ty = ex + tile;
+	SkC *xs = ex + tile;
+	SkC *ty = xs + (size_t)tile * X;
 	SkC *tz = ty + (size_t)tile * sy;
 	SkC *tc = DIM3 ? tz + (size_t)tile * sz : tz;
 
@@ -95,9 +120,9 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 	const int ay = iy < 0 ? -iy : iy, az = iz < 0 ? -iz : iz;
 	const double cy = iy < 0 ? -1.0 : 1.0, cz = iz < 0 ? -1.0 : 1.0;
 
-	SkC acc[A];
+	typename Term::Acc acc[A];
 #pragma unroll
-	for (int m = 0; m < A; ++m) acc[m].re = acc[m].im = 0.0;
+	for (int m = 0; m < A; ++m) Term::zero(acc[m]);
 
 	const long long lo = (long long)blockIdx.y * s.range;
 	const long long hi = lo + s.range < n ? lo + s.range : n;
@@ -105,15 +130,15 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 	{
 		const int cnt = hi - base < (long long)tile ? (int)(hi - base) : tile;   // particles of this tile
 		__syncthreads();   // the previous tile has been read
-		// the base phases: one lane per particle
+		// the base phases and the term's slots: one lane per particle
 		for (int j = tid; j < cnt; j += kSkBlock)
 		{
-			const long long g = base + j;
+			const size_t g = (size_t)(base + j);
 			SkC zero, first;   // z^0 of a particle: (1, 0) if it counts
 			zero.re = zero.im = 0.0;
-			const double tx = (double)p[(size_t)g * D] * s.wx, t1 = (double)p[(size_t)g * D + 1] * s.wy;
-			const double t2 = DIM3 ? (double)p[(size_t)g * D + 2] * s.wz : 0.0;
-			const bool ok = isfinite(tx) && isfinite(t1) && isfinite(t2);
+			const double tx = (double)p[g * D] * s.wx, t1 = (double)p[g * D + 1] * s.wy;
+			const double t2 = DIM3 ? (double)p[g * D + 2] * s.wz : 0.0;
+			const bool ok = Term::stage(p, n, g, isfinite(tx) && isfinite(t1) && isfinite(t2), xs + (size_t)j * X);
 			first.re = ok ? 1.0 : 0.0; first.im = 0.0;
 			SkC e0 = zero, e1 = zero, e2 = zero;
 			if (ok)
@@ -149,11 +174,13 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 				}
 				if (nch > 1) w = sk_mul(w, tc[(size_t)j * nch + chunk]);
 				const SkC e = ex[j];
+				SkC x[X > 0 ? X : 1];
+#pragma unroll
+				for (int c = 0; c < X; ++c) x[c] = xs[(size_t)j * X + c];
 #pragma unroll
 				for (int m = 0; m < A; ++m)
 				{
-					acc[m].re += w.re;
-					acc[m].im += w.im;
+					Term::add(acc[m], w, x);
 					if (m + 1 < A) w = sk_mul(w, e);
 				}
 			}
@@ -161,26 +188,31 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 	}
 	if (S > 1)
 	{
-		// the copies of an item, added in the order of the copies: every lane lends its sum m, copy 0 collects
+		// the copies of an item, added in the order of the copies: every lane lends one complex sum at a time, copy 0 collects
 		SkC *red = reinterpret_cast<SkC *>(sk_lds);
 #pragma unroll
 		for (int m = 0; m < A; ++m)
 		{
-			__syncthreads();   // the last tile, or sum m - 1, has been read
-			red[tid] = acc[m];
-			__syncthreads();
-			if (live && copy == 0)
-				for (int q = 1; q < S; ++q)
-				{
-					const SkC v = red[q * s.lanes + lane];
-					acc[m].re += v.re;
-					acc[m].im += v.im;
-				}
+#pragma unroll
+			for (int c = 0; c < P; ++c)
+			{
+				SkC &v = Term::part(acc[m], c);
+				__syncthreads();   // the last tile, or the sum before this one, has been read
+				red[tid] = v;
+				__syncthreads();
+				if (live && copy == 0)
+					for (int q = 1; q < S; ++q)
+					{
+						const SkC u = red[q * s.lanes + lane];
+						v.re += u.re;
+						v.im += u.im;
+					}
+			}
 		}
 	}
 	if (live && copy == 0)
 	{
-		double *o = out + (size_t)blockIdx.y * 2 * (size_t)s.K;
+		double *o = out + (size_t)blockIdx.y * 2 * P * (size_t)s.K;   // (ostride != 2 P: one range, blockIdx.y == 0)
 #pragma unroll
 		for (int m = 0; m < A; ++m)
 		{
@@ -188,8 +220,14 @@ __global__ __launch_bounds__(kSkBlock) void sk_accumulate_kernel(const T *__rest
 			if (m < s.L && ix <= s.hx)
 			{
 				const size_t k = ((size_t)ix * s.ny + (size_t)(iy + s.hy)) * s.nz + (size_t)(iz + s.hz);
-				o[2 * k] = acc[m].re;
-				o[2 * k + 1] = acc[m].im;
+				double *r = o + k * (size_t)ostride;   // (doubles: the caller's buffer is aligned as doubles are, no more is asked)
+#pragma unroll
+				for (int c = 0; c < P; ++c)
+				{
+					const SkC v = Term::part(acc[m], c);
+					r[2 * c] = v.re;
+					r[2 * c + 1] = v.im;
+				}
 			}
 		}
 	}

@@ -70,6 +70,29 @@ __device__ __forceinline__ int tc_lag(const TcShape &s, int lane, int m)
 	return b < s.lags - s.half ? s.lags - 1 - b : -1;
 }
 
+// The slots of a lane (mode_corr_kernel uses them too): tau[m] its lag and end[m] the origins of that lag, frames - tau (both 0: none,
+// as for a lane that is not live).  Returns the origins any lane of the wave has a lag for, so that the loop over them is uniform.
+template <int A>
+__device__ __forceinline__ int tc_lag_slots(const TcShape &s, bool live, int lane, int (&tau)[A], int (&end)[A])
+{
+	int tend = 0;
+#pragma unroll
+	for (int m = 0; m < A; ++m)
+	{
+		const int l = live ? tc_lag<A>(s, lane, m) : -1;
+		tau[m] = l < 0 ? 0 : l;
+		end[m] = l < 0 ? 0 : s.frames - l;
+		tend = end[m] > tend ? end[m] : tend;
+	}
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1)
+	{
+		const int o = __shfl_xor(tend, d);
+		tend = o > tend ? o : tend;
+	}
+	return __builtin_amdgcn_readfirstlane(tend);
+}
+
 template <int A>
 __global__ __launch_bounds__(kTcBlock) void tc_accumulate_kernel(const float *__restrict__ traj, long long rows, TcShape s, nbco_corr_lag *__restrict__ out)
 {
@@ -81,28 +104,16 @@ __global__ __launch_bounds__(kTcBlock) void tc_accumulate_kernel(const float *__
 	float4 *px = tc_lds + (size_t)(live ? copy : 0) * 2 * (size_t)frames;   // this copy's row: positions, then velocities
 	float4 *pv = px + frames;
 
-	int tau[A], end[A];   // end: the origins of this lag, frames - tau (0: none)
+	int tau[A], end[A];
 	TcSum acc[A];
 	unsigned long long cnt[A];
-	int tend = 0;         // the origins this lane has any lag for
+	const int tend = tc_lag_slots<A>(s, live, lane, tau, end);
 #pragma unroll
 	for (int m = 0; m < A; ++m)
 	{
-		const int l = live ? tc_lag<A>(s, lane, m) : -1;
-		tau[m] = l < 0 ? 0 : l;
-		end[m] = l < 0 ? 0 : frames - l;
-		tend = end[m] > tend ? end[m] : tend;
 		tc_zero(acc[m]);
 		cnt[m] = 0;
 	}
-	// (the bound of the wave, so that the loop's branch is uniform)
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1)
-	{
-		const int o = __shfl_xor(tend, d);
-		tend = o > tend ? o : tend;
-	}
-	tend = __builtin_amdgcn_readfirstlane(tend);
 
 	const long long lo = (long long)blockIdx.x * s.range;
 	const long long hi = lo + s.range < rows ? lo + s.range : rows;
