@@ -9,10 +9,11 @@ allocations make that situation deterministic, the device-side checks turn any s
 Part 3 of the script puts the walks of tests/test_gpu_context_reuse.py that aim at stale launch estimates and shared scratch (its
 parts A, first alternation, and D) through the same build: a stale index then shows up as a count in one of the eight sites.
 
-test_checked_build_runs_the_snapshot_sequences puts the drivers of tests/test_gpu_snapshots.py -- every diagnostic on one long-lived
-context, at an n smaller than one the context has seen -- through the same build: the walks of the probes, the pair statistics and
-the potential pass report to the site NBCO_CHK_WALK, the slice and aperture kernels to NBCO_CHK_GROUP, and under NBCO_POISON the
-block of device scalars (`small`) starts as 0x7f bytes as well.
+test_checked_build_runs_the_snapshot_sequences puts the drivers of tests/test_gpu_snapshots.py and tests/test_gpu_snapshot_series.py
+-- every diagnostic on one long-lived context, at an n smaller than one the context has seen -- through the same build: the walks of
+the probes, the pair statistics, the bond order and the potential pass report to the site NBCO_CHK_WALK, the slice and aperture
+kernels to NBCO_CHK_GROUP, and under NBCO_POISON the block of device scalars (`small`) and the partial-sum buffers of the wave-vector
+sums and the time correlations start as 0x7f bytes as well.
 
 Each of the two tests runs once, in a subprocess of its own (the checked library is selected with NBCO_LIB before the package loads)."""
 import json
@@ -154,7 +155,7 @@ SNAPSHOT_SCRIPT = textwrap.dedent('''
     out["violations_big"] = big.violations()
     big.close(); del d, t
 
-    # 2. the drivers of tests/test_gpu_snapshots.py, with that module's own assertions
+    # 2. the drivers of tests/test_gpu_snapshots.py and tests/test_gpu_snapshot_series.py, with those modules' own assertions
     import test_gpu_snapshots as T
     T.drive_a(o)
     out["violations_a"] = Engine().violations()
@@ -162,6 +163,10 @@ SNAPSHOT_SCRIPT = textwrap.dedent('''
     T.run_size_walk_2d()
     out["violations_b"] = Engine().violations()
     T.drive_c()
+    out["violations_c"] = Engine().violations()
+    import test_gpu_snapshot_series as S
+    S.drive_series_a(o)
+    S.run_shape_walk()
 
     # 3. the counts of every site, all contexts of the process together
     out["violations"] = Engine().violations()
@@ -170,8 +175,9 @@ SNAPSHOT_SCRIPT = textwrap.dedent('''
 
 
 def test_checked_build_runs_the_snapshot_sequences():
-    """the snapshot sequences and size walks of tests/test_gpu_snapshots.py on the checked build with poisoned allocations, behind a
-    context that left a deeper tree's tables in the allocator's pool: every assertion of that module holds and no site has counted"""
+    """the snapshot sequences and size walks of tests/test_gpu_snapshots.py and the drivers of tests/test_gpu_snapshot_series.py on the
+    checked build with poisoned allocations, behind a context that left a deeper tree's tables in the allocator's pool: every
+    assertion of those modules holds and no site has counted"""
     if not os.path.exists(CHECKED):
         pytest.fail("libnbco_hip_checked.so is not built (make -C coulomb_oscillators_amd/csrc)")
     env = dict(os.environ, NBCO_LIB=CHECKED, NBCO_POISON="1")

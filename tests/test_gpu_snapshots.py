@@ -1,8 +1,10 @@
 """Every diagnostic on ONE long-lived context, as nbco3 and nbco drive them at a snapshot (host/nbco3.cpp: nbco_aperture_apply, so that
 n shrinks, the tree is dropped and the order map compacted; nbco_energy_tree; nbco_beam_moments; nbco_slice_moments; nbco_probe_tree;
-nbco_pair_hist_tree; nbco_integrate_steps again), where the modules of these features give each its own context at one particle
-count.  Three of the calls share one private child context, which is created once and then sees another n at every snapshot; all
-scratch lives in buffers that only grow, so after a larger call the tail of every table holds the larger call's data.
+nbco_pair_hist_tree; nbco_bond_order_tree; nbco_bond_order; nbco_structure_factor; nbco_integrate_steps again), where the modules of
+these features give each its own context at one particle count.  Four of the calls share one private child context, which is created
+once and then sees another n at every snapshot; all scratch lives in buffers that only grow, so after a larger call the tail of every
+table holds the larger call's data.  The calls that keep a caller's buffers across snapshots (trajectories, mode series and their
+correlations) are in tests/test_gpu_snapshot_series.py, whose docstring says where each scratch buffer meets a smaller user.
 
 Four bars, used throughout.  No tolerance is introduced here: each one is imported from, or cites, the module that derived it.
 
@@ -13,7 +15,10 @@ Four bars, used throughout.  No tolerance is introduced here: each one is import
     1e-6 on the kinetic and elastic terms of test_energy_kd_against_fp64_direct_energy, the 1e-12 of
     test_probe_is_the_exact_sum_at_every_launch_shape, the 1e-10 of the restatements on the device tree
     (test_psi_against_the_restatement_on_the_device_tree, test_probe_kd_against_the_restatement_on_the_device_tree), and for 2-D
-    test_energy_2d_against_exact_sum, test_energy_fmm_2d_matches_restatement, test_gpu_probe2d._check_exact / _check_fmm.
+    test_energy_2d_against_exact_sum, test_energy_fmm_2d_matches_restatement, test_gpu_probe2d._check_exact / _check_fmm.  The bond
+    order through test_gpu_bond_order.check (nb and the summary's integers exactly, the squares within bond_numpy.TOL2, whose premise
+    nb <= 256 is asserted of every model), the structure factor as test_gpu_structure_factor.check (sk_numpy.bound, n_used = n and
+    rho at k = 0 exactly n).
 (F) fresh-context equality.  A context created for that call alone returns the same bytes for the same input and options; if it
     refuses, the long-lived one refuses with the same status.  energy_tree is also held to test_gpu_energy3d.fresh_energy_kd.
 (R) the run does not notice.  A run with the diagnostic calls equals the run without them, bit for bit: the state, every field of
@@ -34,21 +39,25 @@ import pytest
 
 import aperture_numpy as AP
 import beam_numpy as BN
+import bond_numpy as BO
 import energy2d_numpy as E2
 import energy3d_numpy as e3
 import fmm2d_numpy as F2
 import pairstat_numpy as PN
 import probe2d_numpy as PR2
 import probe3d_numpy as p3
+import sk_numpy as SK
 import slice_numpy as SN
 import test_gpu_aperture as APT
 import test_gpu_beam_diag as BD
+import test_gpu_bond_order as BOT
 import test_gpu_context_reuse as CR
 import test_gpu_energy3d as EN3
 import test_gpu_pair_hist as PH
 import test_gpu_probe2d as PB2
 import test_gpu_probe3d as PB3
 import test_gpu_slice_moments as SL
+import test_gpu_structure_factor as SFT
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +157,47 @@ def aperture_call(e, dim, d, n, half):
     return dict(cmp=(kept, copy.cpu().numpy()[:3 * dim * kept], lost.cpu().numpy(), rows.cpu().numpy()))
 
 
+def bond_call(e, form, d, n, rmax):
+    """one bond-order call through test_gpu_bond_order.run, into poisoned nb and q"""
+    nb, q, s = BOT.run(e, form, d, n, rmax)
+    return dict(cmp=(nb, q, bytes(s)), raw=(nb, q, s))
+
+
+def sk_call(fn, d, n, dim, h, kstep):
+    """one structure-factor call into a rho pre-filled with test_gpu_structure_factor.POISON, all of which must be overwritten"""
+    import torch
+    rho = torch.full((SK.count(h[:dim]),), complex(SFT.POISON, SFT.POISON), dtype=torch.complex128, device="cuda")
+    _, used = fn(d, n, h, kstep, rho=rho)
+    got = rho.cpu().numpy()
+    assert (got.real != SFT.POISON).all() and (got.imag != SFT.POISON).all()
+    return dict(cmp=(got, used))
+
+
+def check_bonds(pos, key, rmax, got, what):
+    """bar (M) of the bond order: test_gpu_bond_order.check against bond_numpy.bond_order, whose TOL2 presumes nb <= 256"""
+    m = model("bonds", key + repr(float(rmax)), lambda: BO.bond_order(pos, rmax))
+    assert m["nb_max"] <= 256, (what, m["nb_max"])
+    BOT.check(got["raw"], m, what)
+
+
+def check_sk(pos, key, h, kstep, got, what, only=None):
+    """bar (M) of the structure factor, as test_gpu_structure_factor.check: within sk_numpy.bound of the long double model (over the
+    flat indices `only` where given, and over every 7th wave vector, the zero vector and the last one where the grid times n is above
+    SK_MODEL_WORK), every particle counted, rho at k = 0 exactly n"""
+    n, dim = pos.shape
+    h, kstep = tuple(h[:dim]), tuple(kstep[:dim])
+    rho, used = got["cmp"]
+    K = SK.count(h)
+    if only is None and K * n > SK_MODEL_WORK:     # (F) compares every byte; the model's cost is kept to a few seconds
+        only = np.unique(np.concatenate([np.arange(0, K, 7), [SK.index(h, 0, 0, 0), K - 1]]))
+    re, im, want_used = model("sk", key + repr((h, kstep, only is not None)), lambda: SK.structure_factor(pos, h, kstep, only=only))
+    err, lim = SK.error(rho if only is None else rho[only], re, im), SK.bound(n, h)
+    print("%s: h %s error %.3g, bound %.3g (fraction %.3g)" % (what, h, err, lim, err / lim))
+    assert used == want_used == n, (what, used, want_used)
+    assert err <= lim, (what, err, lim)
+    assert rho[SK.index(h, 0, 0, 0)] == complex(n, 0.0), what
+
+
 def check_aperture(dim, host, half, got, what):
     """bar (M) of the aperture: bytes (test_gpu_aperture.check_case)"""
     want_state, want_lost, want_rows = AP.apply(host, AP.ELLIPSOID, half)
@@ -178,6 +228,12 @@ PAIR_BINS, PAIR_RMAX = 64, PH.RMAX[1]
 AX_Z = (Z, 64, -3 * RMS[2], 3 * RMS[2])
 AX_SLICE = (Z, 16, -3 * RMS[2], 3 * RMS[2])      # +-3 rms of the INITIAL ball: late snapshots have empty outer slices
 EPS2 = PB3.EPS2
+# the bond radius of the 3-D states: test_snapshots_host.py asserts from the model that it keeps nb <= 256, the premise of
+# bond_numpy.TOL2, and gives at least half of the particles a bond at every snapshot (43 at the most, 90 % at the least)
+BOND_RMAX = 0.0008
+SK_KSTEP = (900.0, 900.0, 900.0)       # of the state tests of test_gpu_structure_factor / test_gpu_modes on the reference ball
+SK_MODEL_WORK = 1 << 22                # wave vectors x particles up to which the long double model is evaluated on the whole grid
+SK_H = (4, 4, 4)                       # the grid of the snapshot sequence; the size walk takes its grids from GRIDS_B
 
 
 def child_opts(opts):
@@ -199,6 +255,7 @@ def inputs3d(o, d, n, prm, par, probes_host):
     x.t_host = probes_host
     x.t, x.m = dev(probes_host), len(probes_host)
     x.xvx = axes_xvx(o)
+    x.sk_h = SK_H
     return x
 
 
@@ -224,8 +281,16 @@ CALLS3D = {       # in the order of a snapshot of nbco3
     "probe": probe3("probe"),
     "pair_hist_tree": pair3("tree"),
     "pair_hist": pair3("exact"),
+    "bond_order_tree": lambda e, x: bond_call(e, "tree", x.d, x.n, BOND_RMAX),
+    "bond_order": lambda e, x: bond_call(e, "exact", x.d, x.n, BOND_RMAX),
+    "structure_factor": lambda e, x: sk_call(e.structure_factor, x.d, x.n, 3, x.sk_h, SK_KSTEP),
 }
-WALK3D = dict(CALLS3D)
+# the size walk: the 2-D form on a cloud of its own (x.cloud2, x.sk_h2) right before the 3-D form, so that the two alternate on one sk_part
+WALK3D = {}
+for _name, _fn in CALLS3D.items():
+    if _name == "structure_factor":
+        WALK3D["structure_factor_2d"] = lambda e, x: sk_call(e.structure_factor_2d, x.d2, len(x.cloud2), 2, x.sk_h2, SFT.K3)
+    WALK3D[_name] = _fn
 WALK3D["aperture_count"] = lambda e, x: dict(cmp=(e.aperture_count(x.d, x.n, AP.ELLIPSOID, APT.HALF),))
 WALK3D["aperture"] = lambda e, x: aperture_call(e, 3, x.d, x.n, APT.HALF)
 FRESH_ONLY = ("probe_tree",)           # (F) alone: no reference evaluates the field off a tree it cannot see
@@ -270,6 +335,10 @@ MODELS3D = {
     "probe": check_probe3,
     "pair_hist_tree": lambda x, got, what: check_pairs(x.host[0], x.key, got, what),
     "pair_hist": lambda x, got, what: check_pairs(x.host[0], x.key, got, what),
+    "bond_order_tree": lambda x, got, what: check_bonds(x.host[0], x.key, BOND_RMAX, got, what),
+    "bond_order": lambda x, got, what: check_bonds(x.host[0], x.key, BOND_RMAX, got, what),
+    "structure_factor": lambda x, got, what: check_sk(x.host[0], x.key, x.sk_h, SK_KSTEP, got, what),
+    "structure_factor_2d": lambda x, got, what: check_sk(x.cloud2, digest(x.cloud2), x.sk_h2, SFT.K3, got, what),
     "aperture_count": lambda x, got, what: None,      # (held to the model through "aperture": its n - n_kept)
     "aperture": lambda x, got, what: check_aperture(3, x.host, APT.HALF, got, what),
 }
@@ -303,6 +372,9 @@ def hold(calls, models, x, got, fresh, what, with_model=True):
         assert got["aperture_count"]["cmp"][0] == x.n - got["aperture"]["cmp"][0], what
     if "pair_hist_tree" in got:
         PH.same(got["pair_hist_tree"]["cmp"], got["pair_hist"]["cmp"], what + ": tree form against exact form")
+    if "bond_order_tree" in got:
+        a, b = got["bond_order_tree"]["cmp"][0], got["bond_order"]["cmp"][0]
+        assert a is not REFUSED and b is not REFUSED and np.array_equal(a, b), what + ": nb of the tree form against the exact form"
 
 
 # ---- (a) the 3-D snapshot sequence -----------------------------------------------------------------------------------------------------
@@ -328,6 +400,29 @@ def preconditions_3d(o):
     assert table[1][0] == 0, table
     assert table[3][1] > 4096 > table[4][1], table
     return table
+
+
+def bond_table(pos, insides, rmax):
+    """(n, nb_max, particles with a bond) of the positions left behind each of the modelled apertures, from bond_numpy.bonds"""
+    keep = np.ones(len(pos), dtype=bool)
+    out = []
+    for inside in insides:
+        keep &= inside
+        nb = np.bincount(BO.bonds(pos[keep], rmax)[0], minlength=int(keep.sum()))
+        out.append((int(keep.sum()), int(nb.max()), int((nb > 0).sum())))
+    return out
+
+
+def assert_bond_table(table):
+    """nb_max <= 256, the premise of bond_numpy.TOL2, and at least half of the particles with a bond, at every snapshot"""
+    assert all(nb_max <= 256 and 2 * bonded >= n for n, nb_max, bonded in table), table
+    return table
+
+
+def bond_preconditions_3d(o):
+    """BOND_RMAX on the unmoved state behind each modelled aperture (as loss_model_3d)"""
+    pos = CR.state(o, N0)[0]
+    return assert_bond_table(bond_table(pos, [AP.inside(pos, AP.ELLIPSOID, [k * r for r in RMS]) for k in KS], BOND_RMAX))
 
 
 def after_force_3d(o, e, x, state_in, what):
@@ -366,13 +461,15 @@ def after_force_3d(o, e, x, state_in, what):
     return info.rebuilt
 
 
-def run_snapshots_3d(o, diagnostics=True):
+def run_snapshots_3d(o, diagnostics=True, extra=None):
     """Driver (a).  compute_force, then five snapshots, three leapfrog steps apart (the rebuild schedule is mid-cycle at every snapshot,
     and a lossy call restarts it), and three steps behind the last.  A snapshot: the aperture (M), then on the n' rows left every call
     of CALLS3D to (F) and (M); at snapshots 2 and 4 compute_force and after_force_3d.  Returns what bar (R) compares.
     Loss counts (lost, kept) per call, from the model on the unmoved state (tests/test_snapshots_host.py prints them):
     (231, 7962), (0, 7962), (577, 7385), (1307, 6078), (2173, 3905).  On the device the second call loses the two particles that three
-    steps have moved across the surface ("few"), so the compute_force of snapshot 2 rebuilds as that of snapshot 4 does."""
+    steps have moved across the surface ("few"), so the compute_force of snapshot 2 rebuilds as that of snapshot 4 does.
+    `extra` rides the same loop (tests/test_gpu_snapshot_series.py): extra.snapshot(e, snap, view, n, order, what) behind each snapshot's
+    aperture and diagnostics, `order` being the order map compacted as the aperture compacts it; extra.finish(e) behind the last."""
     import torch
     from coulomb_oscillators_amd import AP_ELLIPSOID, EVAL_FMM_KDTREE, INTEG_LEAPFROG, Engine
     from coulomb_oscillators_amd.engine import KdInfo
@@ -417,12 +514,16 @@ def run_snapshots_3d(o, diagnostics=True):
                 hold(CALLS3D, MODELS3D, x, got, fresh_calls(OPTS_A, CALLS3D, x), what)
                 want, wphi = EN3.fresh_energy_kd(view, n, prm, **child_opts(OPTS_A))
                 assert np.array_equal(got["energy_tree"]["out"], want) and np.array_equal(got["energy_tree"]["psi"], wphi.cpu().numpy()), what + ": energy_tree"
+            if extra is not None:
+                extra.snapshot(e, snap, view, n, np.delete(log["order"][-1], log["rows"][-1]), what)
             if snap in FORCE_AT:
                 state_in = view.clone()
                 e.compute_force(EVAL_FMM_KDTREE, view, n, prm)
                 if diagnostics:
                     x = inputs3d(o, view, n, prm, par, probes)
                     log["rebuilt_at_force"].append(after_force_3d(o, e, x, state_in, what + ": behind compute_force"))
+        if extra is not None:
+            extra.finish(e)
         e.integrate_steps(INTEG_LEAPFROG, EVAL_FMM_KDTREE, d, n, prm, DT, STEPS)
         look()
         log["state"] = d.cpu().numpy()[:9 * n].copy()
@@ -458,16 +559,76 @@ def drive_a(o):
 
 # ---- (b) the size walk of the diagnostics ----------------------------------------------------------------------------------------------
 SIZES_B = [8193, 300, 20000, 1, 65, 4097, 20000, 2]
+GRIDS_B = [(8, 8, 8), (2, 2, 2), (2, 2, 2), (64, 0, 0), (0, 0, 64), (17, 1, 1), (1, 8, 8), (0, 0, 0)]      # structure_factor at step i
+GRIDS_B2 = [(8, 8), (2, 2), (2, 64), (64, 0), (0, 64), (17, 55), (4, 4), (0, 0)]                           # structure_factor_2d at step i
+CLOUD2_MAX = 4097                      # the 2-D form runs on sk_numpy.cloud(min(n, 4097), .., dim=2)
+LARGEST_GRID = (1025, (64, 64, 64))    # the step appended for structure_factor alone: the largest grid, with several ranges
 MODEL_MAX = 8193
 OPTS_B = dict(fmm_order=4)
+
+
+def sk_shape(dim, n, h, max_acc=17, extra=0, parts=1):
+    """The launch shape of a wave-vector sum, FOLLOWING sk_shape and kgrid_run in csrc/k_reduce.hip (the defaults are SkTerm's: runs
+    of at most 17 indices ix, no slot beside the tables, one complex number per record).  A precondition only: it says which paths
+    the walk takes, and no result is compared with it."""
+    hx, hy, hz = h[0], h[1], (h[2] if dim == 3 else 0)
+    nch = (hx + max_acc) // max_acc
+    L = (hx + nch) // nch
+    ny, nz = 2 * hy + 1, 2 * hz + 1
+    items, K = nch * ny * nz, (hx + 1) * ny * nz
+    per = 1 + extra + (hy + 1) + (hz + 1 if dim == 3 else 0) + (nch if nch > 1 else 0)
+    tile = min(256, 48 * 1024 // (16 * per))
+    kt0 = (items + 255) // 256
+    kt, best = kt0, 0.0
+    for t in range(kt0, 4 * kt0 + 1):
+        lanes = (items + t - 1) // t
+        busy = float(items) * (256 // lanes) / (float(t) * 256)
+        if busy > best:
+            best, kt = busy, t
+        if busy >= 0.85:
+            break
+    lanes = (items + kt - 1) // kt
+    copies = 256 // lanes if lanes <= 128 else 1
+    r0 = min((n + 511) // 512, max(1, 2048 // kt))
+    r0 = max(1, min(r0, (256 << 20) // (16 * parts * K)))
+    rng = ((n + r0 - 1) // r0 + 63) // 64 * 64
+    return dict(dim=dim, n=n, h=tuple(h), nch=nch, L=L, items=items, K=K, lanes=lanes, copies=copies, tile=tile, ranges=(n + rng - 1) // rng)
+
+
+def sk_walk_shapes():
+    """the shapes of the calls that share the live context's sk_part in run_size_walk_3d, in the order of the calls"""
+    out = []
+    for n, h3, h2 in zip(SIZES_B, GRIDS_B, GRIDS_B2):
+        out += [sk_shape(2, min(n, CLOUD2_MAX), h2), sk_shape(3, n, h3)]
+    return out + [sk_shape(3, *LARGEST_GRID)]
+
+
+def preconditions_walk():
+    """what the walk is there for, asserted of the restated shapes: a call with one range directly behind one with at least 16; more
+    ranges on a smaller K than an earlier call (another layout inside the bytes that call wrote); several chunks of ix; workgroups
+    with several copies of their items and with one; a tile below 256"""
+    assert len(GRIDS_B) == len(GRIDS_B2) == len(SIZES_B)
+    t = sk_walk_shapes()
+    assert any(a["ranges"] >= 16 and b["ranges"] == 1 for a, b in zip(t, t[1:])), t
+    assert any(b["ranges"] > a["ranges"] > 1 and b["K"] < a["K"] for i, b in enumerate(t) for a in t[:i]), t
+    assert any(s["nch"] > 1 for s in t) and any(s["nch"] > 1 and s["ranges"] > 1 for s in t), t
+    assert any(s["copies"] > 1 for s in t) and any(s["copies"] == 1 for s in t), t
+    assert any(s["tile"] < 256 for s in t), t
+    big = t[-1]
+    assert big["ranges"] > 1 and big["K"] == SK.count(LARGEST_GRID[1]) == 65 * 129 * 129, big
+    return t
 
 
 def run_size_walk_3d(o):
     """Driver (b), 3-D.  One context over SIZES_B, at every step every call of WALK3D (the aperture on a copy, at 2.5 rms): (F), and (M)
     where n <= 8193.  The private child context, the slice tables, the aperture's scan levels and the probes' sort scratch each see a
-    smaller n behind a larger one."""
+    smaller n behind a larger one.  The wave-vector grid changes with the step as n does (GRIDS_B for structure_factor, GRIDS_B2 for
+    structure_factor_2d on a cloud of min(n, 4097) points right before it), so sk_part is cut anew at every call: preconditions_walk
+    says into what.  A last step runs structure_factor alone on the largest grid at n = 1025, three ranges of 1.08 million wave
+    vectors, held to (F) and, on every 37th wave vector, the zero vector and the last one, to (M)."""
     import torch
     from coulomb_oscillators_amd import Engine
+    preconditions_walk()
     live = Engine(**OPTS_B)
     fresh = {}
     try:
@@ -475,12 +636,29 @@ def run_size_walk_3d(o):
             buf, par = CR.state(o, n), o.params(n)
             d, prm = dev(buf.reshape(-1).copy()), dev(par)
             x = inputs3d(o, d, n, prm, par, np.ascontiguousarray(buf[0][:300] * np.float32(1.2)))
+            x.sk_h, x.sk_h2 = GRIDS_B[step], GRIDS_B2[step]
+            x.cloud2 = SK.cloud(min(n, CLOUD2_MAX), 5000 + step, dim=2)
+            x.d2 = dev(x.cloud2)
             what = "size walk step %d: n %d" % (step, n)
             got = run_calls(live, WALK3D, x)
             assert np.array_equal(d.cpu().numpy(), buf.reshape(-1)), what + ": a call wrote the state"
-            if n not in fresh:
-                fresh[n] = fresh_calls(OPTS_B, WALK3D, x)
-            hold(WALK3D, MODELS3D, x, got, fresh[n], what, with_model=n <= MODEL_MAX)
+            assert np.array_equal(x.d2.cpu().numpy(), x.cloud2), what + ": a call wrote the 2-D cloud"
+            key = (n, x.sk_h, x.sk_h2)
+            if key not in fresh:
+                fresh[key] = fresh_calls(OPTS_B, WALK3D, x)
+            hold(WALK3D, MODELS3D, x, got, fresh[key], what, with_model=n <= MODEL_MAX)
+        n, h = LARGEST_GRID
+        buf = CR.state(o, n)
+        x = Inputs()
+        x.d, x.n, x.sk_h = dev(buf.reshape(-1).copy()), n, h
+        x.host = buf
+        what = "size walk, the largest grid: n %d" % n
+        call = {"structure_factor": CALLS3D["structure_factor"]}
+        got = run_calls(live, call, x)
+        assert_same_result(got["structure_factor"], fresh_calls(OPTS_B, call, x)["structure_factor"], what)
+        K = SK.count(h)
+        only = np.unique(np.concatenate([np.arange(0, K, 37), [SK.index(h, 0, 0, 0), K - 1]]))     # (test_parity_on_the_largest_grid)
+        check_sk(buf[0], digest(buf[0]), h, SK_KSTEP, got["structure_factor"], what, only=only)
     finally:
         live.close()
 
@@ -491,6 +669,11 @@ KS_2D = (1.9, 1.8, 1.7, 1.6)           # of the KV beam's rms radii A / 2: the b
 WALK_K_2D = 1.7
 SIZES_2D = [8193, 300, 4097, 1, 65, 8193]
 EPS2_2D = PB2.EPS2_F32
+# the bond radius in units of the larger KV semi-axis (as x.rmax of pair_hist_2d): test_snapshots_host.py asserts from the model that
+# nb <= 256, the premise of bond_numpy.TOL2, and that at least half of the particles have a bond at every snapshot (23, all but two)
+BOND_RMAX_2D = 0.03
+SK_H_2D = (8, 8)
+SK_TURNS_2D = 6.0                      # kstep_a = 6 / A_a: k . x runs over +-6 rad per index across the beam (the 3-D ball: 900 * 2.5 rms = 6.75, 2.25, 22.5)
 
 
 def kv_rms():
@@ -528,6 +711,8 @@ def inputs2d(d, n, prm, par, probes_host):
     x.xvx = [(X, 32, -A[0], A[0]), (VX, 32, -vx_max(), vx_max())]
     x.ax_slice = (Y, 16, -A[1], A[1])
     x.rmax = 0.05 * max(A)
+    x.bond_rmax = BOND_RMAX_2D * max(A)
+    x.sk_h, x.sk_kstep = SK_H_2D, tuple(SK_TURNS_2D / a for a in A)
     x.half = [WALK_K_2D * r for r in kv_rms()]
     return x
 
@@ -552,6 +737,8 @@ CALLS2D = {
     "probe_fmm_2d": probe2("probe_fmm_2d"),
     "probe_2d": probe2("probe_2d"),
     "pair_hist_2d": lambda e, x: dict(cmp=PH.run(e, "exact2d", x.d, x.n, PAIR_BINS, x.rmax)),
+    "bond_order_2d": lambda e, x: bond_call(e, "exact2d", x.d, x.n, x.bond_rmax),
+    "structure_factor_2d": lambda e, x: sk_call(e.structure_factor_2d, x.d, x.n, 2, x.sk_h, x.sk_kstep),
 }
 WALK2D = dict(CALLS2D)
 WALK2D["aperture_2d"] = lambda e, x: aperture_call(e, 2, x.d, x.n, x.half)
@@ -586,6 +773,8 @@ MODELS2D = {
     "probe_2d": lambda x, got, what: PB2._check_exact(got["cmp"], model("probe_2d", x.key + digest(x.t_host), lambda: PR2.exact(
         x.host[0], x.t_host, EPS2_2D, x.par[0])), what),
     "pair_hist_2d": lambda x, got, what: PH.same(got["cmp"], model("pairs2", x.key, lambda: PN.pair_hist(x.host[0], PAIR_BINS, x.rmax)), what),
+    "bond_order_2d": lambda x, got, what: check_bonds(x.host[0], x.key, x.bond_rmax, got, what),
+    "structure_factor_2d": lambda x, got, what: check_sk(x.host[0], x.key, x.sk_h, x.sk_kstep, got, what),
     "aperture_2d": lambda x, got, what: check_aperture(2, x.host, x.half, got, what),
 }
 
@@ -628,6 +817,13 @@ def preconditions_2d():
     table = loss_model_2d()
     assert all(lost >= 50 and kept >= 1000 for lost, kept in table), table
     return table
+
+
+def bond_preconditions_2d():
+    """BOND_RMAX_2D on the unmoved KV beam behind each modelled aperture (as loss_model_2d)"""
+    pos = state2d(N0)[0][0]
+    insides = [AP.inside(pos, AP.ELLIPSOID, [k * r for r in kv_rms()]) for k in KS_2D]
+    return assert_bond_table(bond_table(pos, insides, BOND_RMAX_2D * max(F2.kv_params()[0])))
 
 
 def run_snapshots_2d(diagnostics=True):
