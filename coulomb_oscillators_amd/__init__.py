@@ -11,7 +11,7 @@ from .engine import (Engine, EngineError, lib_path, build_library, default_opts,
                      INTEG_EULER, INTEG_PRE_EULER, INTEG_LEAPFROG, INTEG_FORESTRUTH, INTEG_PEFRL,
                      PHASES, EVAL2D_DIRECT, EVAL2D_DIRECT_KAHAN, EVAL2D_FMM, REF_SEED, REF_DISCARD, init2d,
                      Moments, HistAxis, Q_X, Q_Y, Q_Z, Q_VX, Q_VY, Q_VZ, Aperture, AP_ELLIPSOID, AP_BOX,
-                     helix_matrices, helix_matrices_2d, bath_coeffs, bond_harmonics, BondSummary, sk_phase,
+                     helix_matrices, helix_matrices_2d, bath_coeffs, bond_harmonics, BondSummary, bond_coherence, SolidSummary, BOND_VEC, sk_phase,
                      time_corr_derive, CORR_LAG, mode_corr_ref, mode_corr_derive, MODE_LAG)
 from .dist import DomainRun, TorchComm, SingleComm, LoopbackWorld, SlabRun, LoopbackSlabs
 
@@ -19,5 +19,5 @@ __all__ = ["Engine", "EngineError", "lib_path", "build_library", "default_opts",
            "EVAL_DIRECT", "EVAL_DIRECT_KAHAN", "EVAL_FMM_KDTREE", "EVAL_FMM_TRACELESS", "EVAL_FMM_SYMMETRIC",
            "INTEG_EULER", "INTEG_PRE_EULER", "INTEG_LEAPFROG", "INTEG_FORESTRUTH", "INTEG_PEFRL", "PHASES",
            "EVAL2D_DIRECT", "EVAL2D_DIRECT_KAHAN", "EVAL2D_FMM", "REF_SEED", "REF_DISCARD", "init2d",
-           "Moments", "HistAxis", "Q_X", "Q_Y", "Q_Z", "Q_VX", "Q_VY", "Q_VZ", "Aperture", "AP_ELLIPSOID", "AP_BOX", "helix_matrices", "helix_matrices_2d", "bath_coeffs", "bond_harmonics", "BondSummary", "sk_phase", "time_corr_derive", "CORR_LAG", "mode_corr_ref", "mode_corr_derive", "MODE_LAG",
+           "Moments", "HistAxis", "Q_X", "Q_Y", "Q_Z", "Q_VX", "Q_VY", "Q_VZ", "Aperture", "AP_ELLIPSOID", "AP_BOX", "helix_matrices", "helix_matrices_2d", "bath_coeffs", "bond_harmonics", "BondSummary", "bond_coherence", "SolidSummary", "BOND_VEC", "sk_phase", "time_corr_derive", "CORR_LAG", "mode_corr_ref", "mode_corr_derive", "MODE_LAG",
            "DomainRun", "TorchComm", "SingleComm", "LoopbackWorld", "SlabRun", "LoopbackSlabs"]

@@ -1,6 +1,7 @@
 // bond_order.hpp -- bond-orientational order (include/nbco.h, nbco_bond_order): the one place where the harmonics of a bond are formed.
 // The device kernels (bond_order_kernels.hpp), nbco_bond_harmonics, `nbco3 -cpu -bonds` (host/nbco_cpu.hpp) and, through the export,
-// the tests all call bond_harmonics / bond_powers2, so that a bond contributes the same polynomials wherever it is met.
+// the tests all call bond_harmonics / bond_powers2, so that a bond contributes the same polynomials wherever it is met.  Further down,
+// in the same spirit, the rule of the second pass (nbco_bond_solid): the bond vector record, the coherence of a bond, the averaged order.
 // Real orthonormal harmonics of degree 4 and 6 as polynomials in the unit vector (x, y, z): the m-th derivative of the Legendre
 // polynomial in z, with its integer coefficients, times the real and the imaginary part of (x + i y)^m from a recurrence, times a
 // constant that holds the normalisation sqrt((2l+1)/(4 pi) (l-m)!/(l+m)!), the sqrt(2) of m > 0 and the common factor taken out of
@@ -105,6 +106,83 @@ template <int D> NBCO_BOND_HD void bond_q(const double (&S)[D == 3 ? kBondSums3 
 	}
 	q[0] = sqrt(a) / (double)nb;
 	q[1] = sqrt(b) / (double)nb;
+}
+
+// ---- crystalline particles (include/nbco.h, nbco_bond_solid): the second pass over stored S_lm -------------------------------------------
+// The bond vector record of a particle, kBondVec doubles: the unit vectors q^_4m = S_4m / |S_4| in [0, 9) and q^_6m = S_6m / |S_6| in
+// [9, 22), |S_l| = sqrt(sum_m S_lm^2), then a_4 = |S_4| / nb in [22] and a_6 in [23]: q_l = sqrt(4 pi / (2l+1)) a_l.  A particle without
+// neighbours, or a norm of 0, leaves zeros behind, never a NaN.
+constexpr int kBondVec = 24, kBondVec6 = 9, kBondVecA = 22;
+
+NBCO_BOND_HD void bond_vector(const double (&S)[kBondSums3], int nb, double (&v)[kBondVec])
+{
+	double a = 0.0, b = 0.0;
+#pragma unroll
+	for (int m = 0; m < 9; ++m) a += S[m] * S[m];
+#pragma unroll
+	for (int m = 0; m < 13; ++m) b += S[9 + m] * S[9 + m];
+	a = sqrt(a); b = sqrt(b);
+	const bool ok4 = nb > 0 && a > 0.0, ok6 = nb > 0 && b > 0.0;
+#pragma unroll
+	for (int m = 0; m < 9; ++m) v[m] = ok4 ? S[m] / a : 0.0;
+#pragma unroll
+	for (int m = 0; m < 13; ++m) v[9 + m] = ok6 ? S[9 + m] / b : 0.0;
+	v[kBondVecA] = ok4 ? a / (double)nb : 0.0;
+	v[kBondVecA + 1] = ok6 ? b / (double)nb : 0.0;
+}
+
+// The coherence of a bond, the part that decides an integer: d6 = (((e0 f0 + e1 f1) + e2 f2) + ... + e12 f12) over the q^_6 of the two
+// ends (e6, f6 point at entry kBondVec6 of their records), every product and every sum rounded once, from the left: the same bits from
+// either end of the bond and from numpy's elementwise products and sequential adds.  The bond is solid iff d6 > dmin (a NaN is not).
+NBCO_BOND_HD double bond_coherence(const double *e6, const double *f6)
+{
+#pragma clang fp contract(off)   // (a fused e f + d would round once where the rule rounds twice, and differently from the other end)
+	double d = e6[0] * f6[0];
+#pragma unroll
+	for (int m = 1; m < 13; ++m)
+	{
+		const double t = e6[m] * f6[m];
+		d = d + t;
+	}
+	return d;
+}
+
+// one term of the averaged order: T_lm += a_l q^_lm of the record f (the particle itself first, then its neighbours as they are met)
+NBCO_BOND_HD void bond_avg_add(const double *f, double (&T)[kBondSums3])
+{
+	const double a4 = f[kBondVecA], a6 = f[kBondVecA + 1];
+#pragma unroll
+	for (int m = 0; m < 9; ++m) T[m] += a4 * f[m];
+#pragma unroll
+	for (int m = 0; m < 13; ++m) T[9 + m] += a6 * f[9 + m];
+}
+
+// {q-bar_4, q-bar_6} of Lechner and Dellago from those sums: sqrt(4 pi / (2l+1) sum_m T_lm^2) / (nb + 1); 0 for a particle without neighbours
+NBCO_BOND_HD void bond_qbar(const double (&T)[kBondSums3], int nb, double (&q)[2])
+{
+	q[0] = q[1] = 0.0;
+	if (nb <= 0) return;
+	double a = 0.0, b = 0.0;
+#pragma unroll
+	for (int m = 0; m < 9; ++m) a += T[m] * T[m];
+#pragma unroll
+	for (int m = 0; m < 13; ++m) b += T[9 + m] * T[9 + m];
+	q[0] = sqrt(kBondQ4 * a) / (double)(nb + 1);
+	q[1] = sqrt(kBondQ6 * b) / (double)(nb + 1);
+}
+
+// What a solid summary is made of, in 8-byte slots: 0, 1: the sums of q-bar_4 and q-bar_6 over the particles with nb > 0, then as 64-bit
+// integers 2: sum nb, 3: #{nb == 0}, 4: sum xi, 5: #{xi >= xi_min}, 6: max xi.
+constexpr int kSolidRec = 7, kSolidRecBonds = 2, kSolidRecIsolated = 3, kSolidRecSolid = 4, kSolidRecCount = 5, kSolidRecMax = 6;
+
+template <class Summary>
+inline void bond_solid_summary_fill(const double (&qsum)[2], long long bonds, long long isolated, long long solid_bonds, long long n_solid, long long xi_max,
+                                    long long n, double dmin, int xi_min, Summary &s)
+{
+	s.n = n; s.bonds = bonds; s.isolated = isolated; s.solid_bonds = solid_bonds; s.n_solid = n_solid;
+	s.xi_max = (int)xi_max; s.xi_min = xi_min; s.dmin = dmin;
+	const long long linked = n - isolated;
+	for (int l = 0; l < 2; ++l) s.qbar_mean[l] = linked > 0 ? qsum[l] / (double)linked : 0.0;
 }
 
 // What a summary is made of: the sums over the particles, in 8-byte slots.  [0, 22): sum_i S(i) (2-D: the first 4, the others 0),

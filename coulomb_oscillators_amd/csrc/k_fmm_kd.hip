@@ -897,6 +897,41 @@ int kd_bond_order_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb, d
 	return sum_host ? bond_summary_finish(c, rec, records, n, 3, sum_host) : NBCO_OK;
 }
 
+// nbco_bond_vectors_tree: pass 1 alone, the records where q would go, in the caller's order
+int kd_bond_vectors_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb, double *vec)
+{
+	NBCO_TRY(kd_radius_walk_tree(c, x, n));
+	launch_radius_walk(c, kd_bond_walk_kernel<false, true, false>, 0, n, R2, R2, nb, vec, (double *)nullptr);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// nbco_bond_solid_tree: one tree; the records in tree order in c->bond_vec -- gathered from the caller's, or written there by a walk of
+// pass 1 -- and the walk of pass 2 over them
+int kd_bond_solid_tree(nbco_ctx *c, float *x, long long n, double R2, const double *vec, double dmin, int xi_min, int *nb, int *xi, double *qbar,
+                       nbco_solid_summary *sum_host)
+{
+	NBCO_TRY(kd_radius_walk_tree(c, x, n));
+	NBCO_TRY(c->reserve(c->bond_vec, sizeof(double) * kBondVec * (size_t)n));
+	double *tvec = c->bond_vec.as<double>();
+	if (vec)
+		hipLaunchKernelGGL(kd_solid_gather_kernel, dim3(grid1d(kBondVec * n)), dim3(kBlock), 0, c->stream, vec, (const int *)c->unsort.as<int>(), n, tvec);
+	else launch_radius_walk(c, kd_bond_walk_kernel<false, true, true>, 0, n, R2, R2, (int *)nullptr, tvec, (double *)nullptr);
+	NBCO_HIP(hipGetLastError());
+	const long long records = (n + 63) / 64;
+	double *rec = nullptr;
+	if (sum_host)
+	{
+		NBCO_TRY(c->reserve(c->part, sizeof(double) * kSolidRec * (size_t)records));
+		rec = c->part.as<double>();
+	}
+	with_flag(sum_host != nullptr, [&](auto ws) {
+		launch_radius_walk(c, kd_solid_walk_kernel<decltype(ws)::value>, 0, n, R2, R2, (const double *)tvec, dmin, xi_min, nb, xi, qbar, rec);
+	});
+	NBCO_HIP(hipGetLastError());
+	return sum_host ? bond_solid_finish(c, rec, records, n, dmin, xi_min, sum_host) : NBCO_OK;
+}
+
 // kd_fields has returned `rc`: twice the room for the lists (the caller's arrays are untouched), or reaction records sized from the
 // pair count just seen, and the same evaluation once more?  On the same rebuild schedule: a forced rebuild here would make the
 // trees of the following tree_steps - 1 evaluations depend on when a buffer happened to fill up.

@@ -493,7 +493,7 @@ constexpr int kBondOut = 256;
 int bond_summary_finish(nbco_ctx *c, const double *rec, long long records, long long n, int dim, nbco_bond_summary *sum_host)
 {
 	double *out = c->small.as<double>() + kBondOut;
-	hipLaunchKernelGGL(bond_reduce_kernel, dim3(1), dim3(kBondGroups * kBondSlots), 0, c->stream, rec, records, out);
+	hipLaunchKernelGGL((bond_reduce_kernel<kBondRec, kBondRecBonds, kBondRecMax>), dim3(1), dim3(kBondGroups * kBondSlots), 0, c->stream, rec, records, out);
 	NBCO_HIP(hipGetLastError());
 	double h[kBondRec];
 	NBCO_HIP(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -526,6 +526,59 @@ int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R
 	});
 	NBCO_HIP(hipGetLastError());
 	return sum_host ? bond_summary_finish(c, rec, records, n, dim, sum_host) : NBCO_OK;
+}
+
+// nbco_bond_vectors: pass 1 alone, the records where q would go
+int launch_bond_vectors(nbco_ctx *c, const float *p, long long n, double R2, int *nb, double *vec)
+{
+	const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+	hipLaunchKernelGGL((bond_exact_kernel<float, 3, false, true>), grid, block, 0, c->stream, p, n, R2, nb, vec, (double *)nullptr);
+	NBCO_HIP(hipGetLastError());
+	return NBCO_OK;
+}
+
+// the solid summary of a call from the wave records in `rec`, in the shape of bond_summary_finish.  Synchronises.
+int bond_solid_finish(nbco_ctx *c, const double *rec, long long records, long long n, double dmin, int xi_min, nbco_solid_summary *sum_host)
+{
+	double *out = c->small.as<double>() + kBondOut;
+	hipLaunchKernelGGL((bond_reduce_kernel<kSolidRec, kSolidRecBonds, kSolidRecMax>), dim3(1), dim3(kBondGroups * kBondSlots), 0, c->stream, rec, records, out);
+	NBCO_HIP(hipGetLastError());
+	double h[kSolidRec];
+	NBCO_HIP(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, c->stream));
+	NBCO_HIP(hipStreamSynchronize(c->stream));
+	const double qsum[2] = {h[0], h[1]};
+	long long ints[kSolidRec - kSolidRecBonds];
+	memcpy(ints, h + kSolidRecBonds, sizeof ints);
+	nbco_solid_summary s;
+	memset(&s, 0, sizeof s);
+	bond_solid_summary_fill(qsum, ints[0], ints[1], ints[2], ints[3], ints[4], n, dmin, xi_min, s);
+	*sum_host = s;
+	return NBCO_OK;
+}
+
+// nbco_bond_solid: pass 2 over the caller's records, or over the records of a pass 1 of its own in c->bond_vec
+int launch_bond_solid(nbco_ctx *c, const float *p, long long n, double R2, const double *vec, double dmin, int xi_min, int *nb, int *xi, double *qbar,
+                      nbco_solid_summary *sum_host)
+{
+	const long long records = (n + 63) / 64;
+	if (!vec)
+	{
+		NBCO_TRY(c->reserve(c->bond_vec, sizeof(double) * kBondVec * (size_t)n));
+		NBCO_TRY(launch_bond_vectors(c, p, n, R2, nullptr, c->bond_vec.as<double>()));
+		vec = c->bond_vec.as<double>();
+	}
+	double *rec = nullptr;
+	if (sum_host)
+	{
+		NBCO_TRY(c->reserve(c->part, sizeof(double) * kSolidRec * (size_t)records));
+		rec = c->part.as<double>();
+	}
+	const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+	with_flag(sum_host != nullptr, [&](auto ws) {
+		hipLaunchKernelGGL((bond_solid_exact_kernel<decltype(ws)::value>), grid, block, 0, c->stream, p, n, R2, vec, dmin, xi_min, nb, xi, qbar, rec);
+	});
+	NBCO_HIP(hipGetLastError());
+	return sum_host ? bond_solid_finish(c, rec, records, n, dmin, xi_min, sum_host) : NBCO_OK;
 }
 
 // ---- sums on the wave-vector grid: static structure factor, mode records (structure_factor_kernels.hpp) ----

@@ -799,6 +799,56 @@ int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, 
 	return maybe_sync(c);
 }
 
+// ---- crystalline particles: bond vector records, solid bonds and the averaged order -----------------
+int nbco_bond_coherence(const double *vec_i, const double *vec_j, double *d6_host)
+{
+	if (!vec_i || !vec_j || !d6_host) return NBCO_ERR_ARG;
+	*d6_host = bond_coherence(vec_i + kBondVec6, vec_j + kBondVec6);
+	return NBCO_OK;
+}
+
+int nbco_bond_vectors(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *vec_dev)
+{
+	NBCO_TRY(bond_args(c, "nbco_bond_vectors", false, p, n, rmax, nb_dev, vec_dev, nullptr));
+	NBCO_TRY(launch_bond_vectors(c, p, n, rmax * rmax, nb_dev, vec_dev));
+	return maybe_sync(c);
+}
+
+int nbco_bond_vectors_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *vec_dev)
+{
+	NBCO_TRY(bond_args(c, "nbco_bond_vectors_tree", true, p, n, rmax, nb_dev, vec_dev, nullptr));
+	NBCO_TRY(on_private_copy(c, "nbco_bond_vectors_tree", p, n, 3, [&](nbco_ctx *k, float *x) { return kd_bond_vectors_tree(k, x, n, rmax * rmax, nb_dev, vec_dev); }));
+	return maybe_sync(c);
+}
+
+// what both solid calls refuse before any launch: what the bond order refuses, and a bad threshold
+static int solid_args(nbco_ctx *c, const char *who, bool tree, const void *p, long long n, double rmax, double dmin, int xi_min, const void *nb_dev, const void *xi_dev,
+                      const void *qbar_dev, const void *sum_host)
+{
+	NBCO_TRY(bond_args(c, who, tree, p, n, rmax, nb_dev ? nb_dev : xi_dev, qbar_dev, sum_host));
+	if (!std::isfinite(dmin)) return c->fail(NBCO_ERR_ARG, std::string(who) + ": dmin must be finite");
+	if (xi_min < 0) return c->fail(NBCO_ERR_ARG, std::string(who) + ": xi_min must not be negative");
+	return NBCO_OK;
+}
+
+int nbco_bond_solid(nbco_ctx *c, const float *p, long long n, double rmax, const double *vec_dev, double dmin, int xi_min, int *nb_dev, int *xi_dev, double *qbar_dev,
+                    nbco_solid_summary *sum_host)
+{
+	NBCO_TRY(solid_args(c, "nbco_bond_solid", false, p, n, rmax, dmin, xi_min, nb_dev, xi_dev, qbar_dev, sum_host));
+	NBCO_TRY(launch_bond_solid(c, p, n, rmax * rmax, vec_dev, dmin, xi_min, nb_dev, xi_dev, qbar_dev, sum_host));
+	return maybe_sync(c);
+}
+
+int nbco_bond_solid_tree(nbco_ctx *c, const float *p, long long n, double rmax, const double *vec_dev, double dmin, int xi_min, int *nb_dev, int *xi_dev,
+                         double *qbar_dev, nbco_solid_summary *sum_host)
+{
+	NBCO_TRY(solid_args(c, "nbco_bond_solid_tree", true, p, n, rmax, dmin, xi_min, nb_dev, xi_dev, qbar_dev, sum_host));
+	NBCO_TRY(on_private_copy(c, "nbco_bond_solid_tree", p, n, 3, [&](nbco_ctx *k, float *x) {
+		return kd_bond_solid_tree(k, x, n, rmax * rmax, vec_dev, dmin, xi_min, nb_dev, xi_dev, qbar_dev, sum_host);
+	}));
+	return maybe_sync(c);
+}
+
 // ---- static structure factor -------------------------------------------------------------------
 int nbco_sk_phase(double t, double *cs_host)
 {

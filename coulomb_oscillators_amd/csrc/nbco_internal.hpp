@@ -307,6 +307,7 @@ struct nbco_ctx
 	nbco_ctx *energy_child = nullptr;   // nbco_energy_tree, nbco_probe_tree: a private context for the tree they build (created on first use, freed by nbco_destroy)
 	bool drifted = false;               // nbco_integrate has moved the particles since the last kd-tree evaluation (a scheme that ends on a drift): nbco_kd_probe refuses
 	DevBuf probe_keys, probe_tmp;       // nbco_kd_probe / nbco_probe_tree: the probes' keys and sort permutation, their sort's scratch
+	DevBuf bond_vec;                    // nbco_bond_solid: the bond vector records of its own pass 1; in the tree form (on the private context) the records in tree order
 	DevBuf sk_part;                     // nbco_structure_factor: the partial sums of the particle ranges
 	DevBuf tc_part;                     // nbco_time_corr: the records of the row ranges
 	DevBuf md_part;                     // nbco_modes_record: the mode records of the particle ranges
@@ -414,6 +415,12 @@ int launch_pair_hist(nbco_ctx *c, const void *p, int dim, long long n, const Pai
 int launch_bond_order(nbco_ctx *c, const void *p, int dim, long long n, double R2, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 // the wave records of a bond-order call (`records` of them, on the device) -> *sum_host.  Synchronises.
 int bond_summary_finish(nbco_ctx *c, const double *rec, long long records, long long n, int dim, nbco_bond_summary *sum_host);
+// crystalline particles, exact forms: pass 1 alone (the bond vector records), and pass 2 over `vec_dev` or, if that is nullptr, over
+// records of its own in c->bond_vec.  bond_solid_finish: the wave records of a solid pass -> *sum_host.  Synchronises.
+int launch_bond_vectors(nbco_ctx *c, const float *p, long long n, double R2, int *nb_dev, double *vec_dev);
+int launch_bond_solid(nbco_ctx *c, const float *p, long long n, double R2, const double *vec_dev, double dmin, int xi_min, int *nb_dev, int *xi_dev, double *qbar_dev,
+                      nbco_solid_summary *sum_host);
+int bond_solid_finish(nbco_ctx *c, const double *rec, long long records, long long n, double dmin, int xi_min, nbco_solid_summary *sum_host);
 // static structure factor (structure_factor_kernels.hpp): 2 K doubles to rho_dev; with n_used_host the call synchronises
 int launch_structure_factor(nbco_ctx *c, const void *p, int dim, long long n, const nbco_sk_grid &g, double *rho_dev, long long *n_used_host);
 // tracked trajectories (time_corr_kernels.hpp): frame `frame` of traj from the state buf, particle numbers from ids (device; NULL: the row);
@@ -439,6 +446,9 @@ int launch_aperture_compact(nbco_ctx *c, void *buf, int dim, long long n, long l
 // k_fmm_kd.hip
 int kd_pair_hist_tree(nbco_ctx *c, float *x, long long n, const PairBins &pb, unsigned long long *counts_dev, double *nn2_dev);
 int kd_bond_order_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
+int kd_bond_vectors_tree(nbco_ctx *c, float *x, long long n, double R2, int *nb_dev, double *vec_dev);
+int kd_bond_solid_tree(nbco_ctx *c, float *x, long long n, double R2, const double *vec_dev, double dmin, int xi_min, int *nb_dev, int *xi_dev, double *qbar_dev,
+                       nbco_solid_summary *sum_host);
 int fmm_kdtree_eval(nbco_ctx *c, float *p, float *a, long long n, const float *param, KdStepLink *link = nullptr);
 int kd_copy_out(nbco_ctx *c, int which, void *host_dst, long long host_bytes);
 int kd_count_pairs(nbco_ctx *c, long long *out);

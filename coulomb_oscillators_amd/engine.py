@@ -106,6 +106,15 @@ class BondSummary(C.Structure):
                 ("q_mean", C.c_double * 2), ("Q", C.c_double * 2)]
 
 
+BOND_VEC = 24   # doubles of a particle's bond vector record: q^_4m in [0, 9), q^_6m in [9, 22), a_4, a_6 (include/nbco.h, nbco_bond_solid)
+
+
+class SolidSummary(C.Structure):
+    """nbco_solid_summary (include/nbco.h)"""
+    _fields_ = [("n", C.c_longlong), ("bonds", C.c_longlong), ("isolated", C.c_longlong), ("solid_bonds", C.c_longlong), ("n_solid", C.c_longlong),
+                ("xi_max", C.c_int), ("xi_min", C.c_int), ("dmin", C.c_double), ("qbar_mean", C.c_double * 2)]
+
+
 class SkGrid(C.Structure):
     """nbco_sk_grid (include/nbco.h)"""
     _fields_ = [("h", C.c_int * 3), ("kstep", C.c_double * 3)]
@@ -247,6 +256,11 @@ def _load():
         "nbco_bond_order": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
         "nbco_bond_order_tree": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
         "nbco_2d_bond_order": [P, P, LL, D, P, P, C.POINTER(BondSummary)],
+        "nbco_bond_coherence": [C.POINTER(D), C.POINTER(D), C.POINTER(D)],
+        "nbco_bond_vectors": [P, P, LL, D, P, P],
+        "nbco_bond_vectors_tree": [P, P, LL, D, P, P],
+        "nbco_bond_solid": [P, P, LL, D, P, D, C.c_int, P, P, P, C.POINTER(SolidSummary)],
+        "nbco_bond_solid_tree": [P, P, LL, D, P, D, C.c_int, P, P, P, C.POINTER(SolidSummary)],
         "nbco_structure_factor": [P, P, LL, C.POINTER(SkGrid), P, C.POINTER(LL)],
         "nbco_2d_structure_factor": [P, P, LL, C.POINTER(SkGrid), P, C.POINTER(LL)],
         "nbco_sk_phase": [D, C.POINTER(D)],
@@ -363,6 +377,18 @@ def bond_harmonics(u):
     if rc != 0:
         raise EngineError("nbco_bond_harmonics failed with status %d" % rc, status=rc)
     return np.array(y4[:], dtype=np.float64), np.array(y6[:], dtype=np.float64)
+
+
+def bond_coherence(vec_i, vec_j):
+    """d6 of a bond from the bond vector records (BOND_VEC doubles each) of its two ends, as the solid-bond kernels form it
+    (nbco_bond_coherence, include/nbco.h): the products of the 13 q^_6 entries added from the left, every product and sum rounded once.
+    Host only, needs no GPU."""
+    a, b = (C.c_double * BOND_VEC)(*[float(t) for t in vec_i]), (C.c_double * BOND_VEC)(*[float(t) for t in vec_j])
+    d6 = C.c_double()
+    rc = _load().nbco_bond_coherence(a, b, C.byref(d6))
+    if rc != 0:
+        raise EngineError("nbco_bond_coherence failed with status %d" % rc, status=rc)
+    return d6.value
 
 
 def sk_phase(t):
@@ -847,6 +873,53 @@ class Engine:
     def bond_order_2d(self, p, n, rmax, nb=None, q=None, summary=True):
         """the exact form for the 2-D fp64 positions (xy pairs; nbco_2d_bond_order): q holds |psi4| and |psi6|, the hexatic order"""
         return self._bond_order(self.lib.nbco_2d_bond_order, p, n, rmax, nb, q, summary)
+
+    # ---- crystalline particles: bond vector records, solid bonds, averaged order ---------------------
+    def _out(self, given, shape, dtype, device):
+        """an output by the conventions of _bond_order: None allocates, False asks for none of it"""
+        if given is None:
+            return self.torch.empty(shape, dtype=dtype, device=device)
+        return None if given is False else given
+
+    def _bond_vectors(self, fn, p, n, rmax, nb, vec):
+        room = max(int(n), 0)   # (the library refuses a bad n; nothing is sized by it)
+        nb = self._out(nb, room, self.torch.int32, p.device)
+        vec = self._out(vec, (room, BOND_VEC), self.torch.float64, p.device)
+        self._chk(fn(self.ctx, _ptr(p), n, float(rmax), _ptr(nb), _ptr(vec)))
+        return nb, vec
+
+    def bond_vectors(self, p, n, rmax, nb=None, vec=None):
+        """the bond vector records of the n positions p, all pairs, exact (nbco_bond_vectors): pass 1 of bond_order with the normalised
+        S_lm as output.  Returns (nb, vec): nb as bond_order's, vec a float64 device tensor (n, BOND_VEC) -- q^_4m, q^_6m, a_4, a_6 --
+        both in the caller's order; allocated if None, overwritten if given, False asks for none of that output."""
+        return self._bond_vectors(self.lib.nbco_bond_vectors, p, n, rmax, nb, vec)
+
+    def bond_vectors_tree(self, p, n, rmax, nb=None, vec=None):
+        """the same from the kd-tree walk of bond_order_tree on the private context (nbco_bond_vectors_tree)"""
+        return self._bond_vectors(self.lib.nbco_bond_vectors_tree, p, n, rmax, nb, vec)
+
+    def _bond_solid(self, fn, p, n, rmax, dmin, xi_min, vec, nb, xi, qbar, summary):
+        room = max(int(n), 0)
+        nb = self._out(nb, room, self.torch.int32, p.device)
+        xi = self._out(xi, room, self.torch.int32, p.device)
+        qbar = self._out(qbar, (room, 2), self.torch.float64, p.device)
+        out = SolidSummary() if summary else None
+        self._chk(fn(self.ctx, _ptr(p), n, float(rmax), _ptr(vec), float(dmin), int(xi_min), _ptr(nb), _ptr(xi), _ptr(qbar), C.byref(out) if summary else None))
+        return nb, xi, qbar, out
+
+    def bond_solid(self, p, n, rmax, dmin, xi_min, vec=None, nb=None, xi=None, qbar=None, summary=True):
+        """which of the n positions p are crystalline, all pairs, exact (nbco_bond_solid): per particle the number xi of SOLID bonds --
+        neighbours j with d6(i, j) > dmin, d6 the dot product of the two q^_6 vectors -- and the neighbour-averaged q-bar_4, q-bar_6.
+        vec: the records of bond_vectors (read only), or None: the call forms them itself and returns the same bytes.  Returns
+        (nb, xi, qbar, summary): int32 (n), int32 (n), float64 (n, 2) device tensors in the caller's order and a SolidSummary (n_solid =
+        #{xi >= xi_min}, solid_bonds, xi_max, the means of q-bar over the particles with neighbours).  Outputs are allocated if None,
+        overwritten if given; False asks for none of that output, summary=False for no summary (the call then does not synchronise)."""
+        return self._bond_solid(self.lib.nbco_bond_solid, p, n, rmax, dmin, xi_min, vec, nb, xi, qbar, summary)
+
+    def bond_solid_tree(self, p, n, rmax, dmin, xi_min, vec=None, nb=None, xi=None, qbar=None, summary=True):
+        """the same from a kd-tree of its own on the private context (nbco_bond_solid_tree); with vec=None one tree and two walks.  For
+        the same records nb, xi and the summary's integers are equal integer for integer, q-bar to rounding."""
+        return self._bond_solid(self.lib.nbco_bond_solid_tree, p, n, rmax, dmin, xi_min, vec, nb, xi, qbar, summary)
 
     # ---- static structure factor -------------------------------------------------------------------
     def _structure_factor(self, fn, dim, p, n, h, kstep, rho, count):

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -94,6 +95,13 @@ const char *kHelp =
     "                    q6_mean Q4 Q6' to <output>/bonds.txt.  From a range-limited kd-tree walk of its own (nbco_bond_order_tree; with -cpu:\n"
     "                    all pairs on the host, the same neighbour rule and harmonics: the same nb, q to rounding).\n"
     "                    The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
+    "  -solid <rmax> <dmin> <xi_min>   At every snapshot write which particles are crystalline to <output>/solid<iter>_<ds>.bin: n int32 -- per\n"
+    "                    particle, in the snapshot's order, the number of neighbours nb closer than rmax -- then n int32: the number xi of\n"
+    "                    those neighbours whose q6 vector is aligned with the particle's own (solid bonds: d6 > dmin), then n x 2 doubles:\n"
+    "                    the neighbour-averaged q-bar_4 and q-bar_6 (0 where nb = 0), and append 'iter n_solid solid_bonds xi_max\n"
+    "                    qbar4_mean qbar6_mean' to <output>/solid.txt, n_solid the particles with xi >= xi_min.  From one kd-tree of its own\n"
+    "                    and two range-limited walks (nbco_bond_solid_tree; with -cpu: all pairs on the host, the same rule: the same nb,\n"
+    "                    q-bar to rounding).  The trajectory is not affected; no effect with -test, -test2 or -accuracy.\n"
     "  -sk <hx> <hy> <hz> <kx> <ky> <kz>   At every snapshot write the static structure factor of the positions to <output>/sk<iter>_<ds>.bin:\n"
     "                    K x 2 doubles {re, im} of rho_k = sum_j exp(i k . x_j) on the grid k = (ix kx, iy ky, iz kz), ix = 0..hx, iy = -hy..hy,\n"
     "                    iz = -hz..hz (h <= 64), K = (hx+1)(2hy+1)(2hz+1), at index ((ix)(2hy+1) + iy + hy)(2hz+1) + iz + hz, and append\n"
@@ -132,7 +140,7 @@ const char *kHelp =
     "                    longer simulated (nbco_aperture_apply; with -cpu the same rule on the host).  Per snapshot\n"
     "                    <output>/lost<iter>_<ds>.bin receives k int32 rows (the rows the lost particles had in the state; with\n"
     "                    -snapshot-order input their particle numbers), then k x 6 floats x y z vx vy vz -- empty when nobody was lost --\n"
-    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs, -bonds, -sk\n"
+    "                    and <output>/losses.txt one line 'iter n_lost n_left'.  The snapshot and -energy, -moments, -probes, -pairs, -bonds, -solid, -sk\n"
     "                    describe the survivors; the snapshot files shrink with n.  A run that loses everybody ends with an error.\n"
     "                    Refused with -test, -test2 and -accuracy.\n"
     "  -aperture-centre <cx> <cy> <cz>   Centre of the aperture (default 0 0 0).\n"
@@ -232,6 +240,37 @@ bool write_pairs(const std::string &folder, int iter, SCAL dt, const std::vector
 	if (!f) std::cerr << "Error: cannot write the pair file of iteration " << iter << " into \"" << folder << "\"" << std::endl;
 	return (bool)f;
 }
+
+// -solid <rmax> <dmin> <xi_min> (rmax = 0: the flag was not given).  <folder>/solid<iter>_<dt>.bin: n int32 of nb, n int32 of xi, then
+// n x 2 doubles {q-bar_4, q-bar_6}; <folder>/solid.txt (emptied when the run starts): 'iter n_solid solid_bonds xi_max qbar4_mean
+// qbar6_mean' per snapshot
+struct SolidOpt
+{
+	double rmax = 0, dmin = 0;
+	int xi_min = 0;
+};
+struct SolidLog
+{
+	SolidOpt opt;
+	std::string folder;
+	std::ofstream out;
+	SolidLog(const SolidOpt &opt_, const std::string &folder_) : opt(opt_), folder(folder_)
+	{
+		if (opt.rmax > 0) out.open(folder + "/solid.txt", std::ios::out | std::ios::trunc);
+	}
+	bool record(int iter, SCAL dt, const std::vector<int> &nb, const std::vector<int> &xi, const std::vector<double> &qbar, const nbco_solid_summary &s)
+	{
+		std::ofstream f(folder + "/solid" + std::to_string(iter) + '_' + std::to_string(dt) + ".bin", std::ios::out | std::ios::binary);
+		if (f) f.write(reinterpret_cast<const char *>(nb.data()), (std::streamsize)(nb.size() * sizeof(int)));
+		if (f) f.write(reinterpret_cast<const char *>(xi.data()), (std::streamsize)(xi.size() * sizeof(int)));
+		if (f) f.write(reinterpret_cast<const char *>(qbar.data()), (std::streamsize)(qbar.size() * sizeof(double)));
+		char buf[256];
+		std::snprintf(buf, sizeof buf, "%d %lld %lld %d %.17g %.17g\n", iter, s.n_solid, s.solid_bonds, s.xi_max, s.qbar_mean[0], s.qbar_mean[1]);
+		out << buf << std::flush;
+		if (!f || !out) std::cerr << "Error: cannot write the solid files of iteration " << iter << " into \"" << folder << "\"" << std::endl;
+		return f && out;
+	}
+};
 
 // -bonds <rmax> (rmax = 0: the flag was not given).  <folder>/bonds<iter>_<dt>.bin: n int32 of nb, then n x 2 doubles {q4, q6};
 // <folder>/bonds.txt (emptied when the run starts): 'iter bonds isolated nb_max q4_mean q6_mean Q4 Q6' per snapshot
@@ -430,7 +469,7 @@ struct Session
 	// simulation: accelerations first, then nIters fused integrator steps; a snapshot [pos | vel] every nSteps iterations
 	// (main3.cu:832-874).  Evaluations are enqueued without a drain; the copy of a snapshot is what waits for the device.
 	int simulate(int scheme, SCAL dt, int nIters, int nSteps, const std::string &folder, std::vector<float> &host, size_t state_bytes, bool input_order,
-	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const SkOpt &sk, const ApertureOpt &aperture,
+	             bool energy, bool moments, const std::vector<float> &probes, const PairsOpt &pairs, double bonds_rmax, const SolidOpt &solid, const SkOpt &sk, const ApertureOpt &aperture,
 	             const SlicesOpt &slices, const double *omega, const nbco_bath &bath, const CorrOpt &corr, const ModesOpt &modes)
 	{
 		// -modes: the series of mode records on the device (K x frames x 8 doubles) and the records of the lags
@@ -490,6 +529,13 @@ struct Session
 		std::vector<int> bonds_nb_host(bond_n), bonds_nb_rows(input_order ? bond_n : 0);
 		std::vector<double> bonds_q_host(2 * bond_n), bonds_q_rows(input_order ? 2 * bond_n : 0);
 		BondsLog blog(bonds_rmax, folder);
+		// -solid: nb, xi and {q-bar_4, q-bar_6} on the device, and the host copies that go into the files
+		const size_t solid_n = solid.rmax > 0 ? (size_t)n : 0;
+		DeviceArray<int> solid_nb(solid_n), solid_xi(solid_n);
+		DeviceArray<double> solid_q(2 * solid_n);
+		std::vector<int> solid_nb_host(solid_n), solid_xi_host(solid_n), solid_nb_rows(input_order ? solid_n : 0), solid_xi_rows(input_order ? solid_n : 0);
+		std::vector<double> solid_q_host(2 * solid_n), solid_q_rows(input_order ? 2 * solid_n : 0);
+		SolidLog slog(solid, folder);
 		// -sk: rho on the device and the host copy that goes into the file
 		DeviceArray<double> sk_rho(sk.on ? 2 * (size_t)sk.K : 0);
 		std::vector<double> sk_rho_host(sk.on ? 2 * (size_t)sk.K : 0);
@@ -680,6 +726,33 @@ struct Session
 				}
 				else if (!blog.record(snap, dt, bonds_nb_host, bonds_q_host, bsum)) return -1;
 			}
+			if (solid.rmax > 0)
+			{
+				// one call: the private context's tree, the walk of the harmonics and the walk of the records; the summary synchronises
+				nbco_solid_summary ssum;
+				check(nbco_bond_solid_tree(ctx(), state.ptr, n, solid.rmax, nullptr, solid.dmin, solid.xi_min, solid_nb.ptr, solid_xi.ptr, solid_q.ptr, &ssum), "bond_solid_tree");
+				solid_nb_host.resize((size_t)n);
+				solid_xi_host.resize((size_t)n);
+				solid_q_host.resize(2 * (size_t)n);
+				HIPCHK(hipMemcpy(solid_nb_host.data(), solid_nb.ptr, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(solid_xi_host.data(), solid_xi.ptr, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(solid_q_host.data(), solid_q.ptr, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+				if (input_order)
+				{
+					solid_nb_rows.resize((size_t)n);
+					solid_xi_rows.resize((size_t)n);
+					solid_q_rows.resize(2 * (size_t)n);
+					for (size_t r = 0; r < (size_t)n; ++r)   // (the rows of the snapshot file)
+					{
+						solid_nb_rows[r] = solid_nb_host[(size_t)rank[r]];
+						solid_xi_rows[r] = solid_xi_host[(size_t)rank[r]];
+						solid_q_rows[2 * r] = solid_q_host[2 * (size_t)rank[r]];
+						solid_q_rows[2 * r + 1] = solid_q_host[2 * (size_t)rank[r] + 1];
+					}
+					if (!slog.record(snap, dt, solid_nb_rows, solid_xi_rows, solid_q_rows, ssum)) return -1;
+				}
+				else if (!slog.record(snap, dt, solid_nb_host, solid_xi_host, solid_q_host, ssum)) return -1;
+			}
 			if (sk.on)
 			{
 				// a sum over the particles: the order of the state does not matter to it
@@ -722,6 +795,7 @@ int main(int argc, const char **argv)
 	std::vector<float> probes;
 	PairsOpt pairs;
 	double bonds_rmax = 0;
+	SolidOpt solid;
 	SkOpt sk;
 	CorrOpt corr;
 	ModesOpt modes;
@@ -869,6 +943,22 @@ int main(int argc, const char **argv)
 				return -1;
 			}
 			i += 2;
+		}
+		else if (a == "-solid")
+		{
+			if (!need(i, 3, "-solid")) return -1;
+			solid.rmax = atof(argv[i + 1]);
+			solid.dmin = atof(argv[i + 2]);
+			char *end = nullptr;
+			const long xm = strtol(argv[i + 3], &end, 10);
+			if (!std::isfinite(solid.rmax) || !(solid.rmax > 0) || !std::isfinite(solid.dmin) || end == argv[i + 3] || *end || xm < 0 || xm > 0x7fffffffL)
+			{
+				std::cerr << "Error: invalid argument to '-solid': " << argv[i + 1] << ' ' << argv[i + 2] << ' ' << argv[i + 3]
+				          << " (rmax greater than 0, dmin finite, xi_min a non-negative integer)\n";
+				return -1;
+			}
+			solid.xi_min = (int)xm;
+			i += 3;
 		}
 		else if (a == "-bonds")
 		{
@@ -1119,6 +1209,9 @@ int main(int argc, const char **argv)
 		std::vector<int> bonds_nb;
 		std::vector<double> bonds_q;
 		BondsLog blog(bonds_rmax, strout);
+		std::vector<int> solid_nb, solid_xi;
+		std::vector<double> solid_q;
+		SolidLog slog(solid, strout);
 		std::vector<double> sk_rho;
 		SkLog sklog(3, sk, strout);
 		LossLog llog(aperture.on, strout);
@@ -1244,6 +1337,12 @@ int main(int argc, const char **argv)
 				nbco_cpu::bond_order(st.data(), nBodies, bonds_rmax, bonds_nb, bonds_q, bsum);
 				if (!blog.record(iter, dt, bonds_nb, bonds_q, bsum)) return -1;
 			}
+			if (solid.rmax > 0)
+			{
+				nbco_solid_summary ssum;
+				nbco_cpu::bond_solid(st.data(), nBodies, solid.rmax, solid.dmin, solid.xi_min, solid_nb, solid_xi, solid_q, ssum);
+				if (!slog.record(iter, dt, solid_nb, solid_xi, solid_q, ssum)) return -1;
+			}
 			if (sk.on)
 			{
 				const long long n_used = nbco_cpu::structure_factor(st.data(), nBodies, sk.g, sk_rho);
@@ -1268,7 +1367,7 @@ int main(int argc, const char **argv)
 		if (test) s.print_error_table(host);
 		else if (test2) s.print_reuse_errors(dt);
 		else rc = s.simulate(scheme, dt, nIters, nSteps, strout, host, state_bytes, input_order, energy && !b_accuracy, moments && !b_accuracy, b_accuracy ? std::vector<float>{} : probes,
-		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, b_accuracy ? SkOpt{} : sk, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
+		                     b_accuracy ? PairsOpt{} : pairs, b_accuracy ? 0.0 : bonds_rmax, b_accuracy ? SolidOpt{} : solid, b_accuracy ? SkOpt{} : sk, aperture, b_accuracy ? SlicesOpt{} : slices, bfield && !b_accuracy ? omega_b : nullptr,
 		                     b_accuracy ? nbco_bath{} : bath, corr, modes);
 	}
 	return rc;

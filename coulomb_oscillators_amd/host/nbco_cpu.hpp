@@ -271,6 +271,72 @@ inline void bond_order(const V3 *x, int n, double rmax, std::vector<int> &nb, st
 	bond_summary_fill(S, qsum, bonds, isolated, top, n, 3, sum);
 }
 
+// Crystalline particles of the positions x[0..n) for `nbco3 -cpu -solid`, by the rule of nbco_bond_solid (include/nbco.h) with the
+// functions of csrc/bond_order.hpp that the device kernels use: pass 1 leaves every particle's bond vector record (bond_vector), pass 2
+// takes the same neighbours again in index order, counts the bonds with bond_coherence > dmin into xi and adds the records into the
+// averaged order (bond_avg_add, the particle itself first; bond_qbar).  nb and xi get n values, qbar n pairs {q-bar_4, q-bar_6}.
+inline void bond_solid(const V3 *x, int n, double rmax, double dmin, int xi_min, std::vector<int> &nb, std::vector<int> &xi, std::vector<double> &qbar,
+                       nbco_solid_summary &sum)
+{
+	const double R2 = rmax * rmax;
+	nb.assign((size_t)n, 0);
+	xi.assign((size_t)n, 0);
+	qbar.assign(2 * (size_t)n, 0.0);
+	std::vector<double> vec((size_t)kBondVec * (size_t)n, 0.0);
+	int *nbp = nb.data(), *xip = xi.data();
+	double *qp = qbar.data(), *vp = vec.data();
+	// f(j) for the neighbours j of i, in index order
+	auto neighbours = [=](int i, auto &&f) {
+		for (int j = 0; j < n; ++j)
+		{
+			const double dx = (double)x[j].x - (double)x[i].x, dy = (double)x[j].y - (double)x[i].y, dz = (double)x[j].z - (double)x[i].z;
+			const double xx = dx * dx, yy = dy * dy, zz = dz * dz, xy = xx + yy, r2 = xy + zz;
+			if (0.0 < r2 && r2 < R2) f(j, dx, dy, dz, r2);
+		}
+	};
+	for_ranges(n, [=](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			double S[kBondSums3] = {}, v[kBondVec];
+			int cnt = 0;
+			neighbours(i, [&](int, double dx, double dy, double dz, double r2) { ++cnt; bond_add<3>(dx, dy, dz, r2, S); });
+			bond_vector(S, cnt, v);
+			nbp[i] = cnt;
+			std::copy(v, v + kBondVec, vp + (size_t)kBondVec * (size_t)i);
+		}
+	});
+	for_ranges(n, [=](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			const double *own = vp + (size_t)kBondVec * (size_t)i;
+			double T[kBondSums3] = {}, q[2];
+			bond_avg_add(own, T);
+			int solid = 0;
+			neighbours(i, [&](int j, double, double, double, double) {
+				const double *f = vp + (size_t)kBondVec * (size_t)j;
+				if (bond_coherence(own + kBondVec6, f + kBondVec6) > dmin) ++solid;
+				bond_avg_add(f, T);
+			});
+			bond_qbar(T, nbp[i], q);
+			xip[i] = solid;
+			qp[2 * (size_t)i] = q[0]; qp[2 * (size_t)i + 1] = q[1];
+		}
+	});
+	double qsum[2] = {0.0, 0.0};
+	long long bonds = 0, isolated = 0, solid_bonds = 0, n_solid = 0, top = 0;
+	for (int i = 0; i < n; ++i)
+	{
+		if (nb[(size_t)i] > 0) { qsum[0] += qbar[2 * (size_t)i]; qsum[1] += qbar[2 * (size_t)i + 1]; }
+		else ++isolated;
+		bonds += nb[(size_t)i];
+		solid_bonds += xi[(size_t)i];
+		if (xi[(size_t)i] >= xi_min) ++n_solid;
+		top = std::max<long long>(top, xi[(size_t)i]);
+	}
+	sum = nbco_solid_summary{};
+	bond_solid_summary_fill(qsum, bonds, isolated, solid_bonds, n_solid, top, n, dmin, xi_min, sum);
+}
+
 // The static structure factor of the positions x[0..n) for `nbco3 -cpu -sk`, by the rule of nbco_structure_factor (include/nbco.h) from
 // csrc/structure_factor.hpp, the header the device kernels use: the phases sk_phase(t_a), the powers and the products by sk_mul, the
 // term (e_y^iy e_z^iz) e_x^ix with one multiplication per ix.  rho gets K pairs {re, im}; returns the number of particles that counted.

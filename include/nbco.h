@@ -805,12 +805,57 @@ typedef struct nbco_bond_summary {
  * only) and walks it as that call does, with the harmonics of the bonds at the leaves.  In both forms this context's tree, rebuild
  * schedule, warm-select history, order tracking and nbco_kd_get_info stay as they were, and a following evaluation or diagnostic
  * returns the bits it would have returned.
- * Not offered: other l, the third-order invariants w_l, the neighbour-averaged q-bar_l and solid-bond counting (a second pass over
- * stored S_lm), Voronoi or k-nearest neighbours instead of a cutoff, a 2-D tree form, sharded runs, and a form on the tree of the
- * LAST EVALUATION, for the reason given at nbco_pair_hist_tree. */
+ * Not offered: other l, the third-order invariants w_l, Voronoi or k-nearest neighbours instead of a cutoff, a 2-D tree form, sharded
+ * runs, and a form on the tree of the LAST EVALUATION, for the reason given at nbco_pair_hist_tree.  (The neighbour-averaged q-bar_l
+ * and solid-bond counting, a second pass over stored S_lm: nbco_bond_solid below.) */
 int nbco_bond_order(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 int nbco_bond_order_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
 int nbco_2d_bond_order(nbco_ctx *c, const double *p, long long n, double rmax, int *nb_dev, double *q_dev, nbco_bond_summary *sum_host);
+/* nbco_bond_vectors / nbco_bond_solid and their _tree forms: WHICH particles are crystalline, and how many.  q6 of a single particle is
+ * noisy -- the distributions of a liquid and of a hot solid overlap -- so freezing, melting and grain growth are followed with two
+ * quantities of a second pass over the stored S_lm: the number of SOLID BONDS xi_i of ten Wolde, Ruiz-Montero and Frenkel (J. Chem.
+ * Phys. 104, 9932), the neighbours whose q6 vector is aligned with the particle's own, and the NEIGHBOUR-AVERAGED q-bar_l of Lechner and
+ * Dellago (J. Chem. Phys. 129, 114707).  Neighbours, p, n and rmax are those of nbco_bond_order, in 3-D.
+ * The bond vector record of a particle: 24 doubles (192 bytes).  [0, 9): q^_4m = S_4m / |S_4|, [9, 22): q^_6m = S_6m / |S_6|, with
+ * |S_l| = sqrt(sum_m S_lm^2); [22], [23]: a_4, a_6 with a_l = |S_l| / nb, so q_l = sqrt(4 pi / (2l+1)) a_l.  nb = 0 or a norm of 0
+ * leaves the 9 or 13 entries and a_l at 0, never NaN.
+ * Coherence of the bond i-j: d6 = (((e0 f0 + e1 f1) + e2 f2) + ... + e12 f12) over e = record_i[9..22), f = record_j[9..22), every
+ * product and every sum rounded once, left to right, no fused multiply-add: the same bits from either end, and what numpy gives with
+ * elementwise products and sequential adds.  The bond is SOLID iff d6 > dmin (a NaN is not); xi[i] is the number of solid bonds of i.
+ * Given the records, xi is an exact integer, the same in every form.  nbco_bond_coherence exports the rule (csrc/bond_order.hpp):
+ * host only, no GPU needed; vec_i and vec_j are whole records.  NBCO_ERR_ARG: a null pointer.
+ * Averaged order: T_lm(i) = a_l(i) q^_lm(i) + sum over the neighbours j of a_l(j) q^_lm(j) -- the particle first, then the neighbours in
+ * the order the kernel meets them -- and q-bar_l(i) = sqrt(4 pi / (2l+1) sum_m T_lm^2) / (nb[i] + 1); 0 for a particle without
+ * neighbours.  q-bar is specified to rounding only (|delta q-bar_l^2| below 1e-11 for nb <= 256 between the forms, given equal records).
+ * nbco_bond_vectors / _tree: pass 1 of nbco_bond_order / _tree -- the same neighbours, the same order of summation -- with the records
+ * as output: vec_dev receives n x 24 doubles, nb_dev n int32 (integer-equal to nbco_bond_order's), both in the caller's order in DEVICE
+ * memory; either may be NULL, not both.
+ * nbco_bond_solid / _tree: pass 2.  vec_dev: the records in the caller's order, read only; NULL: the call forms them itself by the same
+ * form (the tree form then builds one tree and walks it twice, the records staying in tree order in scratch) and returns exactly the
+ * bytes of the two-call sequence.  xi_dev receives n int32, qbar_dev n pairs {q-bar_4, q-bar_6} of doubles, nb_dev n int32, in the
+ * caller's order; any of nb_dev, xi_dev, qbar_dev and sum_host may be NULL, not all four.  The summary is a HOST struct; with it the call
+ * synchronises, without it the calls return as the evaluators do.  One record per wave of 64 particles and a sum of the records in a
+ * fixed order; no floating-point atomics anywhere: a second call returns the same bytes.
+ * Refused before any launch, the outputs untouched: what nbco_bond_order and its tree form refuse; dmin not finite; xi_min < 0.
+ * State: as nbco_bond_order.  The exact forms use only transient scratch of the context, the tree forms run on the private context; this
+ * context's tree, rebuild schedule, warm-select history, order tracking and nbco_kd_get_info stay as they were, and a following
+ * evaluation or diagnostic returns the bits it would have returned.
+ * Not offered: a coherence of l other than 6; the third-order invariants w_l; the largest connected crystalline cluster (connected
+ * components over the solid bonds); 2-D forms; sharded runs; a form on the tree of the LAST EVALUATION. */
+typedef struct nbco_solid_summary {
+	long long n, bonds, isolated;   /* as in nbco_bond_summary */
+	long long solid_bonds, n_solid; /* sum xi[i] (directed: even), #{xi[i] >= xi_min} */
+	int xi_max, xi_min;             /* the largest xi[i]; xi_min as given */
+	double dmin;                    /* as given */
+	double qbar_mean[2];            /* mean of q-bar_4 / q-bar_6 over the particles with nb > 0; 0 if none */
+} nbco_solid_summary;
+int nbco_bond_coherence(const double vec_i[24], const double vec_j[24], double *d6_host);
+int nbco_bond_vectors(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *vec_dev);
+int nbco_bond_vectors_tree(nbco_ctx *c, const float *p, long long n, double rmax, int *nb_dev, double *vec_dev);
+int nbco_bond_solid(nbco_ctx *c, const float *p, long long n, double rmax, const double *vec_dev, double dmin, int xi_min, int *nb_dev, int *xi_dev,
+                    double *qbar_dev, nbco_solid_summary *sum_host);
+int nbco_bond_solid_tree(nbco_ctx *c, const float *p, long long n, double rmax, const double *vec_dev, double dmin, int xi_min, int *nb_dev, int *xi_dev,
+                         double *qbar_dev, nbco_solid_summary *sum_host);
 /* nbco_structure_factor / nbco_2d_structure_factor: the static structure factor -- what Bragg scattering off a Coulomb crystal and the
  * spatial spectrum of a beam's density (micro-bunching, density waves) measure.  For the wave vectors of a grid, k = (ix kstep[0],
  * iy kstep[1], iz kstep[2]) with ix = 0..h[0], iy = -h[1]..h[1], iz = -h[2]..h[2] (the half space ix >= 0: rho_{-k} is the conjugate;
